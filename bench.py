@@ -1,14 +1,20 @@
 #!/usr/bin/env python
 """Benchmark of the Raindrop hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--config P19]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--config P19] [--full] [--dump-outputs DIR]
 
 Step = one training step of `Raindrop_v2` on one synthetic P19-shaped batch of B=256 samples PER
 GPU, inputs resident in HBM: forward + CrossEntropyLoss + backward (train mode, dropout 0.2)
 [+ flat-gradient all-reduce over RCCL when N>1] + Adam update.  `value` is whole-job samples/s.
 For N>1 launch with `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`.
 
-Extra objects on the JSON line (rank 0):
+A plain run sets up, warms up, times K steps and prints the line.  `--dump-outputs DIR` then writes what
+the last timed step computed (loss, logits, the gradients and the updated parameters, float32) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+With --full (rank 0) the line also carries everything measured beside the headline figure: the extra
+objects below, the host-side cost of a step, the module-default step, the fp32 / padded-layout /
+other-configuration child runs:
   roofline     -- the fused message-passing kernels (K1, forward+backward) timed with HIP events on
                   the launch stream, against the HBM roofline; algorithmic bytes per SURVEY.md 8(d):
                   B*32*F*K + 24*K^2 per fwd+bwd.
@@ -67,7 +73,30 @@ def parse():
                     help="the paper's branch (use_beta=True: top-K pruned, per-sample graph) as a captured step: prints tools/bench_use_beta.py's line")
     ap.add_argument("--no-graph", action="store_true",
                     help="eager autograd step instead of the hipGraph-captured static step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: CPU baseline, K1 / encoder rooflines, host cost "
+                         "of a step, module-default step, fp32 / padded-layout / other-configuration child runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, logits, gradients, updated parameters) as DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=0):
+    """arrays: [(name, tensor)] -> out_dir/<name>.npy in float32.  If they exceed `cap` bytes in all, every array larger than its
+    share of the cap is replaced by a fixed, seeded sample of its flattened elements (sorted indices, the same on every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = [(n, t.detach().float().cpu().numpy()) for n, t in arrays]
+    total = sum(a.nbytes for _, a in host)
+    share = cap // max(1, len(host))
+    for name, a in host:
+        if total > cap and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def _use_token_plan(cfg):
@@ -677,7 +706,7 @@ def other_configs(budget_s=420.0):
             out.append({"config": label, "error": "skipped: the time budget of the other-configuration runs (%.0f s) is spent" % budget_s})
             continue
         try:
-            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--lite"] + argv, capture_output=True,
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--lite"] + argv, capture_output=True,
                                  text=True, timeout=min(limit, left), env=env)
             ln = [x for x in res.stdout.splitlines() if x.startswith("{")]
             if not ln:
@@ -879,11 +908,14 @@ def main():
             dset.batch(idxs[fcount[0] % len(idxs)], out=fbuf)
             fcount[0] += 1
 
+    eager_logits = [None]
+
     def eager_step():
         if feed_next is not None:
             feed_next()
         flat.zero()
         out, _, _ = model(batch["src"], batch["static"], batch["times"], batch["lengths"])
+        eager_logits[0] = out
         loss = criterion(out, batch["y"])
         loss.backward()
         flat.finish()
@@ -1111,16 +1143,26 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(loss).item()
-    # host side of a step: what this process spends ENQUEUEING one step (graph replay(s), all-reduce calls and waits, the Adam launch),
-    # measured as 40 steps issued back to back without a synchronisation in between (the device runs behind; the queue absorbs them)
-    torch.cuda.synchronize()
-    th0 = time.perf_counter()
-    for _ in range(40):
-        step()
-    host_us = (time.perf_counter() - th0) / 40 * 1e6
-    torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed step receives after its last step: the loss, the logits, every live parameter's gradient
+        # and the parameters Adam left (both concatenated in synth.live_parameter_names order, padding of the flat buffers dropped)
+        logits = tstep.logits if step is graph_step else eager_logits[0]
+        dump_outputs(args.dump_outputs, [
+            ("loss", loss.reshape(1)), ("logits", logits),
+            ("grads", torch.cat([v.reshape(-1) for v in flat.views])),
+            ("params", torch.cat([p.detach().reshape(-1) for p in flat.params]))])
+    host_us = None
+    if args.full:
+        # host side of a step: what this process spends ENQUEUEING one step (graph replay(s), all-reduce calls and waits, the Adam
+        # launch), measured as 40 steps issued back to back without a synchronisation in between (the device runs behind)
+        torch.cuda.synchronize()
+        th0 = time.perf_counter()
+        for _ in range(40):
+            step()
+        host_us = (time.perf_counter() - th0) / 40 * 1e6
+        torch.cuda.synchronize()
     feed_check = None
-    if feed_next is not None and tstep is not None and world == 1:
+    if args.full and feed_next is not None and tstep is not None and world == 1:
         # --feed: the captured graph has just been replayed on a new batch every step.  Check that path against an eager recomputation:
         # a second captured step with dropout OFF is replayed on 4 further batches and every loss compared with the eager model's
         # (eval mode: padded layout, autograd surface) on the same buffers.
@@ -1144,7 +1186,7 @@ def main():
     # -> loss.backward() -> flat.finish() + Adam, the model's forward and backward as two hipGraphs behind the nn.Module surface.
     # Measured after the timed region, same batch; never allowed to cost the line.
     t_module = None
-    if world == 1 and not args.no_roofline and not args.lite:
+    if args.full and world == 1 and not args.no_roofline and not args.lite:
         try:
             model.graph_step = None                                       # the module's default: what an unchanged loop gets
             os.environ.pop("RD_MODULE_GRAPH", None)
@@ -1201,13 +1243,13 @@ def main():
                        "tuned": (None if tstep is None else {"rowgemm_rows32": tstep.tuned_rows32, "rowgemm_waves16": tstep.tuned_waves16,
                                                              "how": "capture-time A/B of the row-block kernels' workgroup shapes, per-variant "
                                                                     "times summed over the ranks (every rank runs the same variants)"}),
-                       "host_us_per_step": round(host_us, 1),
+                       "host_us_per_step": None if host_us is None else round(host_us, 1),
                        "global_batch": world * B, "parallelism": "dp%d" % world,
                        "grad_allreduce_bytes": flat.nbytes()},
         }
         # K1 roofline: rank 0's own launches (hipGraph replays in an isolated child process, else HIP events in
         # this one), after the timed region -- the other ranks are idle by then; never allowed to cost the line
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 line["roofline"] = roofline_isolated(args) or k1_roofline_events(model, cfg, batch)
                 if isinstance(line["roofline"], dict) and "encoder_layer" in line["roofline"]:
@@ -1239,7 +1281,7 @@ def main():
                         line["config"]["padded_layout_ms_per_step"] = padded_layout_ms(args)
                     if (cfg["name"], B) == ("P19", 256) and os.environ.get("RD_BENCH_OTHER", "1") != "0":
                         line["config"]["other_configs"] = other_configs()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, gs, B, args.cpu_reps)
             line["cpu_baseline"]["reference_o1"] = recorded_o1(cfg["name"], B)
             # what the baseline IS, where a reader of `config` sees it: the restatement (port) with dropout OFF on this

@@ -13,9 +13,12 @@ fixtures stay small.  Stored per model case:
 Each case also records how well the independent restatement (oracle O2) agreed with O1 when the
 fixture was made; the generator refuses to write a fixture if they disagree.
 """
+import glob
+import io
 import json
 import os
 import sys
+import zlib
 
 import numpy as np
 import torch
@@ -63,6 +66,37 @@ SCALED_CASES = [("p19_x3_sparse", "P19", 32, "sparse", 31, 32, 3.0)]
 # Trajectory: TRAJ_STEPS steps of the reference's own loop body (code/Raindrop.py:319-324: forward, zero_grad, CrossEntropyLoss,
 # backward, Adam step) on TRAJ_STEPS different batches, dropout 0; lr 1e-3 (10x the script's) so that 20 steps MOVE the weights.
 TRAJ_STEPS, TRAJ_LR, TRAJ_B = 20, 1e-3, 32
+
+
+PART_LIMIT = 900 * 1024          # bytes per fixture file: the repository keeps every file below 1 MiB
+
+
+def save_parts(path, out, limit=PART_LIMIT):
+    """np.savez_compressed of `out`, spread over `path`, `<stem>.part2.npz`, `<stem>.part3.npz`, .. so that no file exceeds `limit`
+    bytes (members packed in order by their deflated size); tests/helpers.load_golden merges the parts back.  Returns the paths."""
+    stem = path[:-len(".npz")]
+    for old in glob.glob(stem + ".part*.npz"):
+        os.remove(old)
+
+    def deflated(v):
+        buf = io.BytesIO()
+        np.save(buf, np.asanyarray(v), allow_pickle=False)
+        return len(zlib.compress(buf.getvalue())) + 256
+
+    parts, cur, size = [], {}, 0
+    for k, v in out.items():
+        n = deflated(v)
+        if cur and size + n > limit:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += n
+    parts.append(cur)
+    paths = [path] + ["%s.part%d.npz" % (stem, i + 2) for i in range(len(parts) - 1)]
+    for p, d in zip(paths, parts):
+        np.savez_compressed(p, **d)
+    assert all(os.path.getsize(p) < 1 << 20 for p in paths), [(p, os.path.getsize(p)) for p in paths]
+    return paths
 
 
 def traj_case(name="p19_traj20", cfg_name="P19", kind="sparse", pseed=41, bseed0=300):
@@ -117,10 +151,10 @@ def traj_case(name="p19_traj20", cfg_name="P19", kind="sparse", pseed=41, bseed0
         out["heldgradstride/" + n] = np.int64(st)
         out["heldgradnorm/" + n] = np.float64(g_.double().norm().item())
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **out)
+    paths = save_parts(path, out)
     print("%-12s %d steps, loss %.5f -> %.5f, moved %s -> %s (%.1f KB)" % (
         name, TRAJ_STEPS, losses[0], losses[-1], {n.split(".")[-2] if "." in n else n: "%.3g" % out["wmoved/" + n] for n in live[:4]},
-        os.path.basename(path), os.path.getsize(path) / 1024))
+        " + ".join(os.path.basename(p) for p in paths), sum(os.path.getsize(p) for p in paths) / 1024))
 
 
 def strided(t, n=SAMPLE, full_limit=70_000):
@@ -200,10 +234,10 @@ def model_case(name, cfg_name, B, kind, pseed, bseed, use_beta=False, scale=1.0)
         out["gradsum/" + n] = np.float64(g.double().sum().item())
         out["gradnorm/" + n] = np.float64(g.double().norm().item())
     path = os.path.join(HERE, name + ".npz")
-    np.savez_compressed(path, **out)
+    paths = save_parts(path, out)
     print("%-12s logits %s loss %.6f  O2-vs-O1 logit %.2e grad %.2e  -> %s (%.1f KB)" % (
         name, tuple(logits.shape), loss.item(), e_logit, e_grad, os.path.basename(path),
-        os.path.getsize(path) / 1024))
+        sum(os.path.getsize(p) for p in paths) / 1024))
 
 
 def operator_cases():

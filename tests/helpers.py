@@ -1,4 +1,5 @@
 """Shared test helpers: golden loading, model construction mirrored on both sides."""
+import glob
 import json
 import os
 
@@ -15,7 +16,15 @@ BETA_CASES = ["p19_beta_sparse", "p19_beta_ones", "p12_beta_sparse", "wide80_bet
 
 
 def load_golden(name):
-    g = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    """{member: array} of a model / trajectory fixture: `<name>.npz` merged with its `<name>.partN.npz` files, if any (large
+    fixtures are spread over several files, make_goldens.save_parts), and its decoded meta."""
+    paths = [os.path.join(GOLDEN, name + ".npz")]
+    parts = glob.glob(os.path.join(GOLDEN, glob.escape(name) + ".part*.npz"))
+    paths += sorted(parts, key=lambda p: int(p[:-len(".npz")].rsplit(".part", 1)[1]))
+    g = {}
+    for path in paths:
+        with np.load(path, allow_pickle=False) as z:
+            g.update((k, z[k]) for k in z.files)
     meta = json.loads(str(g["meta"]))
     return g, meta
 

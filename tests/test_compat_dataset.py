@@ -1,6 +1,6 @@
 """CPU: the synthetic dataset writer produces files the REFERENCE'S OWN loader and normaliser accept
 (`code/utils_rd.py:23-146,221-257`), with the tensor layout the training loop then feeds to the
-model (`code/Raindrop.py:232-238,310-317`).  Needs the reference tree; skipped on the GPU box."""
+model (`code/Raindrop.py:232-238,310-317`).  The loader tests need the reference tree; the workspace layout does not."""
 import importlib.util
 import os
 
@@ -10,7 +10,7 @@ import pytest
 from oracle import ref_loader
 from raindrop_amd import compat_runner, synth
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
+needs_reference = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
 
 
 def _utils_rd():
@@ -21,6 +21,7 @@ def _utils_rd():
     return mod
 
 
+@needs_reference
 @pytest.mark.parametrize("dataset", ["P19", "P12"])
 def test_reference_loader_accepts_synthetic_dataset(tmp_path, dataset):
     u = _utils_rd()
@@ -48,6 +49,7 @@ def test_reference_loader_accepts_synthetic_dataset(tmp_path, dataset):
     assert np.array_equal(P[:, :, F:].numpy() > 0, raw != 0)
 
 
+@needs_reference
 def test_reference_loader_accepts_synthetic_pam_dataset(tmp_path):
     """PAM (BASELINE.json configs[0]): bare [T,F] records, no static features, 8 classes; the script's PAM branch
     (code/Raindrop.py:196-204) normalises with `tensorize_normalize_other` (code/utils_rd.py:243-257), which also invents the time
@@ -75,6 +77,7 @@ def test_reference_loader_accepts_synthetic_pam_dataset(tmp_path):
 
 
 def test_workspace_layout(tmp_path):
+    # the two script files are symbolic links into the reference tree: made (and checked) whether or not the tree is there
     code = compat_runner.make_workspace(str(tmp_path), "P19", 40, ref_loader.reference_root())
     assert os.path.islink(os.path.join(code, "Raindrop.py")) and os.path.islink(os.path.join(code, "utils_rd.py"))
     shim = open(os.path.join(code, "models_rd.py")).read()

@@ -1,7 +1,7 @@
 """Batch feed: host index plan vs the oracle / the reference's own lines (CPU), and the
 device gather vs numpy fancy indexing, bit for bit (GPU)."""
 import os
-import re
+import sys
 
 import numpy as np
 import pytest
@@ -9,8 +9,6 @@ import torch
 
 from oracle import feed as O
 from raindrop_amd import feed, synth
-
-REF = "/root/reference/code/Raindrop.py"
 
 
 @pytest.mark.parametrize("strategy,bs", [(2, 128), (2, 6), (3, 128), (1, 8)])
@@ -29,79 +27,49 @@ def test_index_plan_matches_oracle(strategy, bs):
         assert len(got) == min((y == 0).sum() // (bs // 2), 3 * (y == 1).sum() // (bs // 2))
 
 
-@pytest.mark.skipif(not os.path.isfile(REF), reason="reference tree not present (GPU box)")
+RECORDS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_records.npz")
+
+
+def _reference_batches(name):
+    """(labels, batch size, numpy seed, the reference's batches) of a case of tests/golden/make_reference_records.py FEED_CASES: the
+    batches as recorded from the reference's OWN statements (the index bookkeeping of `code/Raindrop.py:261-307`); where the
+    reference tree is present they are re-run from the script and must equal the record."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_reference_records as mk
+    _, ls, n, rate, bs, seed, epochs = next(c for c in mk.FEED_CASES if c[0] == name)
+    ytrain = mk.feed_labels(ls, n, rate)
+    with np.load(RECORDS) as z:
+        rec = z[name]
+    if mk.script_available():
+        assert np.array_equal(mk.feed_reference_batches(ytrain, bs, seed, epochs), rec)
+    return ytrain, bs, seed, list(rec)
+
+
 def test_index_plan_matches_reference_script_lines():
-    """Pins the oracle: executes the reference's OWN statements for the strategy-2 plan (the index
-    bookkeeping of `code/Raindrop.py:261-307`, extracted at test time, never copied into the repo)."""
-    src = open(REF).read().splitlines()
-    want = [r"^\s*idx_0 = np\.where\(ytrain == 0\)\[0\]", r"^\s*idx_1 = np\.where\(ytrain == 1\)\[0\]",
-            r"^\s*n0, n1 = len\(idx_0\), len\(idx_1\)", r"^\s*expanded_idx_1 = np\.concatenate",
-            r"^\s*expanded_n1 = len\(expanded_idx_1\)", r"^\s*K0 = n0 //", r"^\s*K1 = expanded_n1 //",
-            r"^\s*n_batches = np\.min\(\[K0, K1\]\)", r"^\s*np\.random\.shuffle\(expanded_idx_1\)", r"^\s*I1 = expanded_idx_1",
-            r"^\s*np\.random\.shuffle\(idx_0\)", r"^\s*I0 = idx_0"]
-    body = []
-    for pat in want:
-        hits = [ln.strip() for ln in src if re.match(pat, ln)]
-        assert hits, pat
-        body.append(hits[0])
-    per_batch = [ln.strip() for ln in src if re.match(r"^\s*idx[01]_batch = I[01]\[n \* int\(batch_size / 2\)", ln)]
-    cat = [ln.strip() for ln in src if re.match(r"^\s*idx = np\.concatenate\(\[idx0_batch, idx1_batch\], axis=0\)", ln)]
-    assert len(per_batch) == 2 and cat
-    rng = np.random.default_rng(5)
-    ytrain = (rng.random(777) < 0.07).astype(np.int64)
-    env = {"np": np, "ytrain": ytrain, "batch_size": 128}
-    np.random.seed(23)
-    exec("\n".join(body), env)
-    ref_batches = []
-    for n in range(int(env["n_batches"])):
-        env["n"] = n
-        exec("\n".join(per_batch + [cat[0]]), env)
-        ref_batches.append(env["idx"].copy())
-    np.random.seed(23)
-    mine = O.epoch_batches(ytrain, 128, 2)
+    """Pins the oracle: the reference's OWN statements for the strategy-2 plan, one epoch (recorded; re-run from the script
+    where the reference tree is present)."""
+    ytrain, bs, seed, ref_batches = _reference_batches("feed_plan_b128")
+    np.random.seed(seed)
+    mine = O.epoch_batches(ytrain, bs, 2)
     assert len(mine) == len(ref_batches) > 0
     for a, b in zip(mine, ref_batches):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.skipif(not os.path.isfile(REF), reason="reference tree not present (GPU box)")
 def test_epoch_planner_matches_reference_script_over_several_epochs():
     """The script shuffles `expanded_idx_1` / `idx_0` IN PLACE every epoch (`code/Raindrop.py:292-296`): epoch k's order is
     a permutation of epoch k-1's.  `feed.EpochPlanner` must reproduce the batches of every epoch, not only the first;
-    checked against the reference's own statements, extracted at test time and executed in the script's nesting."""
-    src = open(REF).read().splitlines()
-    def grab(pat):
-        hits = [ln.strip() for ln in src if re.match(pat, ln)]
-        assert hits, pat
-        return hits[0]
-    setup = [grab(p) for p in (r"^\s*idx_0 = np\.where\(ytrain == 0\)\[0\]", r"^\s*idx_1 = np\.where\(ytrain == 1\)\[0\]",
-                               r"^\s*n0, n1 = len\(idx_0\), len\(idx_1\)", r"^\s*expanded_idx_1 = np\.concatenate",
-                               r"^\s*expanded_n1 = len\(expanded_idx_1\)", r"^\s*K0 = n0 //", r"^\s*K1 = expanded_n1 //",
-                               r"^\s*n_batches = np\.min\(\[K0, K1\]\)")]
-    per_epoch = [grab(p) for p in (r"^\s*np\.random\.shuffle\(expanded_idx_1\)", r"^\s*I1 = expanded_idx_1",
-                                   r"^\s*np\.random\.shuffle\(idx_0\)", r"^\s*I0 = idx_0")]
-    per_batch = [ln.strip() for ln in src if re.match(r"^\s*idx[01]_batch = I[01]\[n \* int\(batch_size / 2\)", ln)]
-    per_batch.append(grab(r"^\s*idx = np\.concatenate\(\[idx0_batch, idx1_batch\], axis=0\)"))
-    rng = np.random.default_rng(8)
-    ytrain = (rng.random(900) < 0.08).astype(np.int64)
-    env = {"np": np, "ytrain": ytrain, "batch_size": 64}
-    np.random.seed(31)
-    exec("\n".join(setup), env)
-    ref = []
-    for epoch in range(3):
-        exec("\n".join(per_epoch), env)
-        for n in range(int(env["n_batches"])):
-            env["n"] = n
-            exec("\n".join(per_batch), env)
-            ref.append(env["idx"].copy())
-    np.random.seed(31)
-    planner = feed.EpochPlanner(ytrain, batch_size=64, strategy=2)
+    checked against the reference's own statements executed in the script's nesting over three epochs (recorded; re-run from
+    the script where the reference tree is present)."""
+    ytrain, bs, seed, ref = _reference_batches("feed_epochs3_b64")
+    np.random.seed(seed)
+    planner = feed.EpochPlanner(ytrain, batch_size=bs, strategy=2)
     mine = [b for _ in range(3) for b in planner.next_epoch()]
     assert len(mine) == len(ref) == 3 * planner.n_batches > 0
     for a, b in zip(mine, ref):
         assert np.array_equal(a, b)
-    np.random.seed(31)
-    first = feed.epoch_index_plan(ytrain, 64, 2)                 # the one-epoch helper: first epoch only
+    np.random.seed(seed)
+    first = feed.epoch_index_plan(ytrain, bs, 2)                 # the one-epoch helper: first epoch only
     assert all(np.array_equal(a, b) for a, b in zip(first, ref[: len(first)]))
 
 

@@ -2,11 +2,11 @@
 # the bench lines of every configuration (rounds 4-5) (P19 full line; P12 both bf16 modes at B = 256 with rooflines; PAM; SYN256)
 out=$GRAFT_REPO_ROOT/gpurun_out/$1; mkdir -p $out
 cd $GRAFT_REPO_ROOT
-[ -n "$SKIP_P19" ] || timeout 600 python bench.py --steps 50 --warmup 10 > $out/bench_P19.json 2> $out/bench_P19.err
-timeout 600 python bench.py --config P12 --batch 256 --precision bf16 --steps 30 --warmup 5 --no-cpu-baseline > $out/bench_P12_bf16.json 2> $out/bench_P12_bf16.err
-timeout 600 python bench.py --config P12 --batch 256 --precision bf16x3 --steps 30 --warmup 5 --no-cpu-baseline > $out/bench_P12_bf16x3.json 2> $out/bench_P12_bf16x3.err
-timeout 600 python bench.py --config PAM --batch 64 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_PAM.json 2> $out/bench_PAM.err
-timeout 600 python bench.py --config SYN256 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_SYN256.json 2> $out/bench_SYN256.err
+[ -n "$SKIP_P19" ] || timeout 600 python bench.py --full --steps 50 --warmup 10 > $out/bench_P19.json 2> $out/bench_P19.err
+timeout 600 python bench.py --full --config P12 --batch 256 --precision bf16 --steps 30 --warmup 5 --no-cpu-baseline > $out/bench_P12_bf16.json 2> $out/bench_P12_bf16.err
+timeout 600 python bench.py --full --config P12 --batch 256 --precision bf16x3 --steps 30 --warmup 5 --no-cpu-baseline > $out/bench_P12_bf16x3.json 2> $out/bench_P12_bf16x3.err
+timeout 600 python bench.py --full --config PAM --batch 64 --steps 20 --warmup 5 --no-cpu-baseline > $out/bench_PAM.json 2> $out/bench_PAM.err
+timeout 600 python bench.py --full --config SYN256 --batch 16 --steps 10 --warmup 3 --no-cpu-baseline > $out/bench_SYN256.json 2> $out/bench_SYN256.err
 for f in P19 P12_bf16 P12_bf16x3 PAM SYN256; do python - <<PY
 import json
 try:

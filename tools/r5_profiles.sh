@@ -31,7 +31,7 @@ unset RD_RG_ROWS32 RD_RG_WAVES16
 cp $out/k1_pmc_traffic.json raindrop_amd/k1_pmc_traffic.json
 cp $out/enc_pmc_traffic.json raindrop_amd/enc_pmc_traffic.json
 cp $out/k1_rocprof.json raindrop_amd/k1_rocprof.json
-timeout 400 python bench.py --steps 50 --warmup 10 > $out/bench_P19.json 2> $out/bench_P19.err
+timeout 400 python bench.py --full --steps 50 --warmup 10 > $out/bench_P19.json 2> $out/bench_P19.err
 python - <<PY
 import json
 d=json.loads(open("$out/bench_P19.json").read().strip().splitlines()[-1])
