@@ -463,9 +463,28 @@ int rd_graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, 
                       int64_t row_stride, const float* edge_weights, int64_t w_bstride, const float* beta_save,
                       const int32_t* kept, const float* dout, float* dV, float* dH, float* dmap_part, float* dw, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* rd_graph_beta_bwd with a second cotangent: dalpha [B,Kk], the gradient that arrives at alpha_out (the structure distance's,
+ * code/models_rd.py:345-346; the reference's alpha is differentiable).  With alpha[b,q] = (1/T) sum_t beta[b,tgt,t] * w[b,e]
+ * (e = kept[b,q]) it adds dbeta[b,n,t] += (1/T) sum_{q: tgt = n} dalpha[b,q] w[b,e] -- the same for every t, carried on to dH and
+ * dmap_part like the rest of dbeta -- and dw[b,e] += dalpha[b,q] (1/T) sum_t beta[b,tgt,t].  dalpha NULL: exactly
+ * rd_graph_beta_bwd.  Both forms (LDS-staged and workspace); the rounds 2-5 kernels (env RD_BETA_V1=1) refuse a non-NULL dalpha
+ * with RD_EUNSUPPORTED.  No atomics: two calls give the same bits. */
+int rd_graph_beta_bwd_alpha(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V, const float* H,
+                            const float* map_weights, const float* p_t, int64_t pt_bstride, const int64_t* edge_index,
+                            int64_t row_stride, const float* edge_weights, int64_t w_bstride, const float* beta_save,
+                            const int32_t* kept, const float* dout, const float* dalpha, float* dV, float* dH, float* dmap_part,
+                            float* dw, void* workspace, size_t workspace_bytes, void* stream);
 /* code/models_rd.py:345-346: distance = mean(cdist(alpha_all.T, alpha_all.T, p=2)) for alpha_all [E,B] (one column of edge
  * scores per sample); workspace B floats.  Identically 0 on the shipped path (equal columns); evaluated here in general. */
 int rd_structure_distance(int32_t E, int32_t B, const float* alpha_all, float* workspace, float* distance, void* stream);
+/* Its backward: grad = the device scalar d loss / d distance (read on the device: capturable) -> dalpha_all [E,B],
+ *   dalpha_all[e,b] = sum_c C[b,c] (alpha_all[e,b] - alpha_all[e,c]),  C[b,c] = 2 grad / (B^2 D[b,c]),  D[b,c] = ||column b - column c||,
+ * C = 0 where D = 0 (torch's cdist convention: B = 1 and identical columns give exact zeros, no NaN).  Any E (0 included) and B;
+ * fp32, fixed-order sums, no atomics.  workspace: rd_structure_distance_bwd_workspace_bytes(E, B) bytes (B*B floats, 4-byte
+ * aligned), caller-owned. */
+size_t rd_structure_distance_bwd_workspace_bytes(int32_t E, int32_t B);
+int rd_structure_distance_bwd(int32_t E, int32_t B, const float* alpha_all, const float* grad, void* workspace, size_t workspace_bytes,
+                              float* dalpha_all, void* stream);
 
 /* ---- building blocks of the paper-faithful sensor stage: Raindrop_v2(use_beta=True), i.e. code/models_rd.py:313-343 with the
  * literal at :317 flipped.  Layer 1 prunes a different edge set per sample, so the stage is composed instead of fused:

@@ -118,7 +118,11 @@ SIGNATURES = {
                           + [_P] * 5 + [_P, c_size_t, _P]),
     "rd_graph_beta_bwd": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64]
                           + [_P] * 7 + [_P, c_size_t, _P]),
+    "rd_graph_beta_bwd_alpha": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64]
+                                + [_P] * 8 + [_P, c_size_t, _P]),
     "rd_structure_distance": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
+    "rd_structure_distance_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "rd_structure_distance_bwd": (c_int32, [c_int32, c_int32, _P, _P, _P, c_size_t, _P, _P]),
     "rd_prep_stats_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
     "rd_prep_stats": (c_int32, [ctypes.c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "rd_prep_mask_normalize": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P]),

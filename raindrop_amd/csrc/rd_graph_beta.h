@@ -17,6 +17,7 @@ struct BetaArgs {
   int32_t* kept;                         // [B][Kk] original edge ids in pruning order (for backward)
   // backward
   const float* dout; float *dV, *dH, *dmap_part, *dw;   // dmap_part [B,N,16]; dw [B,E] or null
+  const float* dalpha;                   // [B][Kk] cotangent of alpha_out (the structure distance's), or null: none
   int B, N, K, T, d, E, Kk;
 };
 

@@ -326,14 +326,14 @@ size_t lds2_fwd(int N, int T, int K, int P2, int Kk, bool stage_v) {
   auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
   return r((size_t)N * T * 4) + r((size_t)P2 * 8) + 6 * r((size_t)Kk * 4) + r((size_t)(N + 1) * 4) + (stage_v ? r((size_t)N * K * 4) : 0);
 }
-size_t lds2_bwd(int N, int Tc, int Kk) {
+size_t lds2_bwd(int N, int Tc, int Kk, bool with_alpha = false) {
   auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
   return 5 * r((size_t)N * Tc * 4) + 7 * r((size_t)Kk * 4) + 2 * r((size_t)(N + 1) * 4) + r((size_t)N * 16 * 4) + r((size_t)Kk * 4) +
-         2 * r((size_t)Kk * Tc * 4);
+         2 * r((size_t)Kk * Tc * 4) + (with_alpha ? r((size_t)Kk * 4) + 2 * r((size_t)N * 4) : 0);
 }
-int bwd2_chunk(int N, int T, int Kk) {       // steps per pass: the largest that fits, then evened out over the passes
+int bwd2_chunk(int N, int T, int Kk, bool with_alpha = false) {   // steps per pass: the largest that fits, then evened out over the passes
   int tc = T;
-  while (tc > 1 && lds2_bwd(N, tc, Kk) > 160 * 1024) --tc;
+  while (tc > 1 && lds2_bwd(N, tc, Kk, with_alpha) > 160 * 1024) --tc;
   const int np = (T + tc - 1) / tc;
   return (T + np - 1) / np;
 }
@@ -445,6 +445,11 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2)
   }
 }
 
+// ALPHA: the alpha_out cotangent a.dalpha [B][Kk] (the structure distance's, code/models_rd.py:345-346) is added:
+//   alpha[q] = (sum_t beta[tgt][t] * w) / T  ->  dbeta[n][t] += (sum over kept edges q into n of dalpha[q] * w[q]) / T (the same for
+//   every step: formed once from the target lists, before the chunks), d w[q] += dalpha[q] * (sum_t beta[tgt][t]) / T.
+// The ALPHA = false instantiation is the operator's own backward, unchanged.
+template <bool ALPHA>
 __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -459,6 +464,9 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
   float* dmacc = (float*)take((size_t)N * 16 * 4); float* dwacc = (float*)take((size_t)Kk * 4);
   float* W = (float*)take((size_t)Kk * Tc * 4); float* DG = (float*)take((size_t)Kk * Tc * 4);
   int* ltg = (int*)take((size_t)Kk * 4); float* lkw = (float*)take((size_t)Kk * 4);      // source-list order (as in the forward)
+  float* dal = ALPHA ? (float*)take((size_t)Kk * 4) : nullptr;                               // dalpha of the kept edges
+  float* cbt = ALPHA ? (float*)take((size_t)N * 4) : nullptr;                                // per-target dbeta term
+  float* bsum = ALPHA ? (float*)take((size_t)N * 4) : nullptr;                               // sum_t beta[n][t], over the chunks
   const float* H = a.H + (size_t)b * N * T * 32;
   const float* V = a.V + (size_t)b * N * K;
   const float* dout = a.dout + (size_t)b * N * K;
@@ -468,12 +476,20 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
     const int e = a.kept[(size_t)b * Kk + q];
     ksrc[q] = node_of(a.ei[e], N); ktgt[q] = node_of(a.ei[a.ei_stride + e], N); kw[q] = w[e];
     dwacc[q] = 0.f;
+    if (ALPHA) dal[q] = a.dalpha[(size_t)b * Kk + q];
   }
   for (int i = tid; i < N * 16; i += GB2_THR) dmacc[i] = 0.f;
   __syncthreads();
   build_lists2(ksrc, Kk, N, soff, slist, tid);
   build_lists2(ktgt, Kk, N, toff, tlist, tid);
   for (int q = tid; q < Kk; q += GB2_THR) { const int e = slist[q]; ltg[q] = ktgt[e]; lkw[q] = kw[e]; }
+  if (ALPHA)
+    for (int n = tid; n < N; n += GB2_THR) {                         // kept edges into n in pruning order
+      float c = 0.f;
+      for (int q = toff[n]; q < toff[n + 1]; ++q) { const int e = tlist[q]; c += dal[e] * kw[e]; }
+      cbt[n] = c / (float)T;
+      bsum[n] = 0.f;
+    }
   __syncthreads();
   float* dV = a.dV + (size_t)b * N * K;
   float* dH = a.dH + (size_t)b * N * T * 32;
@@ -530,6 +546,7 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
         s += kw[e] * DG[e * Tc + tt];
       }
       *reinterpret_cast<float4*>(dV + (size_t)n * K + 4 * t) = acc;
+      if (ALPHA) s += cbt[n];
       const float db = s * (1.0f / 32.0f);
       float* ph = dH + ((size_t)n * T + t) * 32;
 #pragma unroll
@@ -557,6 +574,12 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
         for (int tt = 0; tt < tc; ++tt) s += DG[q * Tc + tt] * beta[ktgt[q] * Tc + tt];
         dwacc[q] = s;
       }
+    if (ALPHA && a.dw)
+      for (int n = tid; n < N; n += GB2_THR) {                       // same thread for a given n in every pass: steps in order
+        float s = bsum[n];
+        for (int tt = 0; tt < tc; ++tt) s += beta[n * Tc + tt];
+        bsum[n] = s;
+      }
     __syncthreads();
   }
   for (int i = tid; i < N * 16; i += GB2_THR) a.dmap_part[(size_t)b * N * 16 + i] = dmacc[i];
@@ -564,8 +587,27 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
     float* dw = a.dw + (size_t)b * a.E;
     for (int e = tid; e < a.E; e += GB2_THR) dw[e] = 0.f;
     __syncthreads();
-    for (int q = tid; q < Kk; q += GB2_THR) dw[a.kept[(size_t)b * Kk + q]] = dwacc[q];
+    for (int q = tid; q < Kk; q += GB2_THR)
+      dw[a.kept[(size_t)b * Kk + q]] = ALPHA ? dwacc[q] + dal[q] * (bsum[ktgt[q]] / (float)T) : dwacc[q];
   }
+}
+
+// squared L2 distance between columns b and c of alpha_all [E, B], rows in order
+__device__ __forceinline__ float col_dist2(const float* __restrict__ alpha, int E, int B, int b, int c) {
+  float s = 0.f;
+  // (same order of sums as rounds 2-5; the loads of eight edges are requested before the first is consumed: the loop was one
+  // dependent L2 round trip per edge -- 141 us at B = 256, E = 578, a quarter of the time the use_beta step spent outside the
+  // graph operator)
+  int e = 0;
+  for (; e + 8 <= E; e += 8) {
+    float xb[8], xc[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { xb[u] = alpha[(size_t)(e + u) * B + b]; xc[u] = alpha[(size_t)(e + u) * B + c]; }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) { const float df = xb[u] - xc[u]; s += df * df; }
+  }
+  for (; e < E; ++e) { const float df = alpha[(size_t)e * B + b] - alpha[(size_t)e * B + c]; s += df * df; }
+  return s;
 }
 
 // mean pairwise L2 distance between the B columns of alpha_all [E, B]  (code/models_rd.py:345-346: cdist(a.T, a.T).mean()).
@@ -574,22 +616,7 @@ __global__ __launch_bounds__(256) void k_distance_rows(const float* __restrict__
   __shared__ float red[256];
   const int b = blockIdx.x;
   float acc = 0.f;
-  for (int c = threadIdx.x; c < B; c += 256) {
-    float s = 0.f;
-    // (same order of sums as rounds 2-5; the loads of eight edges are requested before the first is consumed: the loop was one
-    // dependent L2 round trip per edge -- 141 us at B = 256, E = 578, a quarter of the time the use_beta step spent outside the
-    // graph operator)
-    int e = 0;
-    for (; e + 8 <= E; e += 8) {
-      float xb[8], xc[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { xb[u] = alpha[(size_t)(e + u) * B + b]; xc[u] = alpha[(size_t)(e + u) * B + c]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const float df = xb[u] - xc[u]; s += df * df; }
-    }
-    for (; e < E; ++e) { const float df = alpha[(size_t)e * B + b] - alpha[(size_t)e * B + c]; s += df * df; }
-    acc += sqrtf(s);
-  }
+  for (int c = threadIdx.x; c < B; c += 256) acc += sqrtf(col_dist2(alpha, E, B, b, c));
   red[threadIdx.x] = acc;
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
@@ -603,6 +630,43 @@ __global__ __launch_bounds__(256) void k_distance_reduce(const float* __restrict
   __syncthreads();
   for (int o = 128; o > 0; o >>= 1) { if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
   if (threadIdx.x == 0) *out = red[0] / ((float)B * (float)B);
+}
+
+// Backward of distance = mean_{b,c} D[b][c], D[b][c] = ||alpha[:, b] - alpha[:, c]||, for the gradient g that arrives at it (read
+// from device memory: capturable):  dalpha[e][b] = sum_c C[b][c] (alpha[e][b] - alpha[e][c]),  C[b][c] = 2 g / (B^2 D[b][c]),
+// C = 0 where D == 0 (torch's cdist convention: B = 1 and identical samples give exactly 0, never NaN).
+// k_distance_coef: C [B][B] into the workspace, D formed as k_distance_rows forms it.  D[b][c] and D[c][b] are the same bits (the
+// squared differences are), so C is symmetric and k_distance_bwd reads C[c][b] -- consecutive b across a wave.
+__global__ __launch_bounds__(256) void k_distance_coef(const float* __restrict__ alpha, int E, int B, const float* __restrict__ grad,
+                                                       float* __restrict__ C) {
+  const int b = blockIdx.x;
+  const float coef = 2.0f * grad[0] / ((float)B * (float)B);
+  for (int c = threadIdx.x; c < B; c += 256) {
+    const float d = sqrtf(col_dist2(alpha, E, B, b, c));
+    C[(size_t)b * B + c] = d > 0.f ? coef / d : 0.f;
+  }
+}
+// One thread per (e, b); the sum over the samples c in eight fixed partial sums (c mod 8, c ascending), added as a tree: the terms
+// have both signs and largely cancel, and one running sum over B = 256 of them loses ~6e-7 of the result's max-norm (1.5e-7 this
+// way); the eight also give the loop eight independent chains.  No atomics.
+__global__ __launch_bounds__(256) void k_distance_bwd(const float* __restrict__ alpha, long EB, int B, const float* __restrict__ C,
+                                                      float* __restrict__ dalpha) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < EB; i += (long)gridDim.x * 256) {
+    const long e = i / B;
+    const int b = (int)(i - e * B);
+    const float* row = alpha + (size_t)e * B;
+    const float x = row[b];
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    int c = 0;
+    for (; c + 8 <= B; c += 8) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s[u] += C[(size_t)(c + u) * B + b] * (x - row[c + u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (c + u < B) s[u] += C[(size_t)(c + u) * B + b] * (x - row[c + u]);
+    dalpha[i] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
+  }
 }
 
 int next_pow2(int x) { return beta_next_pow2(x); }
@@ -672,11 +736,11 @@ extern "C" int rd_graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int
   return check_launch("k_graph_beta_fwd");
 }
 
-extern "C" int rd_graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
-                                 const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
-                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
-                                 const float* beta_save, const int32_t* kept, const float* dout, float* dV, float* dH,
-                                 float* dmap_part, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+static int graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V, const float* H,
+                          const float* map_weights, const float* p_t, int64_t pt_bstride, const int64_t* edge_index,
+                          int64_t row_stride, const float* edge_weights, int64_t w_bstride, const float* beta_save,
+                          const int32_t* kept, const float* dout, const float* dalpha, float* dV, float* dH, float* dmap_part,
+                          float* dw, void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_beta(B, N, K, T, d_ob, E);
   if (rc) return rc;
   if (B == 0) return RD_OK;
@@ -685,16 +749,23 @@ extern "C" int rd_graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int
   BetaArgs a{};
   a.V = V; a.H = H; a.map_w = map_weights; a.p_t = p_t; a.pt_bstride = pt_bstride; a.ei = edge_index; a.ei_stride = row_stride;
   a.w = edge_weights; a.w_bstride = w_bstride; a.beta_save = const_cast<float*>(beta_save); a.kept = const_cast<int32_t*>(kept);
-  a.dout = dout; a.dV = dV; a.dH = dH; a.dmap_part = dmap_part; a.dw = dw;
+  a.dout = dout; a.dV = dV; a.dH = dH; a.dmap_part = dmap_part; a.dw = dw; a.dalpha = dalpha;
   a.B = B; a.N = N; a.K = K; a.T = T; a.d = d_ob; a.E = E; a.Kk = rd_graph_beta_kept(E);
   if (!fits_lds(N, T, E, true)) return beta_large_bwd(a, workspace, workspace_bytes, (hipStream_t)stream);
   const int Kc = a.Kk > 0 ? a.Kk : 1;
-  if (!beta_v1() && (K & 3) == 0 && lds2_bwd(N, 1, Kc) <= 160 * 1024) {
-    const int Tc2 = bwd2_chunk(N, T, Kc);
-    RD_LDS_ATTR(k_graph_beta_bwd2, 160 * 1024);
-    hipLaunchKernelGGL(k_graph_beta_bwd2, dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc), (hipStream_t)stream, a, Tc2);
+  const bool al = dalpha != nullptr;
+  if (!beta_v1() && (K & 3) == 0 && lds2_bwd(N, 1, Kc, al) <= 160 * 1024) {
+    const int Tc2 = bwd2_chunk(N, T, Kc, al);
+    if (al) {
+      RD_LDS_ATTR(k_graph_beta_bwd2<true>, 160 * 1024);
+      hipLaunchKernelGGL(k_graph_beta_bwd2<true>, dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc, true), (hipStream_t)stream, a, Tc2);
+    } else {
+      RD_LDS_ATTR(k_graph_beta_bwd2<false>, 160 * 1024);
+      hipLaunchKernelGGL(k_graph_beta_bwd2<false>, dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc), (hipStream_t)stream, a, Tc2);
+    }
     return check_launch("k_graph_beta_bwd2");
   }
+  if (al) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_alpha: the rounds 2-5 kernels (RD_BETA_V1=1) take no alpha cotangent");
   const int Tc = bwd_chunk(N, T, Kc);
   const size_t lds = lds_bytes(N, Tc, 0, Kc, true);
   RD_LDS_ATTR(k_graph_beta_bwd, 160 * 1024);
@@ -702,11 +773,50 @@ extern "C" int rd_graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int
   return check_launch("k_graph_beta_bwd");
 }
 
+extern "C" int rd_graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                                 const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
+                                 const float* beta_save, const int32_t* kept, const float* dout, float* dV, float* dH,
+                                 float* dmap_part, float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+  return graph_beta_bwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride,
+                        beta_save, kept, dout, nullptr, dV, dH, dmap_part, dw, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rd_graph_beta_bwd_alpha(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                                       const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                                       const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
+                                       const float* beta_save, const int32_t* kept, const float* dout, const float* dalpha,
+                                       float* dV, float* dH, float* dmap_part, float* dw, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  return graph_beta_bwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride,
+                        beta_save, kept, dout, dalpha, dV, dH, dmap_part, dw, workspace, workspace_bytes, stream);
+}
+
 extern "C" int rd_structure_distance(int32_t E, int32_t B, const float* alpha_all, float* workspace, float* distance,
                                      void* stream) {
   RD_REQUIRE(E >= 0 && B > 0, "bad dims E=%d B=%d", E, B);
-  RD_REQUIRE(alpha_all && workspace && distance, "NULL tensor");
+  RD_REQUIRE((alpha_all || E == 0) && workspace && distance, "NULL tensor");        // E == 0: no rows to read
   hipLaunchKernelGGL(k_distance_rows, dim3(B), dim3(256), 0, (hipStream_t)stream, alpha_all, E, B, workspace);
   hipLaunchKernelGGL(k_distance_reduce, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, B, distance);
   return check_launch("rd_structure_distance");
+}
+
+extern "C" size_t rd_structure_distance_bwd_workspace_bytes(int32_t E, int32_t B) {
+  (void)E;
+  return B > 0 ? (size_t)B * (size_t)B * sizeof(float) : 0;
+}
+
+extern "C" int rd_structure_distance_bwd(int32_t E, int32_t B, const float* alpha_all, const float* grad, void* workspace,
+                                         size_t workspace_bytes, float* dalpha_all, void* stream) {
+  RD_REQUIRE(E >= 0 && B > 0, "bad dims E=%d B=%d", E, B);
+  RD_REQUIRE(grad && workspace && (E == 0 || (alpha_all && dalpha_all)), "NULL tensor");
+  const size_t need = rd_structure_distance_bwd_workspace_bytes(E, B);
+  RD_REQUIRE(workspace_bytes >= need, "rd_structure_distance_bwd: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  if (E == 0) return RD_OK;                                          // no scores: nothing to write
+  const long EB = (long)E * B;
+  const long blocks = (EB + 255) / 256 < (1L << 20) ? (EB + 255) / 256 : (1L << 20);     // grid-stride beyond
+  hipLaunchKernelGGL(k_distance_coef, dim3(B), dim3(256), 0, (hipStream_t)stream, alpha_all, E, B, grad, (float*)workspace);
+  hipLaunchKernelGGL(k_distance_bwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, alpha_all, EB, B,
+                     (const float*)workspace, dalpha_all);
+  return check_launch("rd_structure_distance_bwd");
 }

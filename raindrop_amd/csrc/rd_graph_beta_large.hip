@@ -8,7 +8,7 @@
 //   scores beta [N,T] -> sort keys [P2] -> bitonic sort (4096-key chunks in LDS, strides >= 4096 in global memory) -> kept edges
 //   in pruning order -> per-source lists (stable: pruning order) -> softmax statistics per (source, step) -> aggregation;
 //   backward: lists by source AND by target, statistics, S = sum_e weight dweight per (source, step), dV, dbeta -> dH, d map_weights,
-//   d edge weight.
+//   d edge weight; with an alpha cotangent (rd_graph_beta_bwd_alpha) its terms join dbeta and d edge weight.
 // The pruning sort's keys are unique (score bits | edge id), so any correct sort yields the same order as the small kernel's:
 // descending score, ties by edge id.
 #include "rd_graph_beta.h"
@@ -274,6 +274,8 @@ __global__ __launch_bounds__(BL_THR) void k_bl_S(LArgs g) {
 }
 // dV[i][4t + c] = sum over kept edges INTO i of weight[e][t] * dout[src(e)][4t + c];
 // dbeta[i][t] = sum over kept edges into i of w[e] * weight * (dweight - S[src]);  dH[i][t][c] = dbeta / 32 * cat(map_w[i], p_t[t])[c]
+// With an alpha cotangent (alpha[e] = sum_t beta[tgt][t] w[e] / T): dbeta[i][t] += (sum over kept edges into i of dalpha[e] w[e]) / T,
+// the same for every step (each thread forms it over the list it walks anyway: the LDS form's order)
 __global__ __launch_bounds__(BL_THR) void k_bl_dv_dbeta(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K;
@@ -294,6 +296,12 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dv_dbeta(LArgs g) {
     s += v.kw[e] * (wg * (dwgt_of(dout, V, K, sr, n, t) - S[(size_t)sr * T + t]));
   }
   *reinterpret_cast<float4*>(a.dV + (size_t)b * N * K + (size_t)n * K + 4 * t) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  if (a.dalpha) {
+    const float* da = a.dalpha + (size_t)b * a.Kk;
+    float c = 0.f;
+    for (int q = toff[n]; q < toff[n + 1]; ++q) { const int e = tlist[q]; c += da[e] * v.kw[e]; }
+    s += c / (float)T;
+  }
   const float db = s * (1.0f / 32.0f);
   float* ph = a.dH + ((size_t)b * N * T + i) * 32;
   const float* pt = a.p_t + (size_t)b * a.pt_bstride;
@@ -320,7 +328,8 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dw_zero(LArgs g) {
   const int e = blockIdx.x * BL_THR + threadIdx.x;
   if (e < g.a.E) g.a.dw[(size_t)blockIdx.y * g.a.E + e] = 0.f;
 }
-// d loss / d w[e] = sum_t weight (dweight - S[src]) beta[tgt][t] for kept edges (0 for pruned ones: k_bl_dw_zero)
+// d loss / d w[e] = sum_t weight (dweight - S[src]) beta[tgt][t] for kept edges (0 for pruned ones: k_bl_dw_zero),
+// + dalpha[e] * (sum_t beta[tgt][t]) / T with an alpha cotangent
 __global__ __launch_bounds__(BL_THR) void k_bl_dw(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K, Kk = a.Kk;
@@ -332,6 +341,11 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dw(LArgs g) {
   const int sr = v.ksrc[q], tg = v.ktgt[q];
   float s = 0.f;
   for (int t = 0; t < T; ++t) s += v.weight(q, t) * (dwgt_of(dout, V, K, sr, tg, t) - S[(size_t)sr * T + t]) * v.beta[(size_t)tg * T + t];
+  if (a.dalpha) {
+    float bs = 0.f;
+    for (int t = 0; t < T; ++t) bs += v.beta[(size_t)tg * T + t];
+    s = s + a.dalpha[(size_t)b * Kk + q] * (bs / (float)T);
+  }
   a.dw[(size_t)b * a.E + a.kept[(size_t)b * Kk + q]] = s;
 }
 

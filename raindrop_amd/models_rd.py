@@ -13,7 +13,8 @@ Differences from the reference, all deliberate and documented in DESIGN.md:
   * no host round trips in forward (PE, padding mask and the edge list are built on device);
   * the caller's `global_structure` is not mutated (the reference writes its diagonal in place
     on CPU, code/models_rd.py:307-308);
-  * `distance` is the exact constant 0 the reference computes on this path.
+  * `distance` is the exact constant 0 the reference computes on this path; on the paper's branch
+    (`use_beta=True, compute_distance=True`) it is the reference's differentiable regulariser.
 """
 import ctypes
 
@@ -190,7 +191,9 @@ class Raindrop_v2(nn.Module):
         that path.  `use_beta=True` runs the paper's branch -- layer 1 through
         `Observation_progation.message`'s use_beta arm (time-dependent edge scores from the positional encoding, half of
         the edges pruned PER SAMPLE), layer 2 on each sample's surviving edges -- and `compute_distance=True` evaluates
-        code/models_rd.py:345-346 on the returned edge scores instead of returning the constant."""
+        code/models_rd.py:345-346 on the returned edge scores instead of returning the constant.  That `distance` is
+        differentiable, as the reference's is: `(ce + lam * distance).backward()` trains the paper's objective (the gradient
+        reaches R_u, increase_dim and map_weights of layer 1 through the edge scores); a loss without it is unchanged."""
         super().__init__()
         from torch.nn import TransformerEncoder, TransformerEncoderLayer
         self.model_type = 'Transformer'
@@ -285,7 +288,9 @@ class Raindrop_v2(nn.Module):
         encoding (:324,:329) -> per-sample pruned edge lists and scores; layer 2 = the default branch on THOSE lists
         (:331-336): relu(lin_value(y1_i)) * sum of the per-target softmax over the surviving edges into i (1 where a
         target keeps an edge, 0 where pruning removed them all); then the [F,T*d] -> [T,F*d] layout and the PE columns.
-        `distance` = mean pairwise distance of the samples' returned scores (:345-346) when `compute_distance`."""
+        `distance` = mean pairwise distance of the samples' returned scores (:345-346) when `compute_distance`, differentiable
+        through those scores (ops.graph_beta(alpha_grad=True) -> ops.structure_distance).  Layer 2's edge weights stay constants:
+        the per-target softmax over them sums to 1 (or is absent), so their true gradient is 0."""
         dev = src.device
         B, T, F_, d = shp.B, shp.T, shp.F, shp.d_ob
         K, D = T * d, F_ * d + self.d_pe
@@ -300,7 +305,8 @@ class Raindrop_v2(nn.Module):
         V = ops.linear(X, l1.lin_value.weight, l1.lin_value.bias, act=1).view(B, F_, K)
         H = ops.linear(X, l1.increase_dim.weight, l1.increase_dim.bias, exact=True).view(B, F_, T * 32)   # edge scores -> top-K: exact fp32
         p_t = z[:, :, F_ * d:].permute(1, 0, 2).contiguous()                       # [B,T,16]: layout only
-        y1, ei2, alpha1 = ops.graph_beta(V, H, l1.map_weights, p_t, g["edge_index"], g["edge_weights"].view(1, -1), d)
+        y1, ei2, alpha1 = ops.graph_beta(V, H, l1.map_weights, p_t, g["edge_index"], g["edge_weights"].view(1, -1), d,
+                                         alpha_grad=self.compute_distance)
         _, ssum2 = ops.edge_softmax_list_batched(ei2, alpha1, F_, norm_row=1)
         y2 = ops.linear(y1.reshape(B * F_, K), l2.lin_value.weight, l2.lin_value.bias, act=1).view(B, F_, K)
         z = ops.rows_to_tokens(y2, ssum2, z, shp)

@@ -442,10 +442,12 @@ def rows_to_tokens(Y, rowscale, z, shp):
 
 class _GraphBeta(torch.autograd.Function):
     """The use_beta graph operator (rd_graph_beta_fwd / _bwd), batched: V [B,N,K], H [B,N,T*32], map_w [N,16],
-    p_t [B or 1, T, 16], edge_index int64 [2,E], edge_weights [B or 1, E] -> out [B,N,K], edge_index' [B,2,Kk], alpha [B,Kk]."""
+    p_t [B or 1, T, 16], edge_index int64 [2,E], edge_weights [B or 1, E] -> out [B,N,K], edge_index' [B,2,Kk], alpha [B,Kk].
+    alpha_grad: alpha is differentiable (rd_graph_beta_bwd_alpha); gradients are then not materialised, so an unused alpha
+    arrives as None (the kernel gets NULL) and so does an unused out (a loss of the structure distance alone)."""
 
     @staticmethod
-    def forward(ctx, V, H, map_w, p_t, edge_index, edge_weights, d_ob):
+    def forward(ctx, V, H, map_w, p_t, edge_index, edge_weights, d_ob, alpha_grad=False):
         _check(V, H, map_w, p_t, edge_weights)
         _check(edge_index, dtype=torch.int64)
         B, N, K = V.shape
@@ -467,26 +469,38 @@ class _GraphBeta(torch.autograd.Function):
                   _ptr(scratch), scratch.numel(), _stream())
         ctx.save_for_backward(V, H, map_w, p_t, edge_index, edge_weights, beta, kept)
         ctx.dims = (B, N, K, T, d_ob, E, pts, ws)
-        ctx.mark_non_differentiable(ei_out, alpha)
+        ctx.alpha_grad = bool(alpha_grad)
+        if alpha_grad:
+            ctx.mark_non_differentiable(ei_out)
+            ctx.set_materialize_grads(False)
+        else:
+            ctx.mark_non_differentiable(ei_out, alpha)
         return out, ei_out, alpha
 
     @staticmethod
-    def backward(ctx, dout, _dei, _dalpha):
+    def backward(ctx, dout, _dei, dalpha):
         V, H, map_w, p_t, edge_index, edge_weights, beta, kept = ctx.saved_tensors
         B, N, K, T, d_ob, E, pts, ws = ctx.dims
-        dout = dout.contiguous()
+        only_alpha = dout is None                                                # only alpha reaches the loss: V gets no gradient
+        dout = torch.zeros_like(V) if only_alpha else dout.contiguous()
         dV, dH = torch.empty_like(V), torch.empty_like(H)
         dmap_part = torch.empty((B, N, 16), dtype=torch.float32, device=V.device)
         want_dw = ctx.needs_input_grad[5]
         dw = torch.empty((B, E), dtype=torch.float32, device=V.device) if want_dw else None
         scratch = _workspace(_lib.load().rd_graph_beta_workspace_bytes(B, N, K, T, E), V.device)
-        _lib.call("rd_graph_beta_bwd", B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index),
-                  edge_index.stride(0), _ptr(edge_weights), ws, _ptr(beta), _ptr(kept), _ptr(dout), _ptr(dV), _ptr(dH),
-                  _ptr(dmap_part), _ptr(dw), _ptr(scratch), scratch.numel(), _stream())
+        args = (B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index), edge_index.stride(0),
+                _ptr(edge_weights), ws, _ptr(beta), _ptr(kept), _ptr(dout))
+        tail = (_ptr(dV), _ptr(dH), _ptr(dmap_part), _ptr(dw), _ptr(scratch), scratch.numel(), _stream())
+        if dalpha is None or not ctx.alpha_grad:                                 # (a non-differentiable alpha gets zeros here)
+            _lib.call("rd_graph_beta_bwd", *args, *tail)
+        else:
+            dalpha = dalpha.contiguous()
+            _check(dalpha)
+            _lib.call("rd_graph_beta_bwd_alpha", *args, _ptr(dalpha), *tail)
         dmap = dmap_part[0] if B == 1 else _colsum_rows(dmap_part.view(B, N * 16)).view(N, 16)
         if want_dw and edge_weights.shape[0] == 1 and B > 1:
             dw = _colsum_rows(dw).view(1, E)
-        return dV, dH, dmap, None, None, dw, None
+        return None if only_alpha else dV, dH, dmap, None, None, dw, None, None
 
 
 def _colsum_rows(x):
@@ -525,11 +539,13 @@ def _validate_edges(edge_index, N, who):
     _EDGES_CHECKED.add(key)
 
 
-def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4):
+def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4, alpha_grad=False):
     """use_beta branch of Observation_progation.message, batched (include/raindrop_hip.h: rd_graph_beta_fwd).  V [B,N,K],
     H [B,N,T*32], map_w [N,16], p_t [B or 1, T, 16], edge_index int64 [2,E], edge_weights [B or 1, E].  Shapes and edge
     endpoints are validated here (one device read for the endpoint range: the reference's index_select syncs and raises
-    IndexError at the same point)."""
+    IndexError at the same point).  Returns (out [B,N,K], edge_index' [B,2,Kk], alpha [B,Kk]); alpha is a constant unless
+    `alpha_grad`, which makes it differentiable as the reference's is (the structure distance's path to the parameters,
+    rd_graph_beta_bwd_alpha)."""
     if V.dim() != 3 or H.dim() != 3 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError("graph_beta: V [B,N,K], H [B,N,T*32], edge_index [2,E] expected")
     B, N, K = V.shape
@@ -546,19 +562,45 @@ def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4):
         raise ValueError("graph_beta: edge_weights must be [1 or B, E], got %s" % (tuple(edge_weights.shape),))
     _validate_edges(edge_index, N, "graph_beta")
     return _GraphBeta.apply(V.contiguous(), H.contiguous(), map_w.contiguous(), p_t.contiguous(), edge_index.contiguous(),
-                            edge_weights.contiguous(), int(d_ob))
+                            edge_weights.contiguous(), int(d_ob), bool(alpha_grad))
 
 
-def structure_distance(alpha_all):
-    """code/models_rd.py:345-346: mean(cdist(alpha_all.T, alpha_all.T, p=2)) for alpha_all [E,B] (no gradient: the
-    reference's training loss does not use it, code/Raindrop.py:319-322)."""
-    a = alpha_all.detach().contiguous()
+def _structure_distance_fwd(a):
     _check(a)
     E, B = a.shape
     ws = torch.empty((B,), dtype=torch.float32, device=a.device)
     out = torch.empty((), dtype=torch.float32, device=a.device)
     _lib.call("rd_structure_distance", E, B, _ptr(a), _ptr(ws), _ptr(out), _stream())
     return out
+
+
+class _StructureDistance(torch.autograd.Function):
+    """rd_structure_distance / _bwd: alpha_all [E,B] -> distance (0-d); the gradient is read on the device (capturable)."""
+
+    @staticmethod
+    def forward(ctx, a):
+        ctx.save_for_backward(a)
+        return _structure_distance_fwd(a)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, = ctx.saved_tensors
+        E, B = a.shape
+        g = g.contiguous()
+        _check(g)
+        da = torch.empty_like(a)
+        ws = _workspace(_lib.load().rd_structure_distance_bwd_workspace_bytes(E, B), a.device)
+        _lib.call("rd_structure_distance_bwd", E, B, _ptr(a), _ptr(g), _ptr(ws), ws.numel(), _ptr(da), _stream())
+        return da
+
+
+def structure_distance(alpha_all):
+    """code/models_rd.py:345-346: mean(cdist(alpha_all.T, alpha_all.T, p=2)) for alpha_all [E,B].  Differentiable when
+    alpha_all requires grad (rd_structure_distance_bwd; the paper's objective CE + lambda * distance, the reference's
+    `local_structure_regularization`, code/Raindrop.py:319); otherwise a constant, as before."""
+    if alpha_all.requires_grad and torch.is_grad_enabled():
+        return _StructureDistance.apply(alpha_all.contiguous())
+    return _structure_distance_fwd(alpha_all.detach().contiguous())
 
 
 # ------------------------------------------------------------------------------------------------

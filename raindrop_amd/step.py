@@ -19,13 +19,31 @@ all-reduce (N > 1) and the Adam kernel stay outside the graph.  The eager model 
 and this step call the SAME kernels in the same order; `tests/test_gpu_parity.py` checks that the
 gradients agree bit for bit.
 """
+import contextlib
 import ctypes
+import gc
 import os
 import time
 
 import torch
 
 from . import _lib, ops
+
+
+@contextlib.contextmanager
+def _graph_capture(graph, **kw):
+    """torch.cuda.graph with Python's cyclic garbage collector held off for the capture.  A model and its captured steps refer to each
+    other (Raindrop_v2._graph_runners -> TrainStep -> model), so an unreachable one is freed by the collector, at whatever point an
+    allocation triggers it; inside another capture that would destroy its hipGraphs while a capture is in progress, which the
+    runtime refuses (the process aborts).  The garbage is collected after the capture instead."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def _p(t):
@@ -493,13 +511,13 @@ class TrainStep:
             self.graph = torch.cuda.CUDAGraph()
             self.graph_b = None
             if not self.split:
-                with torch.no_grad(), torch.cuda.graph(self.graph):
+                with torch.no_grad(), _graph_capture(self.graph):
                     self._body()
                 return
-            with torch.no_grad(), torch.cuda.graph(self.graph):
+            with torch.no_grad(), _graph_capture(self.graph):
                 self._body("a")
             self.graph_b = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(self.graph_b, pool=self.graph.pool()):
+            with torch.no_grad(), _graph_capture(self.graph_b, pool=self.graph.pool()):
                 self._body("b")
         self._with_cell(cap)
 
@@ -521,7 +539,7 @@ class TrainStep:
             pool = None
             for pt in parts:
                 g = torch.cuda.CUDAGraph()
-                with torch.no_grad(), (torch.cuda.graph(g) if pool is None else torch.cuda.graph(g, pool=pool)):
+                with torch.no_grad(), (_graph_capture(g) if pool is None else _graph_capture(g, pool=pool)):
                     self._body(pt)
                 pool = g.pool()
                 graphs.append(g)
@@ -546,7 +564,7 @@ class TrainStep:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), torch.cuda.graph(g):
+            with torch.no_grad(), _graph_capture(g):
                 for k, pt in enumerate(parts):
                     events[k].record()
                     self._body(pt)
@@ -659,7 +677,7 @@ class TrainStep:
             # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
             begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
             try:
-                with torch.no_grad(), torch.cuda.graph(g):
+                with torch.no_grad(), _graph_capture(g):
                     if begin_adv:
                         opt.register_cell(True)
                     if self.split:
@@ -722,11 +740,21 @@ class AutogradStep:
     softmax -> layer 2 -> tokens: ~7 launches for the sensor stage, DESIGN.md (e')), not a fused kernel; `bench.py --use-beta`
     times it.  The optimizer is torch's own Adam in its capturable fused form over the model's parameters (the reference's
     `torch.optim.Adam(model.parameters(), lr)`, code/Raindrop.py:256), inside the graph; `lr` is a device tensor there, so a
-    scheduler can change it without a new capture."""
+    scheduler can change it without a new capture.
 
-    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234):
+    `distance_weight` (lambda): the captured step minimises the paper's objective `CE + lambda * distance` instead, the
+    structure-distance regulariser code/models_rd.py:345-346 returns (differentiable on `use_beta=True, compute_distance=True`:
+    rd_structure_distance_bwd -> rd_graph_beta_bwd_alpha).  Any other model would add lambda * 0 and is refused.  0: CE alone,
+    the same capture as without the argument."""
+
+    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234, distance_weight=0.0):
         self.model, self.batch = model, batch
         self.dev = batch["src"].device
+        self.distance_weight = float(distance_weight)
+        if self.distance_weight != 0.0 and not (getattr(model, "use_beta", False) and getattr(model, "compute_distance", False)):
+            raise _lib.RaindropHipError("AutogradStep(distance_weight=%g): the structure distance is the constant 0 unless the model "
+                                        "has use_beta=True and compute_distance=True (code/models_rd.py:317,345-346)"
+                                        % self.distance_weight)
         TrainStep._validate_shapes_only(model, batch)
         self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -743,6 +771,8 @@ class AutogradStep:
         b = self.batch
         logits, distance, _ = self.model(b["src"], b["static"], b["times"], b["lengths"])
         loss = torch.nn.functional.cross_entropy(logits, b["y"])
+        if self.distance_weight != 0.0:
+            loss = loss + self.distance_weight * distance
         loss.backward()
         if self.opt is not None:
             self.opt.step()
@@ -763,7 +793,7 @@ class AutogradStep:
             for p in self.params:
                 p.grad = None                                      # the captured backward ALLOCATES the gradients (static addresses)
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
+            with _graph_capture(self.graph):
                 _lib.call("rd_seed_cell_advance", _p(self.seed_cell), 1, ops._stream())
                 logits, distance, loss = self._one()
                 self.loss_static, self.logits, self.distance = loss.detach(), logits.detach(), distance.detach()
