@@ -507,6 +507,47 @@ int rd_obs_embed_bwd(const rd_shape* s, const float* src, const float* X, const 
 int rd_rows_to_tokens_fwd(const rd_shape* s, const float* Y, const float* rowscale, float* z, int32_t ldz, void* stream);
 int rd_rows_to_tokens_bwd(const rd_shape* s, const float* dz, int32_t ldz, const float* rowscale, float* dY, void* stream);
 
+/* ---- the use_beta sensor stage as ONE pair in the training step's layout (raindrop_amd/step_beta.py BetaTrainStep) ----------
+ * What Raindrop_v2._sensor_stage_beta composes under autograd (code/models_rd.py:313-346 with `use_beta` on), enqueued by the library:
+ * PE + mask, observation embedding (its dropout site), V = relu(lin_value(X)), H = increase_dim(X) in exact fp32 in every arithmetic
+ * mode (it feeds the top-K), rd_graph_beta_fwd, layer 2's relu(lin_value(y1)), the per-sample aggregate coefficient and the
+ * [B,F,T*d] -> [T,B,F*d | PE] layout.  z follows the token plan registered by rd_set_token_plan (live rows only) or is the padded
+ * [T,B,D]; the seed cell is read at enqueue like rd_sensor_stage_fwd does.  Asynchronous, capturable, caller-owned memory only.
+ * Needs d_ob = 4, d_pe = 16, F <= 1024.  edge_index int64 rows [source; target] `row_stride` apart, edge_weights [E] (shared).
+ * Outputs: z, mask [B,T], edge_index_out [B][2,Kk] int64, alpha_out [B,Kk] (Kk = rd_graph_beta_kept(E)), and, when `distance` is
+ * not NULL, the structure distance (rd_structure_distance of alpha_out^T).  `saved` (rd_beta_stage_saved_bytes) goes to the
+ * backward; `workspace` (rd_beta_stage_workspace_bytes, one size for both directions) is scratch.  256-byte aligned both.
+ * Backward: dz (row stride lddz, the forward's layout) -> the gradients of R_u, both lin_value pairs, increase_dim.weight / .bias
+ * and map_weights, WRITTEN (not accumulated) into the given destinations.  dist_grad: device scalar lambda of CE + lambda * distance
+ * (rd_structure_distance_bwd -> rd_graph_beta_bwd_alpha); NULL: rd_graph_beta_bwd exactly as the autograd surface runs it.  The
+ * backward forms what the distance's gradient needs from `alpha` itself: it does not matter whether the forward was given a
+ * `distance` destination. */
+size_t rd_beta_stage_workspace_bytes(const rd_shape* s, int32_t E);
+size_t rd_beta_stage_saved_bytes(const rd_shape* s, int32_t E);
+int rd_beta_stage_fwd(const rd_shape* s, const float* src, const float* times, const int64_t* lengths, const float* timescales,
+                      const float* R_u, const float* W1, const float* b1, const float* Winc, const float* binc,
+                      const float* map_weights, const float* W2, const float* b2, const int64_t* edge_index, int64_t row_stride,
+                      const float* edge_weights, int32_t E, float p_drop, uint64_t seed, float* z, uint8_t* mask,
+                      int64_t* edge_index_out, float* alpha_out, float* distance, void* saved, size_t saved_bytes, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int rd_beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
+                      const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
+                      const float* edge_weights, int32_t E, float p_drop, const int64_t* edge_index_kept, const float* alpha,
+                      const void* saved, size_t saved_bytes, const float* dz, int32_t lddz, const float* dist_grad, float* dR_u,
+                      float* dW1, float* db1, float* dWinc, float* dbinc, float* dmap_weights, float* dW2, float* db2,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* The stage's two layout kernels on their own.  _fwd: z[row(t,b), f*4+c] = y2[b,f,t*4+c] * coef[b,f], coef = the per-target softmax
+ * sum over sample b's kept edges (edge_index_kept [B][2,Kk], alpha [B,Kk]): bit-identical to rd_edge_softmax_list_batched(norm_row
+ * = 1)'s ssum followed by rd_rows_to_tokens_fwd on the padded layout; with a token plan registered only the live rows are written,
+ * at the plan's rows.  _bwd: dY[b,f,t*4+c] = dz[row(t,b), f*4+c] * coef[b,f] * (y2[b,f,t*4+c] > 0); steps without a row in the plan
+ * layout get exact zeros.  16-byte aligned tensors, row strides multiples of 4.  coef_out (optional): the forward also stores coef
+ * [B,F]; coef (optional): the backward reads that table instead of forming the softmax sums again (same bits; the stage does
+ * this through `saved`).  The lists may be NULL when Kk = 0 (a graph of fewer than two edges keeps none: coef = 0). */
+int rd_beta_l2_tokens_fwd(const rd_shape* s, int32_t Kk, const int64_t* edge_index_kept, const float* alpha, const float* y2, float* z,
+                          int32_t ldz, float* coef_out, void* stream);
+int rd_beta_l2_tokens_bwd(const rd_shape* s, int32_t Kk, const int64_t* edge_index_kept, const float* alpha, const float* y2,
+                          const float* dz, int32_t lddz, const float* coef, float* dY, void* stream);
+
 /* ---- host preprocessing on the device: code/utils_rd.py:149-257, code/Raindrop.py:215-231 ------------
  * Inputs are float64 (the reference's numpy arrays), outputs float32 (its torch.Tensor casts).  Every result is
  * bit-identical to the reference: elementwise steps use the same IEEE float64 operations in the same order, and the

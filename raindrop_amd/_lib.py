@@ -123,6 +123,14 @@ SIGNATURES = {
     "rd_structure_distance": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
     "rd_structure_distance_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "rd_structure_distance_bwd": (c_int32, [c_int32, c_int32, _P, _P, _P, c_size_t, _P, _P]),
+    "rd_beta_stage_workspace_bytes": (c_size_t, [_SHP, c_int32]),
+    "rd_beta_stage_saved_bytes": (c_size_t, [_SHP, c_int32]),
+    "rd_beta_stage_fwd": (c_int32, [_SHP] + [_P] * 12 + [_P, ctypes.c_int64, _P, c_int32, c_float, ctypes.c_uint64] + [_P] * 5
+                          + [_P, c_size_t, _P, c_size_t, _P]),
+    "rd_beta_stage_bwd": (c_int32, [_SHP] + [_P] * 6 + [_P, ctypes.c_int64, _P, c_int32, c_float, _P, _P, _P, c_size_t, _P, c_int32, _P]
+                          + [_P] * 8 + [_P, c_size_t, _P]),
+    "rd_beta_l2_tokens_fwd": (c_int32, [_SHP, c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
+    "rd_beta_l2_tokens_bwd": (c_int32, [_SHP, c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "rd_prep_stats_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
     "rd_prep_stats": (c_int32, [ctypes.c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "rd_prep_mask_normalize": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P]),

@@ -189,6 +189,10 @@ class TrainStep:
         m = self.model
         return plan_supported(m.d_inp, m.d_ob, self.T, self.D, m.nhead, m.nhid, self.lib.rd_get_precision())
 
+    def _k1_buffer_bytes(self):
+        """(saved, workspace) bytes of the sensor stage this step enqueues: the sizes of self.k1_saved / self.k1_ws"""
+        return int(self.lib.rd_msgpass_saved_bytes(self.sp)), int(self.lib.rd_msgpass_workspace_bytes(self.sp))
+
     # ------------------------------------------------------------------------------------------
     def _alloc(self):
         lib, sp, dev, B, T, D = self.lib, self.sp, self.dev, self.B, self.T, self.D
@@ -206,7 +210,7 @@ class TrainStep:
         if arena:
             nl_ = len(m.transformer_encoder.layers)
             al = lambda n: (max(int(n), 256) + (1 << 21) - 1) >> 21 << 21
-            sizes = [al(T * B * D * 4)] * (1 + nl_ + 2) + [al(lib.rd_msgpass_saved_bytes(sp)), al(lib.rd_msgpass_workspace_bytes(sp))] + \
+            sizes = [al(T * B * D * 4)] * (1 + nl_ + 2) + [al(n) for n in self._k1_buffer_bytes()] + \
                     [al(lib.rd_encoder_layer_saved_bytes(sp))] * nl_ + [al(lib.rd_encoder_layer_workspace_bytes(sp))] * nl_
             small_cap = 16 << 20                                  # the small buffers' common region (head workspace, features, plan, ...)
             self._arena = torch.zeros(sum(sizes) + small_cap + (1 << 21), dtype=torch.uint8, device=dev)
@@ -233,8 +237,9 @@ class TrainStep:
         self._u8, self._zeros_f = u8, zeros_f
         self.z = zeros_f((T, B, D))
         self.mask = torch.empty((B, T), dtype=torch.bool, device=dev)
-        self.k1_saved = u8(lib.rd_msgpass_saved_bytes(sp))
-        self.k1_ws = u8(lib.rd_msgpass_workspace_bytes(sp))
+        k1_saved_bytes, k1_ws_bytes = self._k1_buffer_bytes()
+        self.k1_saved = u8(k1_saved_bytes)
+        self.k1_ws = u8(k1_ws_bytes)
         self.nl = len(m.transformer_encoder.layers)
         self.x = [self.z] + [zeros_f((T, B, D)) for _ in range(self.nl)]
         self.enc_saved = [u8(lib.rd_encoder_layer_saved_bytes(sp)) for _ in range(self.nl)]
@@ -288,9 +293,7 @@ class TrainStep:
         B, T, D, Fe = self.B, self.T, self.D, self.Fe
         dh = D + Fe
         c = self._call
-        W1, b1 = P["ob_propagation.lin_value.weight"], P["ob_propagation.lin_value.bias"]
-        W2, b2 = P["ob_propagation_layer2.lin_value.weight"], P["ob_propagation_layer2.lin_value.bias"]
-        ssum = self.graph_info["ssum"]
+        W1, W2 = P["ob_propagation.lin_value.weight"], P["ob_propagation_layer2.lin_value.weight"]
         if part == "k1b":
             return self._k1_bwd(self.dx[self.nl % 2], st)
         if part == "mb":                                  # module mode: backward from the caller's d loss / d logits
@@ -314,9 +317,7 @@ class TrainStep:
                 return
         # ---------------- forward ----------------
         if part in (None, "a", "k1f", "mf"):
-            c("rd_sensor_stage_fwd_prepared" if self.prep_k1 else "rd_sensor_stage_fwd", sp, _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(self.ts), _p(P["R_u"]), _p(W1),
-              _p(b1), _p(W2), _p(b2), _p(ssum), self.p_drop, self.seed, _p(self.z), _p(self.mask), _p(self.k1_saved),
-              self.k1_saved.numel(), st)
+            self._k1_fwd(st)
             if part == "k1f":
                 return
         if part == "encb":
@@ -347,6 +348,15 @@ class TrainStep:
             self._enc_bwd(self.nl - 1, cur, self.dx[1], st)
             return
         self._body_tail(self.nl - 1, cur, k1=(part != "mid"))
+
+    def _k1_fwd(self, st):
+        """The sensor stage's forward into self.z / self.mask (BetaTrainStep, raindrop_amd/step_beta.py, enqueues the use_beta one)."""
+        b, P = self.batch, self.P
+        W1, b1 = P["ob_propagation.lin_value.weight"], P["ob_propagation.lin_value.bias"]
+        W2, b2 = P["ob_propagation_layer2.lin_value.weight"], P["ob_propagation_layer2.lin_value.bias"]
+        self._call("rd_sensor_stage_fwd_prepared" if self.prep_k1 else "rd_sensor_stage_fwd", self.sp, _p(b["src"]), _p(b["times"]),
+                   _p(b["lengths"]), _p(self.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2), _p(self.graph_info["ssum"]), self.p_drop,
+                   self.seed, _p(self.z), _p(self.mask), _p(self.k1_saved), self.k1_saved.numel(), st)
 
     def _enc_bwd(self, i, cur, nxt, st):
         self._call("rd_encoder_layer_bwd", self.sp, i, _p(self.x[i]), _p(self.mask), ctypes.byref(self.enc_w[i]), self.p_drop,

@@ -126,3 +126,12 @@ def live_parameter_names(cfg):
             "linear2.bias", "norm1.weight", "norm1.bias", "norm2.weight", "norm2.bias")]
     names += ["mlp_static.0.weight", "mlp_static.0.bias", "mlp_static.2.weight", "mlp_static.2.bias"]
     return names
+
+
+def live_parameter_names_beta(cfg):
+    """Parameters that receive a gradient on the paper's branch (Raindrop_v2(use_beta=True)), in forward order: the default list
+    plus layer 1's increase_dim and map_weights (only this branch trains them), placed next to ob_propagation.lin_value.* so that
+    the flat gradient buffer keeps the order the two-graph data-parallel step relies on (TrainStep._check_split_order)."""
+    names = live_parameter_names(cfg)
+    i = names.index("ob_propagation.lin_value.bias") + 1
+    return names[:i] + ["ob_propagation.increase_dim.weight", "ob_propagation.increase_dim.bias", "ob_propagation.map_weights"] + names[i:]
