@@ -118,7 +118,7 @@ int rd_drop_trailing(void);
  * every gradient (its rows of the encoder's activation gradients are exactly zero).  rd_token_plan turns `lengths` into a
  * layout: samples ordered by descending length (ties by index), sample b's live steps t < min(lengths[b], T) at rows
  * off[rank[b]] + t of every [tokens, *] tensor.  While a plan is registered (rd_set_token_plan: per host thread, consumed when a
- * call is ENQUEUED, like the seed cell), rd_sensor_stage_fwd, rd_encoder_layer_fwd/bwd, rd_head_train and rd_msgpass_bwd read and
+ * call is ENQUEUED, like the seed cell), rd_sensor_stage_fwd, rd_encoder_layer_fwd/bwd, rd_head_train, rd_masked_mean_fwd and rd_msgpass_bwd read and
  * write ONLY those rows -- buffers keep their padded sizes, the first plan[0] rows are used -- and skip the arithmetic whose
  * operand is an exactly-zero padded step.  Logits, loss and all parameter gradients are the same function of the inputs as
  * without a plan (up to the order of the fp32 sums over tokens); z / x / dx at padded steps, which nothing reads, are not
@@ -326,7 +326,9 @@ int rd_attention_bwd(const rd_shape* s, int32_t layer, const float* qkv, const u
                      const float* out, const float* lse, const float* dout, float* dqkv, float* delta_ws, void* stream);
 
 /* code/models_rd.py:366-367,379: out[b, :D] = sum_t r[t,b,:] * (1 - mask[b,t]) / (lengths[b] + 1);
- * out has row stride ldo (so it can be the left block of the [agg | emb] head input). */
+ * out has row stride ldo (so it can be the left block of the [agg | emb] head input).  The forward follows a registered token
+ * plan (r then holds the live rows only; same sums in the same order, so the same bits as on the padded layout); the backward
+ * does not (the training step's plan runs the fused head). */
 int rd_masked_mean_fwd(const rd_shape* s, int32_t D, const float* r, const uint8_t* mask,
                        const int64_t* lengths, float* out, int32_t ldo, void* stream);
 int rd_masked_mean_bwd(const rd_shape* s, int32_t D, const float* dout, int32_t ldo,
@@ -572,6 +574,32 @@ int rd_prep_time(int64_t N, int32_t T, const double* minutes, float* hours, int3
  * host in the reference's order) or [k] (per_sample = 0: the same top-ranked set for every sample). */
 int rd_prep_remove_features(int64_t N, int32_t T, int32_t F, float* P, const int32_t* idx, int32_t k, int32_t per_sample,
                             int32_t layout, void* stream);
+
+/* ---- validation metrics on the device (code/Raindrop.py:348-370,385-401; raindrop_amd/csrc/rd_metrics.hip) -----------------
+ * What the reference computes on the host every epoch with sklearn, where the logits are.  Asynchronous, capturable, caller-owned
+ * memory only.
+ *
+ * rd_rank_metrics: scores f32 [N, C] with row stride ld (floats), y int64 [N].  For every column c the one-vs-rest ranking
+ * statistics of scores[:, c] against (y == c) with sklearn's semantics -- thresholds are the DISTINCT score values, tied scores
+ * (float32 equality; -0 == +0) form one group; tp / fp = cumulative counts at the end of a tie group in descending score order,
+ * P positives, Q = N - P:
+ *   auroc_num[c] = sum (fp - fp_prev)(tp + tp_prev)                 exact int64
+ *   auroc[c]     = auroc_num[c] / (2 P Q)                           float64; NaN when P = 0 or Q = 0
+ *   auprc[c]     = sum (tp - tp_prev) / P * tp / (tp + fp)          float64, summed in an order that is a function of N alone;
+ *                                                                   0 when P = 0 (sklearn's value: recall := 1, precision 0)
+ *   mean[0], mean[1] = plain means of auroc / auprc over the columns (NaN when a column is NaN)
+ * = roc_auc_score(one_hot(y), scores, average=None / "macro") and average_precision_score of the same; binary tasks read column 1.
+ * Labels outside [0, C) are negatives of every column.  NaN scores are not refused (no host sync): a NaN with the sign bit clear
+ * ranks above +inf, one with it set below -inf, equal payloads tie.  1 <= N <= 2^22, 1 <= C <= 65535.
+ * N <= 16384: one launch, one workgroup per column, keys sorted in LDS, no workspace.  Larger N: 16384-key chunks sorted in LDS
+ * with global compare-exchange launches between them, through `workspace` (rd_rank_metrics_workspace_bytes, 8-byte aligned). */
+size_t rd_rank_metrics_workspace_bytes(int64_t N, int32_t C);
+int rd_rank_metrics(int64_t N, int32_t C, const float* scores, int64_t ld, const int64_t* y, double* auroc, double* auprc,
+                    double* mean, int64_t* auroc_num, void* workspace, size_t workspace_bytes, void* stream);
+/* counts int64 [C, C] (overwritten): counts[t][p] = rows with label t whose first maximum (np.argmax; a NaN is a maximum) is
+ * column p.  Rows with a label outside [0, C) are not counted.  Accuracy and macro precision / recall / F1 follow from the C^2
+ * integers on the host.  C <= 4096. */
+int rd_confusion(int64_t N, int32_t C, const float* logits, int64_t ld, const int64_t* y, int64_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

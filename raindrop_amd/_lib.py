@@ -140,6 +140,9 @@ SIGNATURES = {
     "rd_linear_bwd_weight_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "rd_linear_bwd_weight": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P,
                                         _P, c_size_t, _P]),
+    "rd_rank_metrics_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
+    "rd_rank_metrics": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "rd_confusion": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P]),
 }
 
 _lib = None

@@ -2348,15 +2348,19 @@ int launch_ln_bwd(const float* dy, const float* s, const float* stats, const flo
 // code/models_rd.py:366-367,379: agg[b,c] = sum_t r[t,b,c] * (1 - mask[b,t]) / (lengths[b] + 1)
 __global__ __launch_bounds__(1024) void k_masked_mean_fwd(const float* __restrict__ r, const uint8_t* __restrict__ mask,
                                                           const int64_t* __restrict__ lengths, float* __restrict__ out,
-                                                          int T, int B, int D, int ldo) {
+                                                          int T, int B, int D, int ldo, const int32_t* __restrict__ tp) {
   // block = (sample, 64-column chunk); 16 time groups x 64 columns, fixed-order LDS combine
+  // tp (token plan, rd_plan.h) or null: r holds the live rows only, sample b's step t at row brow[b] + t -- the same steps enter the
+  // same partial sums in the same order as on the padded layout (mask[b,t] is set exactly for the steps that have no row)
   __shared__ float red[16][64];
   const int b = blockIdx.x, cl = threadIdx.x & 63, tg = threadIdx.x >> 6;
   const int c = blockIdx.y * 64 + cl;
+  const long row0 = tp ? (long)tp[plan::brow_base(B, T) + b] : (long)b, rstep = tp ? 1 : (long)B;
+  const int Tv = tp ? tp[plan::blen_base(B, T) + b] : T;
   float s = 0.f;
   if (c < D)
-    for (int t = tg; t < T; t += 16)
-      if (!mask[(long)b * T + t]) s += r[((long)t * B + b) * D + c];
+    for (int t = tg; t < Tv; t += 16)
+      if (!mask[(long)b * T + t]) s += r[(row0 + (long)t * rstep) * D + c];
   red[tg][cl] = s;
   __syncthreads();
   if (tg == 0 && c < D) {
@@ -2941,7 +2945,7 @@ extern "C" int rd_masked_mean_fwd(const rd_shape* s, int32_t D, const float* r, 
   if (s->B == 0) return RD_OK;
   RD_REQUIRE(r && mask && lengths && out, "NULL tensor");
   hipLaunchKernelGGL(k_masked_mean_fwd, dim3(s->B, cdiv(D, 64)), dim3(1024), 0, (hipStream_t)stream, r, mask, lengths,
-                     out, s->T, s->B, D, ldo);
+                     out, s->T, s->B, D, ldo, token_plan());
   return check_launch("k_masked_mean_fwd");
 }
 

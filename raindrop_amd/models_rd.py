@@ -262,6 +262,7 @@ class Raindrop_v2(nn.Module):
         captures its own on its first training call"""
         d = dict(self.__dict__)
         d.pop("_graph_runners", None)
+        d.pop("_eval_steps", None)                                 # raindrop_amd.feed.evaluate_captured's cached forwards
         return d
 
     def init_weights(self):

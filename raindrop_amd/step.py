@@ -65,6 +65,8 @@ def plan_supported(d_inp, d_ob, T, D, nhead, nhid, precision):
 
 
 class TrainStep:
+    plan_needs_fused_head = True      # the training head's backward (rd_masked_mean_bwd) does not follow a plan; a forward-only step's head does
+
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
                  module_mode=False):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
@@ -93,20 +95,7 @@ class TrainStep:
         self.p_drop = cfgp if model.training else 0.0
         self.seed = (int(seed) + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF     # ranks draw different dropout masks
         self._validate(model, batch, labels=not self.module_mode)
-        T, B = batch["src"].shape[0], batch["src"].shape[1]
-        self.T, self.B = T, B
-        self.shp = _lib.shape(B, T, model.d_inp, model.d_ob, d_pe=model.d_pe, nhead=model.nhead, nhid=model.nhid,
-                              d_static=model.d_static if model.static else 0, n_classes=model.n_classes,
-                              max_len=model.max_len)
-        self.sp = ctypes.byref(self.shp)
-        self.D = model.d_inp * model.d_ob + model.d_pe
-        self.graph_info = model._graph(self.dev)                 # adjacency / ssum (built eagerly, once)
-        self.ts = model.pos_encoder.timescales(self.dev)
-        named = dict(model.named_parameters())
-        gview = dict(zip(flat.names, flat.views))                # gradient slices in the flat buffer
-        self.P = named
-        self.G = gview
-        self._alloc()
+        self._setup_shapes(dict(zip(flat.names, flat.views)))    # gradient slices in the flat buffer
         self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev)
         # side branch for the trailing launches of the step (the weight-gradient reduces, the head's weight gradients: nothing in
         # the backward chain reads them).  MEASURED round 4, same box, 3 x 300 steps each: 0.554 ms/step with the branch against
@@ -119,9 +108,36 @@ class TrainStep:
         # gradient bucket's all-reduce needs between the graphs -- is launched on its own at the end of graph A instead of riding
         # in graph B; the head's tiles ride inside A, layer 0's reduce inside B.  RD_TRAILING_RIDE=0: every launch on its own (A/B).
         self.ride = self.side is None and os.environ.get("RD_TRAILING_RIDE", "1") != "0"
+        self._setup_plan_and_prepare()
+        if self.split:
+            self._check_split_order()
+        self._ptrs = self._param_ptrs()                          # the captured graph / cached structs hold these addresses
+        self.graph = None
+        self.graph_b = None
+        if use_graph:
+            self._capture()
+
+    def _setup_shapes(self, gview):
+        """Shape struct, sensor graph, parameter / gradient tables and every buffer of the step (raindrop_amd/evalstep.py comes
+        here with an empty gradient table and `forward_only` set)."""
+        model, batch = self.model, self.batch
+        T, B = batch["src"].shape[0], batch["src"].shape[1]
+        self.T, self.B = T, B
+        self.shp = _lib.shape(B, T, model.d_inp, model.d_ob, d_pe=model.d_pe, nhead=model.nhead, nhid=model.nhid,
+                              d_static=model.d_static if model.static else 0, n_classes=model.n_classes,
+                              max_len=model.max_len)
+        self.sp = ctypes.byref(self.shp)
+        self.D = model.d_inp * model.d_ob + model.d_pe
+        self.graph_info = model._graph(self.dev)                 # adjacency / ssum (built eagerly, once)
+        self.ts = model.pos_encoder.timescales(self.dev)
+        self.P = dict(model.named_parameters())
+        self.G = gview
+        self._alloc()
+
+    def _setup_plan_and_prepare(self):
         # token plan: the step's fast paths only (fused message passing, row-block encoder, fused head)
         self.plan = None
-        if self._want_plan and self.head_fused and self._plan_supported():
+        if self._want_plan and (self.head_fused or not self.plan_needs_fused_head) and self._plan_supported():
             self.plan = torch.zeros(max(int(self.lib.rd_token_plan_bytes(self.sp)) // 4, 64), dtype=torch.int32, device=self.dev)
         # all weight splits of the step in one launch (rd_step_prepare) where the shape takes prepared tiles
         enc_ok, k1_ok = ctypes.c_int32(0), ctypes.c_int32(0)
@@ -132,13 +148,6 @@ class TrainStep:
         self._prep_w = (ctypes.POINTER(_lib.RdEncoderPtrs) * self.nl)(*[ctypes.pointer(w) for w in self.enc_w])
         self._prep_saved = (ctypes.c_void_p * self.nl)(*[t.data_ptr() for t in self.enc_saved])
         self._prep_bytes = (ctypes.c_size_t * self.nl)(*[t.numel() for t in self.enc_saved])
-        if self.split:
-            self._check_split_order()
-        self._ptrs = self._param_ptrs()                          # the captured graph / cached structs hold these addresses
-        self.graph = None
-        self.graph_b = None
-        if use_graph:
-            self._capture()
 
     @staticmethod
     def _validate(model, batch, labels=True):
@@ -173,12 +182,12 @@ class TrainStep:
                 raise _lib.RaindropHipError("TrainStep: labels must lie in [0, %d), got [%d, %d]" % (model.n_classes, lo, hi))
 
     @staticmethod
-    def _validate_shapes_only(model, batch):
+    def _validate_shapes_only(model, batch, labels=True):
         """dtype / contiguity / device / shape / label checks of `_validate` without its refusal of the paper's branch (AutogradStep)"""
         ub, cd = getattr(model, "use_beta", False), getattr(model, "compute_distance", False)
         try:
             model.use_beta, model.compute_distance = False, False
-            TrainStep._validate(model, batch)
+            TrainStep._validate(model, batch, labels=labels)
         finally:
             model.use_beta, model.compute_distance = ub, cd
 
@@ -207,10 +216,11 @@ class TrainStep:
         # alternating, one call: profiles/r06_step_arena_ab.txt).  Every kernel of a step starts on cold translations (~1 GB of
         # traffic since its last run); fewer, larger mappings are fewer walks.
         arena = os.environ.get("RD_STEP_ARENA", "1") == "1"
+        fwd_only = getattr(self, "forward_only", False)          # raindrop_amd/evalstep.py: no gradient buffers, no backward workspaces
         if arena:
             nl_ = len(m.transformer_encoder.layers)
             al = lambda n: (max(int(n), 256) + (1 << 21) - 1) >> 21 << 21
-            sizes = [al(T * B * D * 4)] * (1 + nl_ + 2) + [al(n) for n in self._k1_buffer_bytes()] + \
+            sizes = [al(T * B * D * 4)] * (1 + nl_ + (0 if fwd_only else 2)) + [al(n) for n in self._k1_buffer_bytes()] + \
                     [al(lib.rd_encoder_layer_saved_bytes(sp))] * nl_ + [al(lib.rd_encoder_layer_workspace_bytes(sp))] * nl_
             small_cap = 16 << 20                                  # the small buffers' common region (head workspace, features, plan, ...)
             self._arena = torch.zeros(sum(sizes) + small_cap + (1 << 21), dtype=torch.uint8, device=dev)
@@ -247,19 +257,19 @@ class TrainStep:
         # next layer's backward already writes its own
         self.enc_wss = [u8(lib.rd_encoder_layer_workspace_bytes(sp)) for _ in range(self.nl)]
         self.enc_ws = self.enc_wss[0]
-        self.dx = [zeros_f((T, B, D)) for _ in range(2)]                   # ping-pong gradient buffers
+        self.dx = [None, None] if fwd_only else [zeros_f((T, B, D)) for _ in range(2)]   # ping-pong gradient buffers
         self.Fe = m.d_inp if m.static else 0
         self.feat = zeros_f((B, D + self.Fe))
-        self.dfeat = zeros_f((B, D + self.Fe))
+        self.dfeat = None if fwd_only else zeros_f((B, D + self.Fe))
         self.hid = zeros_f((B, D + self.Fe))
-        self.dhid = zeros_f((B, D + self.Fe))
+        self.dhid = None if fwd_only else zeros_f((B, D + self.Fe))
         self.logits = zeros_f((B, m.n_classes))
-        self.dlogits = zeros_f((B, m.n_classes))
-        self.loss = torch.zeros((), **f32)
+        self.dlogits = None if fwd_only else zeros_f((B, m.n_classes))
+        self.loss = None if fwd_only else torch.zeros((), **f32)
         dh = D + self.Fe
-        self.wg_ws = u8(max(lib.rd_linear_bwd_weight_workspace_bytes(B, dh, dh),
-                            lib.rd_linear_bwd_weight_workspace_bytes(B, m.n_classes, dh),
-                            lib.rd_linear_bwd_weight_workspace_bytes(B, max(self.Fe, 1), max(m.d_static, 1))))
+        self.wg_ws = None if fwd_only else u8(max(lib.rd_linear_bwd_weight_workspace_bytes(B, dh, dh),
+                                                  lib.rd_linear_bwd_weight_workspace_bytes(B, m.n_classes, dh),
+                                                  lib.rd_linear_bwd_weight_workspace_bytes(B, max(self.Fe, 1), max(m.d_static, 1))))
         # classifier head + loss + their backward as two launches (rd_head.hip) when the sizes fit, else operator by operator
         self.head_fused = bool(lib.rd_head_train_supported(D, self.Fe, m.n_classes))
         self.head_ws = u8(lib.rd_head_train_workspace_bytes(B, dh, m.n_classes)) if self.head_fused else None
@@ -268,7 +278,8 @@ class TrainStep:
         for i, layer in enumerate(m.transformer_encoder.layers):
             pre = "transformer_encoder.layers.%d." % i
             self.enc_w.append(_lib.RdEncoderPtrs(*[self.P[pre + n].data_ptr() for n in ops.ENC_PARAM_NAMES]))
-            self.enc_g.append(_lib.RdEncoderPtrs(*[self.G[pre + n].data_ptr() for n in ops.ENC_PARAM_NAMES]))
+            if not fwd_only:
+                self.enc_g.append(_lib.RdEncoderPtrs(*[self.G[pre + n].data_ptr() for n in ops.ENC_PARAM_NAMES]))
 
     # ------------------------------------------------------------------------------------------
     def _call(self, name, *a):
@@ -406,16 +417,8 @@ class TrainStep:
         B, D, Fe = self.B, self.D, self.Fe
         dh = D + Fe
         c = self._call
-        c("rd_masked_mean_fwd", sp, D, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]), _p(self.feat), dh, st)
-        if Fe:
-            emb_out = self.feat[:, D:]                                       # right block of [agg | emb]
-            c("rd_linear_fwd", B, Fe, m.d_static, _p(b["static"]), m.d_static, _p(P["emb.weight"]), _p(P["emb.bias"]),
-              ctypes.c_void_p(emb_out.data_ptr()), dh, 0, st)
-        c("rd_linear_fwd", B, dh, dh, _p(self.feat), dh, _p(P["mlp_static.0.weight"]), _p(P["mlp_static.0.bias"]),
-          _p(self.hid), dh, 1, st)
         C = m.n_classes
-        c("rd_linear_fwd", B, C, dh, _p(self.hid), dh, _p(P["mlp_static.2.weight"]), _p(P["mlp_static.2.bias"]),
-          _p(self.logits), C, 0, st)
+        self._head_forward_by_operator(st)
         # ---------------- loss: mean cross entropy (code/Raindrop.py:255,322) and its gradient ----------
         c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
         # ---------------- backward ----------------
@@ -432,6 +435,23 @@ class TrainStep:
             c("rd_linear_bwd_weight", B, Fe, m.d_static, ctypes.c_void_p(demb.data_ptr()), dh, _p(b["static"]),
               m.d_static, _p(G["emb.weight"]), _p(G["emb.bias"]), ws, wsn, st)
         c("rd_masked_mean_bwd", sp, D, _p(self.dfeat), dh, _p(self.mask), _p(b["lengths"]), _p(cur), st)
+
+    def _head_forward_by_operator(self, st):
+        """The forward half of `_head_by_operator`, up to the logits: the calls the eager model makes (models_rd.py forward)."""
+        m, b, P, sp = self.model, self.batch, self.P, self.sp
+        B, D, Fe = self.B, self.D, self.Fe
+        dh = D + Fe
+        c = self._call
+        c("rd_masked_mean_fwd", sp, D, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]), _p(self.feat), dh, st)
+        if Fe:
+            emb_out = self.feat[:, D:]                                       # right block of [agg | emb]
+            c("rd_linear_fwd", B, Fe, m.d_static, _p(b["static"]), m.d_static, _p(P["emb.weight"]), _p(P["emb.bias"]),
+              ctypes.c_void_p(emb_out.data_ptr()), dh, 0, st)
+        c("rd_linear_fwd", B, dh, dh, _p(self.feat), dh, _p(P["mlp_static.0.weight"]), _p(P["mlp_static.0.bias"]),
+          _p(self.hid), dh, 1, st)
+        C = m.n_classes
+        c("rd_linear_fwd", B, C, dh, _p(self.hid), dh, _p(P["mlp_static.2.weight"]), _p(P["mlp_static.2.bias"]),
+          _p(self.logits), C, 0, st)
 
     def _with_cell(self, fn):
         """Run `fn` with this step's seed cell registered.  The registration is read when a kernel is ENQUEUED (the pointer

@@ -59,7 +59,7 @@ class BetaTrainStep(TrainStep):
         if model.d_ob != 4 or model.d_pe != 16 or model.d_inp > 1024:
             raise _lib.RaindropHipError("BetaTrainStep: the use_beta stage needs d_ob = 4, d_pe = 16 and at most 1024 sensors "
                                         "(got %d, %d, %d)" % (model.d_ob, model.d_pe, model.d_inp))
-        TrainStep._validate_shapes_only(model, batch)
+        TrainStep._validate_shapes_only(model, batch, labels=labels)
 
     def _k1_buffer_bytes(self):
         """self.k1_saved / self.k1_ws are the use_beta stage's buffers here (the default branch's are not allocated)"""
