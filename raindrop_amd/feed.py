@@ -220,7 +220,7 @@ def _eval_step(model, ds, B):
     key = (int(B), int(ds.T), int(ds.W), int(ds.ds), str(ds.dev), int(_lib.load().rd_get_precision()),
            os.environ.get("RD_TOKEN_PLAN", "1") != "0", bool(getattr(model, "use_beta", False)), bool(getattr(model, "compute_distance", False)))
     step = steps.get(key)
-    if step is not None and step._impl._param_ptrs() != step._impl._ptrs:
+    if step is not None and step._param_ptrs() != step._ptrs:
         step = None
     if step is None:
         steps.pop(key, None)

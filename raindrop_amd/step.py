@@ -1,4 +1,4 @@
-"""Static training step for `Raindrop_v2`: forward + CrossEntropyLoss + backward as ONE hipGraph.
+"""Static steps for `Raindrop_v2`: forward + CrossEntropyLoss + backward as ONE hipGraph.
 
 `code/Raindrop.py:319-323` runs `model.forward -> criterion -> loss.backward()` through autograd,
 ~100 host-side launches per step.  Every stage of this model already has a forward and a backward
@@ -13,11 +13,25 @@ Python in the replay path, every buffer allocated once:
     ... the same chain backwards, each gradient written straight into its slice of the flat
     gradient buffer (raindrop_amd.dp.FlatGradAllReduce): no accumulate kernels, no packing copy.
 
+How the host layer is laid out:
+
+* `Step` owns the buffers (`_Arena`), one enqueue method per STAGE (`_begin`, `_sensor_fwd`, `_enc_fwd`, `_head_train`,
+  `_head_fwd`, `_head_bwd`, `_enc_bwd_top`, `_enc_bwd_rest`, `_sensor_bwd`) and the table `Step.PARTS`, which says which stages
+  make up each part a caller may enqueue or capture.  Every stage enqueues through the per-instance hook `_call`.
+* `has_backward` is a constructor-level fact: without it (raindrop_amd/evalstep.py) no gradient table, gradient buffer, backward
+  workspace, seed cell or trailing rider exists, and the head runs operator by operator up to the logits.
+* What differs between the default branch and `use_beta` sits in a sensor-stage object (`SensorStage` here, `BetaSensorStage` in
+  raindrop_amd/step_beta.py): model validation, buffer sizes, extra buffers, the forward and the backward call, and whether
+  rd_step_prepare's K1 weight tiles apply.
+* `capture_graphs` is the one place that warms up on a side stream, joins, synchronizes and captures.
+* `TrainStep` adds what training needs: the two-graph data-parallel form, the autotune of the row-block knobs, the measurement
+  captures of bench.py, `capture_full` with the optimizer inside.
+
 The captured graph is replayed per step; dropout masks change per replay through the device seed
 cell (`rd_set_seed_cell` / `rd_seed_cell_advance`), which the graph bumps itself.  The gradient
 all-reduce (N > 1) and the Adam kernel stay outside the graph.  The eager model (`models_rd.py`)
 and this step call the SAME kernels in the same order; `tests/test_gpu_parity.py` checks that the
-gradients agree bit for bit.
+gradients agree bit for bit, `tests/test_step_launches_gpu.py` that every form enqueues what it always did.
 """
 import contextlib
 import ctypes
@@ -46,6 +60,33 @@ def _graph_capture(graph, **kw):
             gc.enable()
 
 
+def warm_up(enqueue, passes=2, no_grad=True):
+    """`enqueue()` `passes` times on a side stream (lazy initialisations happen here, not in a capture), joined and synchronized."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side), (torch.no_grad() if no_grad else contextlib.nullcontext()):
+        for _ in range(passes):
+            enqueue()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+
+
+def capture_graphs(bodies, warm=None):
+    """One hipGraph per callable of `bodies`, captured in order out of one memory pool, after two warm-up passes of `warm`
+    (default: the bodies in order).  Replaying the graphs in order is what the bodies enqueue."""
+    def all_bodies():
+        for body in bodies:
+            body()
+    warm_up(warm or all_bodies)
+    graphs = []
+    for body in bodies:
+        g = torch.cuda.CUDAGraph()
+        with torch.no_grad(), _graph_capture(g, **({"pool": graphs[-1].pool()} if graphs else {})):
+            body()
+        graphs.append(g)
+    return graphs
+
+
 def _p(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
@@ -64,63 +105,147 @@ def plan_supported(d_inp, d_ob, T, D, nhead, nhid, precision):
             and D % 4 == 0 and nhid % 4 == 0 and env_on and os.environ.get("RD_ATTN_BIG", "0") == "0")
 
 
-class TrainStep:
-    plan_needs_fused_head = True      # the training head's backward (rd_masked_mean_bwd) does not follow a plan; a forward-only step's head does
+def validate_batch(model, batch, labels=True):
+    """The step hands raw data_ptr()s to the C-ABI: everything the autograd wrappers check per call is checked here
+    once (dtype, contiguity, device, shapes, label range).  Labels are read on the host ONCE, at construction."""
+    T, B = batch["src"].shape[0], batch["src"].shape[1]
+    want = {"src": (torch.float32, (T, B, 2 * model.d_inp)), "times": (torch.float32, (T, B)),
+            "lengths": (torch.int64, (B,))}
+    if labels:
+        want["y"] = (torch.int64, (B,))
+    if model.static:
+        want["static"] = (torch.float32, (B, model.d_static))
+    dev = batch["src"].device
+    for k, (dt, shape) in want.items():
+        t = batch.get(k)
+        if t is None or not t.is_cuda or t.device != dev:
+            raise _lib.RaindropHipError("TrainStep: batch[%r] must be a tensor on %s" % (k, dev))
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.RaindropHipError("TrainStep: batch[%r] must be contiguous %s %s, got %s %s" % (
+                k, dt, shape, t.dtype, tuple(t.shape)))
+    if T != model.max_len:
+        raise _lib.RaindropHipError("TrainStep: src.shape[0] (%d) must equal max_len (%d)" % (T, model.max_len))
+    if B > 0 and labels:
+        lo, hi = int(batch["y"].min()), int(batch["y"].max())
+        if lo < 0 or hi >= model.n_classes:
+            raise _lib.RaindropHipError("TrainStep: labels must lie in [0, %d), got [%d, %d]" % (model.n_classes, lo, hi))
 
-    def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 module_mode=False):
-        """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
-        live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
-        of device tensors that are REUSED every step (copy new data into them).
-        token_plan: store and process only the live (sample, step) rows (include/raindrop_hip.h "token plan": the padding mask of
-        code/models_rd.py:298-299 applied as a layout; same logits, loss and gradients).  None = environment RD_TOKEN_PLAN
-        (default on) where the shape supports it."""
-        self.model, self.flat, self.batch = model, flat, batch
-        # module_mode (raindrop_amd.graph_module): the loss is the CALLER's -- the step is cut into parts 'mf' (forward up to the
-        # logits) and 'mb' (backward from self.dlogits, which the caller fills), batch carries no labels
-        self.module_mode = bool(module_mode)
-        # split: capture the step as TWO graphs -- (A) forward + loss + the backward of the head and the last encoder layer, (B) the
-        # rest of the backward pass -- so that a data-parallel caller can start the all-reduce of the gradients A has finished
-        # (run(between=...)) beside B.  None = on when torch.distributed runs more than one rank (RD_DP_OVERLAP=0 turns it off).
-        if split is None:
-            import torch.distributed as dist
-            split = (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-                     and os.environ.get("RD_DP_OVERLAP", "1") != "0")
-        self.split = bool(split) and len(model.transformer_encoder.layers) >= 2
-        self._want_plan = (os.environ.get("RD_TOKEN_PLAN", "1") != "0") if token_plan is None else bool(token_plan)
-        self.autotune, self.tuned_rows32, self.tuned_waves16 = bool(autotune), None, None
+
+class SensorStage:
+    """The sensor stage of the DEFAULT branch (rd_sensor_stage_fwd / rd_msgpass_bwd: code/models_rd.py:317's `use_beta = False`,
+    distance exactly 0), and the interface a step asks its sensor stage through."""
+    prepared_tiles = True         # rd_step_prepare's K1 weight tiles are this stage's
+    distance = None
+
+    def check(self, model):
+        """A model built with the paper's branch switched on would silently train a different network here (and never see
+        gradients for increase_dim / map_weights): refuse it."""
+        if getattr(model, "use_beta", False) or getattr(model, "compute_distance", False):
+            raise _lib.RaindropHipError("TrainStep: Raindrop_v2(use_beta=True / compute_distance=True) runs on the eager model "
+                                        "surface only (model.forward + autograd); the captured step implements the default branch")
+
+    def buffer_bytes(self, step):
+        """(saved, workspace) bytes: the sizes of step.k1_saved / step.k1_ws (rd_msgpass_workspace_bytes is the backward's)"""
+        return (int(step.lib.rd_msgpass_saved_bytes(step.sp)),
+                int(step.lib.rd_msgpass_workspace_bytes(step.sp)) if step.has_backward else 0)
+
+    def alloc(self, step):
+        pass
+
+    def _weights(self, P):
+        return [P["ob_propagation" + n] for n in (".lin_value.weight", ".lin_value.bias", "_layer2.lin_value.weight", "_layer2.lin_value.bias")]
+
+    def forward(self, s, st):
+        b, P = s.batch, s.P
+        W1, b1, W2, b2 = self._weights(P)
+        s._call("rd_sensor_stage_fwd_prepared" if s.prep_k1 else "rd_sensor_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]),
+                _p(b["lengths"]), _p(s.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2), _p(s.graph_info["ssum"]), s.p_drop,
+                s.seed, _p(s.z), _p(s.mask), _p(s.k1_saved), s.k1_saved.numel(), st)
+
+    def backward(self, s, cur, st):
+        b, P = s.batch, s.P
+        W1, _, W2, _ = self._weights(P)
+        s._call("rd_msgpass_bwd", s.sp, _p(b["src"]), _p(P["R_u"]), _p(W1), _p(W2), _p(s.graph_info["ssum"]), s.p_drop,
+                _p(s.k1_saved), s.k1_saved.numel(), _p(s.z), _p(cur), s.D, *[_p(g) for g in self._weights(s.G)], _p(s.G["R_u"]),
+                _p(s.k1_ws), s.k1_ws.numel(), st)
+
+
+class _Arena:
+    """Every buffer of a step carved out of ONE zero-filled allocation (round 6; RD_STEP_ARENA=0: separate torch allocations, A/B):
+    the large ones on 2-MB boundaries, the small ones (< 1 MB: head workspace, features, plan, ...) packed at 256-byte
+    granularity into a common 16-MB region in front.  Why: the K1 backward kernel's duration was bimodal BETWEEN PROCESSES (16.4
+    vs 18.6 us, HISTORY round 5: "it follows how the process's memory is mapped") -- with one contiguous mapping it is
+    16.2-16.6 us in every process and the step's kernel sum drops 0.6 % (four processes each, alternating, one call:
+    profiles/r06_step_arena_ab.txt).  Every kernel of a step starts on cold translations (~1 GB of traffic since its last run);
+    fewer, larger mappings are fewer walks.  `large`: the byte counts of the large buffers, known up front; a buffer the list
+    missed gets an allocation of its own.  Zero-filled: with a token plan parts of these buffers are never written, and a ghost
+    product (x 0) of an uninitialised NaN pattern would not be 0."""
+
+    def __init__(self, dev, large):
+        self.dev, self.buf = dev, None
+        if os.environ.get("RD_STEP_ARENA", "1") == "1":
+            small_cap = 16 << 20
+            self.buf = torch.zeros(sum(self.al(n) for n in large) + small_cap + (1 << 21), dtype=torch.uint8, device=dev)
+            self.small = (-self.buf.data_ptr()) % (1 << 21)
+            self.small_end = self.off = self.small + small_cap
+
+    @staticmethod
+    def al(n):
+        return (max(int(n), 256) + (1 << 21) - 1) >> 21 << 21
+
+    def u8(self, nbytes):
+        n = max(int(nbytes), 256)
+        if self.buf is not None:
+            if n < (1 << 20) and self.small + n <= self.small_end:
+                o = self.small
+                self.small += (n + 255) >> 8 << 8
+                return self.buf[o:o + n]
+            o = self.off
+            self.off += self.al(n)
+            if self.off <= self.buf.numel():
+                return self.buf[o:o + n]
+        return torch.zeros(n, dtype=torch.uint8, device=self.dev)
+
+    def zeros(self, shape):
+        if self.buf is None:
+            return torch.zeros(shape, dtype=torch.float32, device=self.dev)
+        n = int(torch.Size(shape).numel()) * 4
+        return self.u8(n)[:n].view(torch.float32).view(shape)
+
+
+class Step:
+    """Buffers, stages and parts of a captured step; `TrainStep` and `EvalStep` (raindrop_amd/evalstep.py) are built on it."""
+    # part -> the stages it enqueues, in order.  None: the whole training step; 'a' / 'b': the two halves of the data-parallel
+    # form (TrainStep.__init__); 'begin' / 'k1f' / 'mid' / 'k1b': the step cut around the message-passing stage, 'enc' / 'head' /
+    # 'encb': 'mid' cut further (capture_segments / capture_marked: bench.py times the K1 launches and the encoder layers as they
+    # run INSIDE the step); 'mf' / 'mb': forward up to the logits and backward from `dlogits` (graph_module; EvalStep runs 'mf')
+    PARTS = {
+        None:    ("begin", "sensor_fwd", "enc_fwd", "head_train", "enc_bwd_top", "enc_bwd_rest", "sensor_bwd"),
+        "a":     ("begin", "sensor_fwd", "enc_fwd", "head_train", "enc_bwd_top"),
+        "b":     ("enc_bwd_rest", "sensor_bwd"),
+        "begin": ("begin",),
+        "k1f":   ("sensor_fwd",),
+        "mid":   ("enc_fwd", "head_train", "enc_bwd_top", "enc_bwd_rest"),
+        "enc":   ("enc_fwd",),
+        "head":  ("head_train",),
+        "encb":  ("enc_bwd_top", "enc_bwd_rest"),
+        "k1b":   ("sensor_bwd",),
+        "mf":    ("begin", "sensor_fwd", "enc_fwd", "head_fwd"),
+        "mb":    ("head_bwd", "enc_bwd_top", "enc_bwd_rest", "sensor_bwd"),
+    }
+
+    def __init__(self, model, batch, sensor, flat=None, has_backward=True, labels=True, p_drop=None, seed=1234, token_plan=None):
+        """sensor: the sensor-stage object of the model's branch.  has_backward=False: a forward-only step -- no gradient tables,
+        no dx / dfeat / dhid / dlogits / loss / weight-gradient workspace, no backward workspaces, seed cell or trailing riders,
+        dropout off whatever model.training says, and the eager surface's head operator by operator."""
+        self.model, self.flat, self.batch, self.sensor, self.has_backward = model, flat, batch, sensor, bool(has_backward)
         self.dev = batch["src"].device
         self.lib = _lib.load()
         cfgp = float(model.dropout.p) if p_drop is None else float(p_drop)
-        self.p_drop = cfgp if model.training else 0.0
-        self.seed = (int(seed) + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF     # ranks draw different dropout masks
-        self._validate(model, batch, labels=not self.module_mode)
-        self._setup_shapes(dict(zip(flat.names, flat.views)))    # gradient slices in the flat buffer
-        self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev)
-        # side branch for the trailing launches of the step (the weight-gradient reduces, the head's weight gradients: nothing in
-        # the backward chain reads them).  MEASURED round 4, same box, 3 x 300 steps each: 0.554 ms/step with the branch against
-        # 0.521 without -- the fourth time a forked graph loses here (the fork / join edges cost more than the 5-8 us launches
-        # they take off the chain).  Off by default; RD_SIDE_REDUCE=1 turns it on (results are identical).
-        self.side = torch.cuda.Stream(device=self.dev) if os.environ.get("RD_SIDE_REDUCE", "0") == "1" else None
-        # trailing launches (the head's weight-gradient tiles, a layer's slice reduce) parked and appended to the next backward
-        # chain launch as extra workgroups on its idle CUs (include/raindrop_hip.h rd_set_defer_trailing).  Also in the two-graph
-        # data-parallel form: every part ends with rd_flush_trailing (_body), so the last layer's reduce -- whose results the first
-        # gradient bucket's all-reduce needs between the graphs -- is launched on its own at the end of graph A instead of riding
-        # in graph B; the head's tiles ride inside A, layer 0's reduce inside B.  RD_TRAILING_RIDE=0: every launch on its own (A/B).
-        self.ride = self.side is None and os.environ.get("RD_TRAILING_RIDE", "1") != "0"
-        self._setup_plan_and_prepare()
-        if self.split:
-            self._check_split_order()
-        self._ptrs = self._param_ptrs()                          # the captured graph / cached structs hold these addresses
-        self.graph = None
-        self.graph_b = None
-        if use_graph:
-            self._capture()
-
-    def _setup_shapes(self, gview):
-        """Shape struct, sensor graph, parameter / gradient tables and every buffer of the step (raindrop_amd/evalstep.py comes
-        here with an empty gradient table and `forward_only` set)."""
-        model, batch = self.model, self.batch
+        self.p_drop = cfgp if model.training and has_backward else 0.0
+        self.seed = (int(seed) + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF if has_backward else 0   # ranks draw different dropout masks
+        sensor.check(model)
+        validate_batch(model, batch, labels=labels)
         T, B = batch["src"].shape[0], batch["src"].shape[1]
         self.T, self.B = T, B
         self.shp = _lib.shape(B, T, model.d_inp, model.d_ob, d_pe=model.d_pe, nhead=model.nhead, nhid=model.nhid,
@@ -131,65 +256,37 @@ class TrainStep:
         self.graph_info = model._graph(self.dev)                 # adjacency / ssum (built eagerly, once)
         self.ts = model.pos_encoder.timescales(self.dev)
         self.P = dict(model.named_parameters())
-        self.G = gview
+        self.G = dict(zip(flat.names, flat.views)) if has_backward else {}      # gradient slices in the flat buffer
         self._alloc()
-
-    def _setup_plan_and_prepare(self):
-        # token plan: the step's fast paths only (fused message passing, row-block encoder, fused head)
+        self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev) if has_backward else None
+        # side branch for the trailing launches of the step (the weight-gradient reduces, the head's weight gradients: nothing in
+        # the backward chain reads them).  MEASURED round 4, same box, 3 x 300 steps each: 0.554 ms/step with the branch against
+        # 0.521 without -- the fourth time a forked graph loses here (the fork / join edges cost more than the 5-8 us launches
+        # they take off the chain).  Off by default; RD_SIDE_REDUCE=1 turns it on (results are identical).
+        side = has_backward and os.environ.get("RD_SIDE_REDUCE", "0") == "1"
+        self.side = torch.cuda.Stream(device=self.dev) if side else None
+        # trailing launches (the head's weight-gradient tiles, a layer's slice reduce) parked and appended to the next backward
+        # chain launch as extra workgroups on its idle CUs (include/raindrop_hip.h rd_set_defer_trailing).  Also in the two-graph
+        # data-parallel form: every part ends with rd_flush_trailing (_body), so the last layer's reduce -- whose results the first
+        # gradient bucket's all-reduce needs between the graphs -- is launched on its own at the end of graph A instead of riding
+        # in graph B; the head's tiles ride inside A, layer 0's reduce inside B.  RD_TRAILING_RIDE=0: every launch on its own (A/B).
+        self.ride = has_backward and self.side is None and os.environ.get("RD_TRAILING_RIDE", "1") != "0"
+        # token plan: the step's fast paths only (fused message passing, row-block encoder; the TRAINING head's backward,
+        # rd_masked_mean_bwd, does not follow a plan, so a step with a backward needs the fused head for it)
+        self._want_plan = (os.environ.get("RD_TOKEN_PLAN", "1") != "0") if token_plan is None else bool(token_plan)
         self.plan = None
-        if self._want_plan and (self.head_fused or not self.plan_needs_fused_head) and self._plan_supported():
+        if self._want_plan and (self.head_fused or not has_backward) and self._plan_supported():
             self.plan = torch.zeros(max(int(self.lib.rd_token_plan_bytes(self.sp)) // 4, 64), dtype=torch.int32, device=self.dev)
         # all weight splits of the step in one launch (rd_step_prepare) where the shape takes prepared tiles
         enc_ok, k1_ok = ctypes.c_int32(0), ctypes.c_int32(0)
         _lib.call("rd_step_prepare_covers", self.sp, ctypes.byref(enc_ok), ctypes.byref(k1_ok))
         one = os.environ.get("RD_STEP_PREPARE", "1") != "0"
         self.one_begin = os.environ.get("RD_STEP_BEGIN", "1") != "0"      # A/B: token plan and weight splits as one launch
-        self.prep_enc, self.prep_k1 = bool(enc_ok.value) and one, bool(k1_ok.value) and one
+        self.prep_enc, self.prep_k1 = bool(enc_ok.value) and one, bool(k1_ok.value) and one and sensor.prepared_tiles
         self._prep_w = (ctypes.POINTER(_lib.RdEncoderPtrs) * self.nl)(*[ctypes.pointer(w) for w in self.enc_w])
         self._prep_saved = (ctypes.c_void_p * self.nl)(*[t.data_ptr() for t in self.enc_saved])
         self._prep_bytes = (ctypes.c_size_t * self.nl)(*[t.numel() for t in self.enc_saved])
-
-    @staticmethod
-    def _validate(model, batch, labels=True):
-        """The step hands raw data_ptr()s to the C-ABI: everything the autograd wrappers check per call is checked here
-        once (dtype, contiguity, device, shapes, label range).  Labels are read on the host ONCE, at construction."""
-        # The step enqueues the DEFAULT branch of the sensor stage (rd_sensor_stage_fwd / rd_msgpass_bwd: code/models_rd.py:317's
-        # `use_beta = False`, distance exactly 0).  A model built with the paper's branch switched on would silently train a
-        # different network here (and never see gradients for increase_dim / map_weights): refuse it.
-        if getattr(model, "use_beta", False) or getattr(model, "compute_distance", False):
-            raise _lib.RaindropHipError("TrainStep: Raindrop_v2(use_beta=True / compute_distance=True) runs on the eager model "
-                                        "surface only (model.forward + autograd); the captured step implements the default branch")
-        T, B = batch["src"].shape[0], batch["src"].shape[1]
-        want = {"src": (torch.float32, (T, B, 2 * model.d_inp)), "times": (torch.float32, (T, B)),
-                "lengths": (torch.int64, (B,))}
-        if labels:
-            want["y"] = (torch.int64, (B,))
-        if model.static:
-            want["static"] = (torch.float32, (B, model.d_static))
-        dev = batch["src"].device
-        for k, (dt, shape) in want.items():
-            t = batch.get(k)
-            if t is None or not t.is_cuda or t.device != dev:
-                raise _lib.RaindropHipError("TrainStep: batch[%r] must be a tensor on %s" % (k, dev))
-            if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-                raise _lib.RaindropHipError("TrainStep: batch[%r] must be contiguous %s %s, got %s %s" % (
-                    k, dt, shape, t.dtype, tuple(t.shape)))
-        if T != model.max_len:
-            raise _lib.RaindropHipError("TrainStep: src.shape[0] (%d) must equal max_len (%d)" % (T, model.max_len))
-        if B > 0 and labels:
-            lo, hi = int(batch["y"].min()), int(batch["y"].max())
-            if lo < 0 or hi >= model.n_classes:
-                raise _lib.RaindropHipError("TrainStep: labels must lie in [0, %d), got [%d, %d]" % (model.n_classes, lo, hi))
-
-    @staticmethod
-    def _validate_shapes_only(model, batch, labels=True):
-        """dtype / contiguity / device / shape / label checks of `_validate` without its refusal of the paper's branch (AutogradStep)"""
-        ub, cd = getattr(model, "use_beta", False), getattr(model, "compute_distance", False)
-        try:
-            model.use_beta, model.compute_distance = False, False
-            TrainStep._validate(model, batch, labels=labels)
-        finally:
-            model.use_beta, model.compute_distance = ub, cd
+        self._ptrs = self._param_ptrs()                          # the captured graph / cached structs hold these addresses
 
     def _param_ptrs(self):
         return tuple(p.data_ptr() for p in self.P.values()) + tuple(g.data_ptr() for g in self.G.values())
@@ -198,227 +295,132 @@ class TrainStep:
         m = self.model
         return plan_supported(m.d_inp, m.d_ob, self.T, self.D, m.nhead, m.nhid, self.lib.rd_get_precision())
 
-    def _k1_buffer_bytes(self):
-        """(saved, workspace) bytes of the sensor stage this step enqueues: the sizes of self.k1_saved / self.k1_ws"""
-        return int(self.lib.rd_msgpass_saved_bytes(self.sp)), int(self.lib.rd_msgpass_workspace_bytes(self.sp))
-
-    # ------------------------------------------------------------------------------------------
     def _alloc(self):
-        lib, sp, dev, B, T, D = self.lib, self.sp, self.dev, self.B, self.T, self.D
-        m = self.model
-        f32 = dict(dtype=torch.float32, device=dev)
-        # zero-filled: with a token plan parts of these buffers are never written, and a ghost product (x 0) of an uninitialised
-        # NaN pattern would not be 0
-        # Every buffer of the step is carved out of ONE allocation (round 6; RD_STEP_ARENA=0: separate torch allocations, A/B): the
-        # large ones on 2-MB boundaries, the small ones packed into a common region.  Why: the K1 backward kernel's duration was
-        # bimodal BETWEEN PROCESSES (16.4 vs 18.6 us, HISTORY round 5: "it follows how the process's memory is mapped") -- with one
-        # contiguous mapping it is 16.2-16.6 us in every process and the step's kernel sum drops 0.6 % (four processes each,
-        # alternating, one call: profiles/r06_step_arena_ab.txt).  Every kernel of a step starts on cold translations (~1 GB of
-        # traffic since its last run); fewer, larger mappings are fewer walks.
-        arena = os.environ.get("RD_STEP_ARENA", "1") == "1"
-        fwd_only = getattr(self, "forward_only", False)          # raindrop_amd/evalstep.py: no gradient buffers, no backward workspaces
-        if arena:
-            nl_ = len(m.transformer_encoder.layers)
-            al = lambda n: (max(int(n), 256) + (1 << 21) - 1) >> 21 << 21
-            sizes = [al(T * B * D * 4)] * (1 + nl_ + (0 if fwd_only else 2)) + [al(n) for n in self._k1_buffer_bytes()] + \
-                    [al(lib.rd_encoder_layer_saved_bytes(sp))] * nl_ + [al(lib.rd_encoder_layer_workspace_bytes(sp))] * nl_
-            small_cap = 16 << 20                                  # the small buffers' common region (head workspace, features, plan, ...)
-            self._arena = torch.zeros(sum(sizes) + small_cap + (1 << 21), dtype=torch.uint8, device=dev)
-            self._arena_off = (-self._arena.data_ptr()) % (1 << 21)
-            self._small_off, self._small_end = self._arena_off, self._arena_off + small_cap
-            self._arena_off += small_cap
-
-            def carve(nbytes):
-                n = max(int(nbytes), 256)
-                if n < (1 << 20) and self._small_off + n <= self._small_end:
-                    o = self._small_off
-                    self._small_off += (n + 255) >> 8 << 8
-                else:
-                    o = self._arena_off
-                    self._arena_off += al(n)
-                    if self._arena_off > self._arena.numel():     # (sizes above are exact; a shape this list missed falls back)
-                        return torch.zeros(n, dtype=torch.uint8, device=dev)
-                return self._arena[o:o + n]
-            u8 = carve
-            zeros_f = lambda shape: carve(int(torch.Size(shape).numel()) * 4)[:int(torch.Size(shape).numel()) * 4].view(torch.float32).view(shape)
-        else:
-            u8 = lambda n: torch.zeros(max(int(n), 256), dtype=torch.uint8, device=dev)
-            zeros_f = lambda shape: torch.zeros(shape, **f32)
-        self._u8, self._zeros_f = u8, zeros_f
-        self.z = zeros_f((T, B, D))
-        self.mask = torch.empty((B, T), dtype=torch.bool, device=dev)
-        k1_saved_bytes, k1_ws_bytes = self._k1_buffer_bytes()
-        self.k1_saved = u8(k1_saved_bytes)
-        self.k1_ws = u8(k1_ws_bytes)
+        """Every buffer of the step, in the arena's order (the offsets are part of the measured step: _Arena)."""
+        lib, sp, B, T, D, m, bwd = self.lib, self.sp, self.B, self.T, self.D, self.model, self.has_backward
         self.nl = len(m.transformer_encoder.layers)
-        self.x = [self.z] + [zeros_f((T, B, D)) for _ in range(self.nl)]
-        self.enc_saved = [u8(lib.rd_encoder_layer_saved_bytes(sp)) for _ in range(self.nl)]
+        k1_bytes = self.sensor.buffer_bytes(self)
+        enc_saved, enc_ws = lib.rd_encoder_layer_saved_bytes(sp), lib.rd_encoder_layer_workspace_bytes(sp)
+        self._arena = a = _Arena(self.dev, [T * B * D * 4] * (1 + self.nl + (2 if bwd else 0)) + list(k1_bytes)
+                                 + [enc_saved] * self.nl + [enc_ws] * self.nl)
+        grad = lambda shape: a.zeros(shape) if bwd else None
+        self.z = a.zeros((T, B, D))
+        self.mask = torch.empty((B, T), dtype=torch.bool, device=self.dev)
+        self.k1_saved, self.k1_ws = a.u8(k1_bytes[0]), a.u8(k1_bytes[1])
+        self.x = [self.z] + [a.zeros((T, B, D)) for _ in range(self.nl)]
+        self.enc_saved = [a.u8(enc_saved) for _ in range(self.nl)]
         # one workspace per layer: a layer's trailing reduce launch (side branch, rd_set_side_stream) reads its partials while the
         # next layer's backward already writes its own
-        self.enc_wss = [u8(lib.rd_encoder_layer_workspace_bytes(sp)) for _ in range(self.nl)]
+        self.enc_wss = [a.u8(enc_ws) for _ in range(self.nl)]
         self.enc_ws = self.enc_wss[0]
-        self.dx = [None, None] if fwd_only else [zeros_f((T, B, D)) for _ in range(2)]   # ping-pong gradient buffers
+        self.dx = [grad((T, B, D)), grad((T, B, D))]              # ping-pong gradient buffers (_grad_in)
         self.Fe = m.d_inp if m.static else 0
-        self.feat = zeros_f((B, D + self.Fe))
-        self.dfeat = None if fwd_only else zeros_f((B, D + self.Fe))
-        self.hid = zeros_f((B, D + self.Fe))
-        self.dhid = None if fwd_only else zeros_f((B, D + self.Fe))
-        self.logits = zeros_f((B, m.n_classes))
-        self.dlogits = None if fwd_only else zeros_f((B, m.n_classes))
-        self.loss = None if fwd_only else torch.zeros((), **f32)
         dh = D + self.Fe
-        self.wg_ws = None if fwd_only else u8(max(lib.rd_linear_bwd_weight_workspace_bytes(B, dh, dh),
-                                                  lib.rd_linear_bwd_weight_workspace_bytes(B, m.n_classes, dh),
-                                                  lib.rd_linear_bwd_weight_workspace_bytes(B, max(self.Fe, 1), max(m.d_static, 1))))
-        # classifier head + loss + their backward as two launches (rd_head.hip) when the sizes fit, else operator by operator
-        self.head_fused = bool(lib.rd_head_train_supported(D, self.Fe, m.n_classes))
-        self.head_ws = u8(lib.rd_head_train_workspace_bytes(B, dh, m.n_classes)) if self.head_fused else None
-        self.enc_w = []
-        self.enc_g = []
-        for i, layer in enumerate(m.transformer_encoder.layers):
-            pre = "transformer_encoder.layers.%d." % i
-            self.enc_w.append(_lib.RdEncoderPtrs(*[self.P[pre + n].data_ptr() for n in ops.ENC_PARAM_NAMES]))
-            if not fwd_only:
-                self.enc_g.append(_lib.RdEncoderPtrs(*[self.G[pre + n].data_ptr() for n in ops.ENC_PARAM_NAMES]))
+        self.feat, self.dfeat = a.zeros((B, dh)), grad((B, dh))
+        self.hid, self.dhid = a.zeros((B, dh)), grad((B, dh))
+        self.logits, self.dlogits = a.zeros((B, m.n_classes)), grad((B, m.n_classes))
+        self.loss = torch.zeros((), dtype=torch.float32, device=self.dev) if bwd else None
+        self.wg_ws = a.u8(max(lib.rd_linear_bwd_weight_workspace_bytes(B, dh, dh),
+                              lib.rd_linear_bwd_weight_workspace_bytes(B, m.n_classes, dh),
+                              lib.rd_linear_bwd_weight_workspace_bytes(B, max(self.Fe, 1), max(m.d_static, 1)))) if bwd else None
+        # classifier head + loss + their backward as two launches (rd_head.hip) when the sizes fit, else operator by operator.
+        # Forward-only: the eager surface's head in both layouts (raindrop_amd/evalstep.py has the reason)
+        self.head_fused = bwd and bool(lib.rd_head_train_supported(D, self.Fe, m.n_classes))
+        self.head_ws = a.u8(lib.rd_head_train_workspace_bytes(B, dh, m.n_classes)) if self.head_fused else None
+        tables = lambda T_: [_lib.RdEncoderPtrs(*[T_["transformer_encoder.layers.%d.%s" % (i, n)].data_ptr() for n in ops.ENC_PARAM_NAMES])
+                             for i in range(self.nl)]
+        self.enc_w, self.enc_g = tables(self.P), tables(self.G) if bwd else []
+        self.sensor.alloc(self)
 
-    # ------------------------------------------------------------------------------------------
+    # ---- stages: each enqueues on the current stream through self._call, no host sync ------------------------------------------
     def _call(self, name, *a):
         _lib.call(name, *a)
 
-    def _body(self, part=None):
-        """_body_impl + the join of the side branch: launches forked inside this part (weight-gradient reduces, the head's weight
-        gradients: rd_set_side_stream) are complete, in stream order, when the part is."""
-        self._body_impl(part)
-        _lib.call("rd_flush_trailing", ops._stream())              # a parked trailing launch nobody picked up (layer 0's reduce)
-        _lib.call("rd_side_join", ops._stream())
+    def _grad_in(self, i):
+        """The buffer of the ping-pong pair that holds d loss / d x[i + 1], which layer i's backward READS (and the layer above,
+        or the head, wrote): dx[0] for the top layer, alternating downwards; _grad_in(-1) is what the sensor stage reads."""
+        return self.dx[(self.nl - 1 - i) % 2]
 
-    def _body_impl(self, part=None):
-        """Enqueue one forward + loss + backward on the current stream (no host sync).  part 'a' / 'b': the two halves of the split
-        form (see __init__); 'begin' / 'k1f' / 'mid' / 'k1b': the step cut around the message-passing stage, 'enc' / 'head' / 'encb':
-        'mid' cut further into encoder forward | head + loss | encoder backward (capture_segments: bench.py times the K1 launches
-        and the encoder layers as they run INSIDE the step); None: everything."""
-        if part == "b":
-            return self._body_tail(self.nl - 2)
-        m, b, P, G, sp = self.model, self.batch, self.P, self.G, self.sp
-        st = ops._stream()
-        B, T, D, Fe = self.B, self.T, self.D, self.Fe
-        dh = D + Fe
-        c = self._call
+    def _begin(self):
+        """Token plan, seed bump and weight splits: one launch (rd_step_begin) where all three exist, else one each."""
+        b, P, sp, st, c = self.batch, self.P, self.sp, ops._stream(), self._call
         W1, W2 = P["ob_propagation.lin_value.weight"], P["ob_propagation_layer2.lin_value.weight"]
-        if part == "k1b":
-            return self._k1_bwd(self.dx[self.nl % 2], st)
-        if part == "mb":                                  # module mode: backward from the caller's d loss / d logits
-            self._head_module(self.dx[0], st, backward=True)
-            return self._body_tail(self.nl - 1, self.dx[0])
-        if part in (None, "a", "begin", "mf"):
-            prep = self.prep_enc or self.prep_k1
-            prep_args = (self.nl if self.prep_enc else 0, self._prep_w, self._prep_saved, self._prep_bytes,
-                         _p(W1) if self.prep_k1 else None, _p(W2) if self.prep_k1 else None, _p(self.k1_saved), self.k1_saved.numel(), st)
-            cell = _p(self.seed_cell) if self.p_drop > 0.0 else None
-            if self.plan is not None and prep and self.one_begin:             # plan + seed bump + every weight split: ONE launch
-                c("rd_step_begin", sp, _p(b["lengths"]), _p(self.plan), cell, 1, *prep_args)
-            else:
-                if self.plan is not None:                                      # lengths -> token plan (+ the seed bump: one launch)
-                    c("rd_token_plan", sp, _p(b["lengths"]), _p(self.plan), cell, 1, st)
-                elif self.p_drop > 0.0:
-                    c("rd_seed_cell_advance", _p(self.seed_cell), 1, st)       # fresh masks per replay
-                if prep:
-                    c("rd_step_prepare", sp, *prep_args)
-            if part == "begin":
-                return
-        # ---------------- forward ----------------
-        if part in (None, "a", "k1f", "mf"):
-            self._k1_fwd(st)
-            if part == "k1f":
-                return
-        if part == "encb":
-            return self._body_tail(self.nl - 1, self.dx[0], k1=False)
-        if part != "head":
-            for i in range(self.nl):
-                c("rd_encoder_layer_fwd", sp, i | (0x10000 if self.prep_enc else 0), _p(self.x[i]), _p(self.mask), ctypes.byref(self.enc_w[i]), self.p_drop,
-                  self.seed, _p(self.x[i + 1]), _p(self.enc_saved[i]), self.enc_saved[i].numel(), _p(self.enc_wss[i]),
-                  self.enc_wss[i].numel(), st)
-            if part == "enc":
-                return
-        cur = self.dx[0]
-        if part == "mf":                                  # module mode: forward ends with the logits
-            return self._head_module(cur, st, backward=False)
-        if self.head_fused:
-            e = (lambda n: _p(P[n]) if Fe else None)
-            ge = (lambda n: _p(G[n]) if Fe else None)
-            c("rd_head_train", sp, D, m.d_static if Fe else 0, Fe, m.n_classes, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]),
-              _p(b["static"]) if Fe else None, e("emb.weight"), e("emb.bias"), _p(P["mlp_static.0.weight"]),
-              _p(P["mlp_static.0.bias"]), _p(P["mlp_static.2.weight"]), _p(P["mlp_static.2.bias"]), _p(b["y"]), _p(self.loss),
-              _p(self.logits), ge("emb.weight"), ge("emb.bias"), _p(G["mlp_static.0.weight"]), _p(G["mlp_static.0.bias"]),
-              _p(G["mlp_static.2.weight"]), _p(G["mlp_static.2.bias"]), _p(cur), _p(self.head_ws), self.head_ws.numel(), st)
-        else:
-            self._head_by_operator(cur, st)
-        if part == "head":
-            return
-        if part == "a":                                   # the last layer's backward closes part A
-            self._enc_bwd(self.nl - 1, cur, self.dx[1], st)
-            return
-        self._body_tail(self.nl - 1, cur, k1=(part != "mid"))
+        prep = self.prep_enc or self.prep_k1
+        prep_args = (self.nl if self.prep_enc else 0, self._prep_w, self._prep_saved, self._prep_bytes,
+                     _p(W1) if self.prep_k1 else None, _p(W2) if self.prep_k1 else None, _p(self.k1_saved), self.k1_saved.numel(), st)
+        cell = _p(self.seed_cell) if self.p_drop > 0.0 else None
+        if self.plan is not None and prep and self.one_begin:
+            return c("rd_step_begin", sp, _p(b["lengths"]), _p(self.plan), cell, 1, *prep_args)
+        if self.plan is not None:                                          # lengths -> token plan (+ the seed bump: one launch)
+            c("rd_token_plan", sp, _p(b["lengths"]), _p(self.plan), cell, 1, st)
+        elif self.p_drop > 0.0:
+            c("rd_seed_cell_advance", _p(self.seed_cell), 1, st)           # fresh masks per replay
+        if prep:
+            c("rd_step_prepare", sp, *prep_args)
 
-    def _k1_fwd(self, st):
-        """The sensor stage's forward into self.z / self.mask (BetaTrainStep, raindrop_amd/step_beta.py, enqueues the use_beta one)."""
-        b, P = self.batch, self.P
-        W1, b1 = P["ob_propagation.lin_value.weight"], P["ob_propagation.lin_value.bias"]
-        W2, b2 = P["ob_propagation_layer2.lin_value.weight"], P["ob_propagation_layer2.lin_value.bias"]
-        self._call("rd_sensor_stage_fwd_prepared" if self.prep_k1 else "rd_sensor_stage_fwd", self.sp, _p(b["src"]), _p(b["times"]),
-                   _p(b["lengths"]), _p(self.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2), _p(self.graph_info["ssum"]), self.p_drop,
-                   self.seed, _p(self.z), _p(self.mask), _p(self.k1_saved), self.k1_saved.numel(), st)
+    def _sensor_fwd(self):
+        self.sensor.forward(self, ops._stream())                           # -> self.z, self.mask
 
-    def _enc_bwd(self, i, cur, nxt, st):
-        self._call("rd_encoder_layer_bwd", self.sp, i, _p(self.x[i]), _p(self.mask), ctypes.byref(self.enc_w[i]), self.p_drop,
-                   self.seed, _p(self.enc_saved[i]), self.enc_saved[i].numel(), _p(cur), _p(nxt), ctypes.byref(self.enc_g[i]),
-                   _p(self.enc_wss[i]), self.enc_wss[i].numel(), st)
+    def _sensor_bwd(self):
+        self.sensor.backward(self, self._grad_in(-1), ops._stream())
 
-    def _body_tail(self, top, cur=None, k1=True):
-        """Backward of encoder layers top .. 0 and (k1) of the sensor stage; the entry gradient is dx[0] for the top layer of the
-        stack (written by the head) and alternates between the two buffers from there."""
-        st = ops._stream()
-        if cur is None:                                   # layer `top` reads what layer top + 1 wrote
-            cur = self.dx[(self.nl - 1 - top) % 2]
-        for i in range(top, -1, -1):
-            nxt = self.dx[1] if cur is self.dx[0] else self.dx[0]
-            self._enc_bwd(i, cur, nxt, st)
-            cur = nxt
-        if k1:
-            self._k1_bwd(cur, st)
+    def _enc_fwd(self):
+        for i in range(self.nl):
+            self._call("rd_encoder_layer_fwd", self.sp, i | (0x10000 if self.prep_enc else 0), _p(self.x[i]), _p(self.mask),
+                       ctypes.byref(self.enc_w[i]), self.p_drop, self.seed, _p(self.x[i + 1]), _p(self.enc_saved[i]),
+                       self.enc_saved[i].numel(), _p(self.enc_wss[i]), self.enc_wss[i].numel(), ops._stream())
 
-    def _k1_bwd(self, cur, st):
-        b, P, G, sp = self.batch, self.P, self.G, self.sp
-        W1, W2 = P["ob_propagation.lin_value.weight"], P["ob_propagation_layer2.lin_value.weight"]
-        self._call("rd_msgpass_bwd", sp, _p(b["src"]), _p(P["R_u"]), _p(W1), _p(W2), _p(self.graph_info["ssum"]), self.p_drop,
-                   _p(self.k1_saved), self.k1_saved.numel(), _p(self.z), _p(cur), self.D, _p(G["ob_propagation.lin_value.weight"]),
-                   _p(G["ob_propagation.lin_value.bias"]), _p(G["ob_propagation_layer2.lin_value.weight"]),
-                   _p(G["ob_propagation_layer2.lin_value.bias"]), _p(G["R_u"]), _p(self.k1_ws), self.k1_ws.numel(), st)
+    def _enc_bwd(self, hi, lo):
+        """Backward of encoder layers hi .. lo."""
+        for i in range(hi, lo - 1, -1):
+            self._call("rd_encoder_layer_bwd", self.sp, i, _p(self.x[i]), _p(self.mask), ctypes.byref(self.enc_w[i]), self.p_drop,
+                       self.seed, _p(self.enc_saved[i]), self.enc_saved[i].numel(), _p(self._grad_in(i)), _p(self._grad_in(i - 1)),
+                       ctypes.byref(self.enc_g[i]), _p(self.enc_wss[i]), self.enc_wss[i].numel(), ops._stream())
 
-    def _head_module(self, cur, st, backward):
-        """The classifier head around a loss the caller evaluates (module mode): rd_head_forward -> self.logits, rd_head_backward
-        from self.dlogits -> the head's parameter gradients and the encoder stack's entry gradient `cur`."""
-        m, b, P, G, sp = self.model, self.batch, self.P, self.G, self.sp
-        D, Fe = self.D, self.Fe
-        e = (lambda n: _p(P[n]) if Fe else None)
-        ge = (lambda n: _p(G[n]) if Fe else None)
-        common = (sp, D, m.d_static if Fe else 0, Fe, m.n_classes, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]),
-                  _p(b["static"]) if Fe else None, e("emb.weight"), e("emb.bias"), _p(P["mlp_static.0.weight"]),
-                  _p(P["mlp_static.0.bias"]), _p(P["mlp_static.2.weight"]), _p(P["mlp_static.2.bias"]))
-        if not backward:
-            return self._call("rd_head_forward", *common, _p(self.logits), _p(self.head_ws), self.head_ws.numel(), st)
-        self._call("rd_head_backward", *common, _p(self.dlogits), ge("emb.weight"), ge("emb.bias"), _p(G["mlp_static.0.weight"]),
-                   _p(G["mlp_static.0.bias"]), _p(G["mlp_static.2.weight"]), _p(G["mlp_static.2.bias"]), _p(cur), _p(self.head_ws),
-                   self.head_ws.numel(), st)
+    def _enc_bwd_top(self):                                                # the last layer's backward closes part 'a'
+        self._enc_bwd(self.nl - 1, self.nl - 1)
 
-    def _head_by_operator(self, cur, st):
+    def _enc_bwd_rest(self):
+        self._enc_bwd(self.nl - 2, 0)
+
+    def _fused_head_args(self):
+        """The argument list the three fused head kernels share: (inputs and weights, [gradients ..., entry gradient, workspace,
+        its size, stream]); rd_head_forward takes the last three of the second."""
+        m, b, P, G, Fe = self.model, self.batch, self.P, self.G, self.Fe
+        e = lambda T_, n: _p(T_[n]) if Fe else None
+        w = lambda T_: (e(T_, "emb.weight"), e(T_, "emb.bias")) + tuple(_p(T_["mlp_static." + n]) for n in ("0.weight", "0.bias", "2.weight", "2.bias"))
+        return ((self.sp, self.D, m.d_static if Fe else 0, Fe, m.n_classes, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]),
+                 _p(b["static"]) if Fe else None) + w(P),
+                (w(G) if G else ()) + (_p(self._grad_in(self.nl - 1)), _p(self.head_ws), self.head_ws.numel(), ops._stream()))
+
+    def _head_train(self):
+        """Classifier head + mean cross entropy and their backward, down to the encoder stack's entry gradient."""
+        if not self.head_fused:
+            return self._head_by_operator()
+        common, tail = self._fused_head_args()
+        self._call("rd_head_train", *common, _p(self.batch["y"]), _p(self.loss), _p(self.logits), *tail)
+
+    def _head_fwd(self):
+        """The head around a loss the caller evaluates (or none): up to self.logits."""
+        if not self.head_fused:
+            return self._head_forward_by_operator()
+        common, tail = self._fused_head_args()
+        self._call("rd_head_forward", *common, _p(self.logits), *tail[-3:])
+
+    def _head_bwd(self):
+        """From self.dlogits, which the caller fills: the head's parameter gradients and the encoder stack's entry gradient."""
+        if not self.head_fused:
+            raise _lib.RaindropHipError("part 'mb' needs the fused head (rd_head_backward) and a step with a backward")
+        common, tail = self._fused_head_args()
+        self._call("rd_head_backward", *common, _p(self.dlogits), *tail)
+
+    def _head_by_operator(self):
         """masked mean -> [agg | emb] -> mlp_static -> cross entropy and their backward, one C-ABI call per operator."""
-        m, b, P, G, sp = self.model, self.batch, self.P, self.G, self.sp
-        B, D, Fe = self.B, self.D, self.Fe
+        m, b, P, G, sp, st = self.model, self.batch, self.P, self.G, self.sp, ops._stream()
+        B, D, Fe, C = self.B, self.D, self.Fe, m.n_classes
         dh = D + Fe
         c = self._call
-        C = m.n_classes
-        self._head_forward_by_operator(st)
+        self._head_forward_by_operator()
         # ---------------- loss: mean cross entropy (code/Raindrop.py:255,322) and its gradient ----------
         c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
         # ---------------- backward ----------------
@@ -434,12 +436,12 @@ class TrainStep:
             demb = self.dfeat[:, D:]
             c("rd_linear_bwd_weight", B, Fe, m.d_static, ctypes.c_void_p(demb.data_ptr()), dh, _p(b["static"]),
               m.d_static, _p(G["emb.weight"]), _p(G["emb.bias"]), ws, wsn, st)
-        c("rd_masked_mean_bwd", sp, D, _p(self.dfeat), dh, _p(self.mask), _p(b["lengths"]), _p(cur), st)
+        c("rd_masked_mean_bwd", sp, D, _p(self.dfeat), dh, _p(self.mask), _p(b["lengths"]), _p(self._grad_in(self.nl - 1)), st)
 
-    def _head_forward_by_operator(self, st):
+    def _head_forward_by_operator(self):
         """The forward half of `_head_by_operator`, up to the logits: the calls the eager model makes (models_rd.py forward)."""
-        m, b, P, sp = self.model, self.batch, self.P, self.sp
-        B, D, Fe = self.B, self.D, self.Fe
+        m, b, P, sp, st = self.model, self.batch, self.P, self.sp, ops._stream()
+        B, D, Fe, C = self.B, self.D, self.Fe, m.n_classes
         dh = D + Fe
         c = self._call
         c("rd_masked_mean_fwd", sp, D, _p(self.x[-1]), _p(self.mask), _p(b["lengths"]), _p(self.feat), dh, st)
@@ -449,26 +451,68 @@ class TrainStep:
               ctypes.c_void_p(emb_out.data_ptr()), dh, 0, st)
         c("rd_linear_fwd", B, dh, dh, _p(self.feat), dh, _p(P["mlp_static.0.weight"]), _p(P["mlp_static.0.bias"]),
           _p(self.hid), dh, 1, st)
-        C = m.n_classes
         c("rd_linear_fwd", B, C, dh, _p(self.hid), dh, _p(P["mlp_static.2.weight"]), _p(P["mlp_static.2.bias"]),
           _p(self.logits), C, 0, st)
 
+    def _stages(self, part=None):
+        for stage in self.PARTS[part]:
+            getattr(self, "_" + stage)()
+
+    def _body(self, part=None):
+        """The stages of `part` + the join of the side branch: launches forked inside this part (weight-gradient reduces, the
+        head's weight gradients: rd_set_side_stream) are complete, in stream order, when the part is."""
+        self._stages(part)
+        _lib.call("rd_flush_trailing", ops._stream())              # a parked trailing launch nobody picked up (layer 0's reduce)
+        _lib.call("rd_side_join", ops._stream())
+
     def _with_cell(self, fn):
-        """Run `fn` with this step's seed cell registered.  The registration is read when a kernel is ENQUEUED (the pointer
-        travels as a kernel argument), so it is scoped to the enqueue / the capture: a captured graph keeps the cell it was
-        captured with, and nothing else in the process (an eager model, another TrainStep) ever sees this step's cell --
-        dropping a TrainStep can no longer leave a dangling pointer behind."""
-        _lib.call("rd_set_seed_cell", _p(self.seed_cell))
-        _lib.call("rd_set_token_plan", _p(self.plan))
-        _lib.call("rd_set_side_stream", ctypes.c_void_p(self.side.cuda_stream) if self.side is not None else None)
-        _lib.call("rd_set_defer_trailing", 1 if self.ride else 0)
+        """Run `fn` with this step's token plan and -- with a backward -- seed cell, side stream and trailing riders registered.
+        The registration is read when a kernel is ENQUEUED (the pointer travels as a kernel argument), so it is scoped to the
+        enqueue / the capture: a captured graph keeps the cell it was captured with, and nothing else in the process (an eager
+        model, another step) ever sees this step's cell -- dropping a step can not leave a dangling pointer behind."""
+        regs = [("rd_set_token_plan", _p(self.plan), None)]
+        if self.has_backward:
+            regs = [("rd_set_seed_cell", _p(self.seed_cell), None), regs[0],
+                    ("rd_set_side_stream", ctypes.c_void_p(self.side.cuda_stream) if self.side is not None else None, None),
+                    ("rd_set_defer_trailing", 1 if self.ride else 0, 0)]
+        for name, on, _ in regs:
+            _lib.call(name, on)
         try:
             return fn()
         finally:
-            _lib.call("rd_set_seed_cell", None)
-            _lib.call("rd_set_token_plan", None)
-            _lib.call("rd_set_side_stream", None)
-            _lib.call("rd_set_defer_trailing", 0)
+            for name, _, off in regs:
+                _lib.call(name, off)
+
+
+class TrainStep(Step):
+    def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
+                 module_mode=False, sensor=None):
+        """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
+        live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
+        of device tensors that are REUSED every step (copy new data into them).
+        token_plan: store and process only the live (sample, step) rows (include/raindrop_hip.h "token plan": the padding mask of
+        code/models_rd.py:298-299 applied as a layout; same logits, loss and gradients).  None = environment RD_TOKEN_PLAN
+        (default on) where the shape supports it.
+        sensor: the sensor-stage object (default: the default branch's; BetaTrainStep passes the use_beta one)."""
+        # module_mode (raindrop_amd.graph_module): the loss is the CALLER's -- the step is cut into parts 'mf' (forward up to the
+        # logits) and 'mb' (backward from self.dlogits, which the caller fills), batch carries no labels
+        self.module_mode = bool(module_mode)
+        # split: capture the step as TWO graphs -- (A) forward + loss + the backward of the head and the last encoder layer, (B) the
+        # rest of the backward pass -- so that a data-parallel caller can start the all-reduce of the gradients A has finished
+        # (run(between=...)) beside B.  None = on when torch.distributed runs more than one rank (RD_DP_OVERLAP=0 turns it off).
+        if split is None:
+            import torch.distributed as dist
+            split = (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+                     and os.environ.get("RD_DP_OVERLAP", "1") != "0")
+        self.split = bool(split) and len(model.transformer_encoder.layers) >= 2
+        self.autotune, self.tuned_rows32, self.tuned_waves16 = bool(autotune), None, None
+        super().__init__(model, batch, sensor or SensorStage(), flat=flat, labels=not self.module_mode, p_drop=p_drop, seed=seed,
+                         token_plan=token_plan)
+        if self.split:
+            self._check_split_order()
+        self.graph = self.graph_b = self.graph_full = self._full_opt = self._full_hyper = None
+        if use_graph:
+            self._capture()
 
     def _capture(self):
         """Capture the step as one hipGraph (two in the split form).  With `autotune`, the step is captured once per setting of the
@@ -529,52 +573,20 @@ class TrainStep:
         _lib.call("rd_set_rowgemm_rows32", best_r32)                 # eager calls of this process follow the same choice
         _lib.call("rd_set_rowgemm_waves16", best_w16)
 
+
     def _capture_one(self):
         def cap():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):                                         # warm-up: lazy inits happen here
-                    self._body()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self.graph = torch.cuda.CUDAGraph()
-            self.graph_b = None
-            if not self.split:
-                with torch.no_grad(), _graph_capture(self.graph):
-                    self._body()
-                return
-            with torch.no_grad(), _graph_capture(self.graph):
-                self._body("a")
-            self.graph_b = torch.cuda.CUDAGraph()
-            with torch.no_grad(), _graph_capture(self.graph_b, pool=self.graph.pool()):
-                self._body("b")
+            if self.split:
+                self.graph, self.graph_b = capture_graphs([lambda: self._body("a"), lambda: self._body("b")], warm=self._body)
+            else:
+                (self.graph,), self.graph_b = capture_graphs([self._body]), None
         self._with_cell(cap)
 
     def capture_segments(self, parts=("begin", "k1f", "mid", "k1b")):
         """The same step as consecutive hipGraphs, one per part (measurement only: bench.py brackets the 'k1f' / 'k1b' replays with
         HIP events, so the message-passing launches are timed with the cache state, clocks and neighbours they have in the step).
         Replaying the graphs in order is one step."""
-        graphs = []
-
-        def cap():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):
-                    for pt in parts:
-                        self._body(pt)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            pool = None
-            for pt in parts:
-                g = torch.cuda.CUDAGraph()
-                with torch.no_grad(), (_graph_capture(g) if pool is None else _graph_capture(g, pool=pool)):
-                    self._body(pt)
-                pool = g.pool()
-                graphs.append(g)
-        self._with_cell(cap)
-        return graphs
+        return self._with_cell(lambda: capture_graphs([lambda pt=pt: self._body(pt) for pt in parts]))
 
     def capture_marked(self, parts=("begin", "k1f", "enc", "head", "encb", "k1b")):
         """The step as ONE hipGraph with an external timing event recorded in front of every part and behind the last
@@ -582,27 +594,19 @@ class TrainStep:
         step, without the ~10 us a graph boundary costs per segment.  Returns (graph, events); raises where the runtime cannot
         capture external event records (callers fall back to capture_segments)."""
         events = [torch.cuda.Event(enable_timing=True, external=True) for _ in range(len(parts) + 1)]
-        out = []
 
-        def cap():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):
-                    for pt in parts:
-                        self._body(pt)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.no_grad(), _graph_capture(g):
-                for k, pt in enumerate(parts):
-                    events[k].record()
-                    self._body(pt)
-                events[len(parts)].record()
-            out.append(g)
-        self._with_cell(cap)
-        return out[0], events
+        def parts_only():
+            for pt in parts:
+                self._body(pt)
 
+        def marked():
+            for k, pt in enumerate(parts):
+                events[k].record()
+                self._body(pt)
+            events[len(parts)].record()
+        return self._with_cell(lambda: capture_graphs([marked], warm=parts_only))[0], events
+
+    # ------------------------------------------------------------------------------------------
     # ------------------------------------------------------------------------------------------
     def _early_names(self):
         """Parameters whose gradients the first all-reduce bucket of the split form carries: the last encoder layer's and the
@@ -682,6 +686,7 @@ class TrainStep:
         flat.allreduce_wait(rest)
         return loss
 
+
     # ------------------------------------------------------------------------------------------
     def capture_full(self, opt):
         """The WHOLE step as ONE hipGraph (round 5; opt-in): forward + loss + backward, the gradient all-reduce(s) and the optimizer.
@@ -692,41 +697,37 @@ class TrainStep:
         the caller falls back to run_allreduce() + opt.step()."""
         flat = self.flat
         opt.sync_step_cell()
+        # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
+        # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
+        begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
+
+        def warm():                                                        # outside the capture: RCCL's lazy inits, too
+            self._body()
+            flat.allreduce()
+
+        def whole():
+            if begin_adv:
+                opt.register_cell(True)
+            if self.split:
+                off = self.early_grad_offset()
+                self._body("a")
+                opt.register_cell(False)
+                h1 = flat.allreduce_range_async(off, flat.flat.numel())
+                self._body("b")
+                h0 = flat.allreduce_range_async(0, off)
+                flat.allreduce_wait(h1)
+                flat.allreduce_wait(h0)
+            else:
+                self._body()
+                opt.register_cell(False)
+                flat.allreduce()
+            opt.step_captured(advance=not begin_adv)
 
         def cap():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():
-                for _ in range(2):                                         # warm-up outside the capture (RCCL's lazy inits, too)
-                    self._body()
-                    flat.allreduce()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
-            # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
-            begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
             try:
-                with torch.no_grad(), _graph_capture(g):
-                    if begin_adv:
-                        opt.register_cell(True)
-                    if self.split:
-                        off = self.early_grad_offset()
-                        self._body("a")
-                        opt.register_cell(False)
-                        h1 = flat.allreduce_range_async(off, flat.flat.numel())
-                        self._body("b")
-                        h0 = flat.allreduce_range_async(0, off)
-                        flat.allreduce_wait(h1)
-                        flat.allreduce_wait(h0)
-                    else:
-                        self._body()
-                        opt.register_cell(False)
-                        flat.allreduce()
-                    opt.step_captured(advance=not begin_adv)
+                self.graph_full, = capture_graphs([whole], warm=warm)
             finally:
                 opt.register_cell(False)
-            self.graph_full = g
         self._with_cell(cap)
         opt.sync_step_cell()                                               # the warm-up did not step the optimizer; neither did the capture
         self._full_opt = opt
@@ -735,6 +736,8 @@ class TrainStep:
 
     def run_full(self):
         """One replay of capture_full's graph = one training step including the optimizer; returns the loss tensor."""
+        if self.graph_full is None:
+            raise _lib.RaindropHipError("TrainStep.run_full: call capture_full(opt) first")
         if self._param_ptrs() != self._ptrs:
             raise _lib.RaindropHipError("TrainStep: a parameter or gradient buffer moved since construction: build a new TrainStep")
         if self._full_opt.hyper() != self._full_hyper:                     # betas / eps changed: launch constants of the captured
@@ -754,9 +757,7 @@ class TrainStep:
 
     def close(self):
         """Kept for callers of the round-1 API: the seed cell is no longer registered outside run() / capture."""
-        self.graph_full = None
-        self.graph = None
-        self.graph_b = None
+        self.graph = self.graph_b = self.graph_full = None
 
 
 class AutogradStep:
@@ -785,7 +786,7 @@ class AutogradStep:
             raise _lib.RaindropHipError("AutogradStep(distance_weight=%g): the structure distance is the constant 0 unless the model "
                                         "has use_beta=True and compute_distance=True (code/models_rd.py:317,345-346)"
                                         % self.distance_weight)
-        TrainStep._validate_shapes_only(model, batch)
+        validate_batch(model, batch)
         self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev)
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.opt = None
@@ -809,19 +810,16 @@ class AutogradStep:
         return logits, distance, loss
 
     def _capture(self):
+        def one_pass():
+            for p in self.params:
+                p.grad = None
+            self._one()
         _lib.call("rd_set_seed_cell", _p(self.seed_cell))
         try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(3):                                 # warm-up: lazy initialisations, the optimizer's state tensors
-                    for p in self.params:
-                        p.grad = None
-                    self._one()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
+            warm_up(one_pass, passes=3, no_grad=False)             # lazy initialisations, the optimizer's state tensors
             for p in self.params:
                 p.grad = None                                      # the captured backward ALLOCATES the gradients (static addresses)
+            # (not capture_graphs: autograd stays on, and the gradients are reset between the warm-up and the capture)
             self.graph = torch.cuda.CUDAGraph()
             with _graph_capture(self.graph):
                 _lib.call("rd_seed_cell_advance", _p(self.seed_cell), 1, ops._stream())

@@ -165,7 +165,7 @@ def test_replay_sees_weights_changed_in_place(kw, precision_mode):
     if dgot is not None:
         assert torch.equal(dgot, fresh2.distance)
     m2 = m.to("cpu").to(DEV)                                       # moved parameters are refused, as TrainStep does
-    if any(p.data_ptr() != q for p, q in zip(m.parameters(), step._impl._ptrs)):
+    if any(p.data_ptr() != q for p, q in zip(m.parameters(), step._ptrs)):
         with pytest.raises(_lib.RaindropHipError):
             step.run()
 
