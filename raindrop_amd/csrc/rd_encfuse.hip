@@ -404,6 +404,8 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
   const float inv_keep = 1.0f / (1.0f - a.p);
   const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
   EFSTAMP(0);
+  // layout read by tests/test_rowgemm_variants_gpu.py (_live_blocks counts the start stamps to tell the block height): phases at
+  // [0, 256), start of block b at 256 + 2 b, end at 256 + 1024 + 2 b; the backward chain's half begins at 4096 (launch_enc_pre_bwd)
   if (a.stamps && tid == 0) { a.stamps[256 + 2 * blockIdx.x] = wall_clock64(); a.stamps[256 + 2 * blockIdx.x + 1] = clock64(); }
   zero_pad_columns<RT>(Hh, Hl, ntH, tid);                      // columns 16 ntH .. KPH of the h planes (linear2 reduces over KPH)
   // ---- attention rows -> split planes (zero padded to KPD columns, rows beyond M zero) ----

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(64 * WV) void k_rowgemm(RowGemmArgs a) {
   __bf16* Ah = reinterpret_cast<__bf16*>(rsm);
   __bf16* Al = Ah + RG_ROWS * LDA;
   float* stage = reinterpret_cast<float*>(Al + RG_ROWS * LDA);         // [64][260] fp32
-  float* lnred = stage + RG_ROWS * RG_LDS_STAGE;                       // LNB only: [8 waves][2K] dgamma | dbeta partials
+  float* lnred = stage + RG_ROWS * RG_LDS_STAGE;                       // LNB only: [WV waves][2K] dgamma | dbeta partials
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.x * RG_ROWS;
   const int ntiles = (a.N + 15) >> 4;
@@ -191,7 +191,8 @@ __global__ __launch_bounds__(64 * WV) void k_rowgemm(RowGemmArgs a) {
   // while the panel streams in.
   RPanel<KH, RG_NJ> pw;
   if constexpr (LNB) {
-    // ---- LayerNorm backward per row (wave w: rows 8w .. 8w+7 of the block; lane l: columns 4l .. 4l+3) -> split planes ----
+    // ---- LayerNorm backward per row (wave w: rows RPW w .. RPW w + RPW - 1 of the block, RPW = RG_ROWS / WV; lane l: columns
+    // 4l .. 4l+3) -> split planes ----
     constexpr int RPW = RG_ROWS / RG_WAVES;
     const int c = 4 * lane;
     const bool cok = c < a.K, cpl = c < KPc;
@@ -289,7 +290,7 @@ __global__ __launch_bounds__(64 * WV) void k_rowgemm(RowGemmArgs a) {
   RGSTAMP(1);
   lds_barrier();                       // LDS ordering only: do not drain the weight panel (rd_common.h)
   RGSTAMP(2);
-  if constexpr (LNB) {                 // this workgroup's dgamma | dbeta partial: the 8 waves in fixed order
+  if constexpr (LNB) {                 // this workgroup's dgamma | dbeta partial: the WV waves in fixed order
     const int K2 = 2 * a.K;
     for (int i = tid; i < K2; i += RG_THR)
     {
@@ -384,7 +385,7 @@ __global__ __launch_bounds__(64 * WV) void k_rowgemm(RowGemmArgs a) {
     lds_barrier();
     if (rd == 0) RGSTAMP(5);
     if constexpr (LN) {
-      // ---- LayerNorm epilogue: wave w owns rows w, w + 8, ...; lane l owns columns 4l .. 4l+3 of the row
+      // ---- LayerNorm epilogue: wave w owns rows w, w + WV, ... (RG_ROWS / WV of them); lane l owns columns 4l .. 4l+3 of the row
       constexpr int RPW = RG_ROWS / RG_WAVES;
       const int c = 4 * lane;
       const bool cok = c < a.N;

@@ -485,6 +485,11 @@ class Step:
 
 
 class TrainStep(Step):
+    # candidates of the autotune in _capture (masks of rd_set_rowgemm_rows32 / rd_set_rowgemm_waves16): the workgroup heights are
+    # timed at TUNE_WAVES[0], then the other wave masks at the best height.  tests/test_rowgemm_variants_gpu.py runs every pair.
+    TUNE_HEIGHTS = (15, 0, 3, 12)
+    TUNE_WAVES = (12, 15)
+
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
                  module_mode=False, sensor=None):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
@@ -524,7 +529,10 @@ class TrainStep(Step):
         Results: the knobs change which rows share a workgroup, never a row's arithmetic; on the fused row-local chains
         (rd_encfuse.hip: the P19 / P12 widths) no cross-row sum depends on them, so every variant gives the same gradient bits.
         On the unfused LayerNorm-epilogue products (other widths) the dgamma / dbeta partial grouping follows the workgroup
-        height: there the bits depend on the choice, which is why it is recorded (pin it with RD_RG_ROWS32 / RD_RG_WAVES16)."""
+        height: there the bits depend on the choice, which is why it is recorded (pin it with RD_RG_ROWS32 / RD_RG_WAVES16).
+        Held by tests/test_rowgemm_variants_gpu.py: every TUNE_HEIGHTS x TUNE_WAVES pair (and the four corner masks) against the
+        default masks on the row-block path -- output, input gradient and all weight / bias gradients bit-identical, the four
+        LayerNorm affine gradients within 2e-5 of their max-norm."""
         import torch.distributed as dist
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         if not self.autotune or os.environ.get("RD_RG_ROWS32") is not None or os.environ.get("RD_RG_WAVES16") is not None:
@@ -559,15 +567,16 @@ class TrainStep(Step):
             return (time.perf_counter() - t0, graphs)
         # workgroup height first (all / none / plain products only / LayerNorm-fused ones only) at the default wave counts,
         # then the wave count of the plain products at the best height
-        heights = (15, 0, 3, 12)
-        runs = [timed(r32, 12) for r32 in heights]
+        heights = self.TUNE_HEIGHTS
+        runs = [timed(r32, self.TUNE_WAVES[0]) for r32 in heights]
         ts = agree([r[0] for r in runs])
         bi = min(range(len(heights)), key=lambda i: (ts[i], i))
-        best_r32, best_w16, best_graphs, best_t = heights[bi], 12, runs[bi][1], ts[bi]
-        alt = timed(best_r32, 15)
-        alt_t = agree([alt[0]])[0]
-        if alt_t < best_t:
-            best_w16, best_graphs = 15, alt[1]
+        best_r32, best_w16, best_graphs, best_t = heights[bi], self.TUNE_WAVES[0], runs[bi][1], ts[bi]
+        for w16 in self.TUNE_WAVES[1:]:
+            alt = timed(best_r32, w16)
+            alt_t = agree([alt[0]])[0]
+            if alt_t < best_t:
+                best_w16, best_graphs, best_t = w16, alt[1], alt_t
         self.graph, self.graph_b = best_graphs
         self.tuned_rows32, self.tuned_waves16 = best_r32, best_w16
         _lib.call("rd_set_rowgemm_rows32", best_r32)                 # eager calls of this process follow the same choice

@@ -368,6 +368,7 @@ def test_two_ranks_tune_to_the_same_kernel_variants():
     """Under torch.distributed the capture-time tuner sums every variant's time over the ranks before choosing: both ranks must end
     up with the SAME (rows32, waves16) -- the step is then the same program on every rank and the one a single process would tune
     to -- and the all-reduced gradients are bit-identical."""
+    from raindrop_amd.step import TrainStep
     world, port = 2, _free_port()
     mgr = mp.Manager()
     ret = mgr.dict()
@@ -375,7 +376,7 @@ def test_two_ranks_tune_to_the_same_kernel_variants():
     a, b = ret[0], ret[1]
     assert a[0] is not None and a[1] is not None and a[2] and b[2]
     assert (a[0], a[1]) == (b[0], b[1]), (a[:2], b[:2])
-    assert a[0] in (15, 0, 3, 12) and a[1] in (12, 15)
+    assert a[0] in TrainStep.TUNE_HEIGHTS and a[1] in TrainStep.TUNE_WAVES
     assert np.array_equal(a[4], b[4])
 
 

@@ -512,10 +512,18 @@ def test_fused_row_local_chains_match_row_block_products(T, B, p_drop, F, precis
     must agree to summation order (LayerNorm row sums; per-block LayerNorm partials: 32- vs 48-row blocks) in the output and
     the gradients.  B = 150 / 137 (9000 / 8220 rows) make the kernels pick their 48-row blocks on a 256-CU device, B = 256
     (15360 rows) two rounds of 32-row blocks.  F = 34 / 36 are the widths compiled in (P19: 152 x 272, P12: 160 x 288), F = 35
-    runs the runtime-width instantiation."""
+    runs the runtime-width instantiation: encfuse_ok accepts a width pair that is not compiled in only under
+    RD_ENC_SPECIALIZE=0, which that case sets for both runs.  The chains' debug stamps (include/raindrop_hip_debug.h) must be
+    written by the RD_ENC_FUSE=1 run and stay zero in the =0 run: the two runs really took different paths."""
     if precision_mode == "fp32":
         pytest.skip("the fused chains are bf16-mode kernels")
     from raindrop_amd import _lib, ops
+    if F == 35:
+        monkeypatch.setenv("RD_ENC_SPECIALIZE", "0")
+    set_stamps = _lib.load().rd_debug_set_encfuse_stamps
+    set_stamps.argtypes, set_stamps.restype = [ctypes.c_void_p], None
+    stamps = torch.zeros(8192, dtype=torch.int64, device=DEV)          # forward chain [0, 4096), backward chain [4096, 8192)
+    launched = {}
     nhead = 2
     D, nhid = F * 4 + 16, 2 * F * 4
     rng = np.random.default_rng(T * 7 + B)
@@ -527,13 +535,22 @@ def test_fused_row_local_chains_match_row_block_products(T, B, p_drop, F, precis
     p = _enc_params(D, nhid, seed=T)
     shp = _lib.shape(B, T, F, 4, nhead=nhead, nhid=nhid)
     res = {}
-    for fuse in ("0", "1"):
-        monkeypatch.setenv("RD_ENC_FUSE", fuse)
-        xd = x.clone().requires_grad_(True)
-        pd = [p[n].to(DEV).requires_grad_(True) for n in ops.ENC_PARAM_NAMES]
-        y = ops.encoder_layer(xd, mask, shp, 1, p_drop, 77, pd)
-        g = torch.autograd.grad(y, [xd] + pd, dy)
-        res[fuse] = (y.detach().cpu().numpy(), [t.cpu().numpy() for t in g])
+    set_stamps(ctypes.c_void_p(stamps.data_ptr()))
+    try:
+        for fuse in ("0", "1"):
+            monkeypatch.setenv("RD_ENC_FUSE", fuse)
+            stamps.zero_()
+            xd = x.clone().requires_grad_(True)
+            pd = [p[n].to(DEV).requires_grad_(True) for n in ops.ENC_PARAM_NAMES]
+            y = ops.encoder_layer(xd, mask, shp, 1, p_drop, 77, pd)
+            g = torch.autograd.grad(y, [xd] + pd, dy)
+            res[fuse] = (y.detach().cpu().numpy(), [t.cpu().numpy() for t in g])
+            torch.cuda.synchronize()
+            launched[fuse] = (bool(stamps[:4096].any()), bool(stamps[4096:].any()))
+    finally:
+        set_stamps(None)
+        torch.cuda.synchronize()
+    assert launched == {"0": (False, False), "1": (True, True)}, launched
     # same products, same dropout quads; the LayerNorm row sums are grouped differently (16-lane butterflies over three quads per
     # lane in the fused chains, one 64-lane tree in the row-block kernels): rounding-level differences only
     assert _rel(res["1"][0], res["0"][0]) < 2e-6, _rel(res["1"][0], res["0"][0])
