@@ -212,6 +212,15 @@ int rd_edge_attention_bwd(int32_t N, int32_t E, int32_t H, int32_t C, const floa
 int rd_edge_softmax_list_batched(int32_t B, int32_t N, int32_t E, const int64_t* edge_index, int64_t batch_stride,
                                  int64_t row_stride, int32_t norm_row, const float* edge_weights, int64_t w_bstride,
                                  float* gamma_e, float* ssum, void* stream);
+/* rd_edge_softmax_list_batched followed by F.dropout(gamma, p) (what layer 2 of the use_beta model computes forward when its operator
+ * was given dropout > 0, code/models_rd.py:331-336 -> code/Ob_propagation.py:196): gamma_e[b,e] is 0 or gamma / (1 - p), ssum the
+ * sum of THOSE.  Forward only -- no gradient w.r.t. the weights is formed anywhere, which is why the model refuses that setting in
+ * training mode: ssum no longer sums to 1 per target, so the weights' gradient is no longer 0.  The mask is
+ * rd_edge_softmax_list_dropout's rule per (sample b, list position e): element e & 3 of quad b * ceil(E / 4) + e / 4 of the edge-
+ * coefficient site under (seed + the registered seed cell).  p_drop = 0: rd_edge_softmax_list_batched. */
+int rd_edge_softmax_list_batched_dropout(int32_t B, int32_t N, int32_t E, const int64_t* edge_index, int64_t batch_stride,
+                                         int64_t row_stride, int32_t norm_row, const float* edge_weights, int64_t w_bstride,
+                                         float p_drop, uint64_t seed, float* gamma_e, float* ssum, void* stream);
 int rd_edge_gamma_dense(int32_t N, int32_t E, const int64_t* edge_index, int64_t row_stride, const float* gamma_e,
                         float* gamma_dense, void* stream);
 int rd_aggregate_batched_fwd(int32_t B, int32_t N, int32_t C, const float* gamma, const float* V, const float* skip,
@@ -476,6 +485,33 @@ int rd_graph_beta_bwd_alpha(int32_t B, int32_t N, int32_t K, int32_t T, int32_t 
                             int64_t row_stride, const float* edge_weights, int64_t w_bstride, const float* beta_save,
                             const int32_t* kept, const float* dout, const float* dalpha, float* dV, float* dH, float* dmap_part,
                             float* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* Coefficient dropout of the use_beta branch: F.dropout(gamma, p) after the softmax (code/Ob_propagation.py:195-196).  The reference
+ * repeats gamma to [E/2, T*d_ob] before the softmax and drops element-wise, so the d_ob = 4 channels of one (edge, step) share the
+ * softmax weight P and have four independent keep decisions:
+ *   out[b,s,4t+c] = sum over kept e with src(e) = s of  P[b,e,t] * keep[b,e,t,c] / (1 - p) * V[b,tgt(e),4t+c]
+ * THE MASK: one quad of the library's counter-based generator per (sample b, edge e, step t) at the edge-coefficient site, under
+ * (seed + the registered seed cell, read at enqueue), its four uniforms the four channels, keep iff u >= p:
+ *   quad = (b * E + e) * T + t,  e = the edge's id in the INPUT list (not its position among the kept ones)
+ * so both forms, both directions and every sample draw from one numbering (< 2^48 at every supported size).  Only the aggregation
+ * sees the mask: pruning, edge_index_out, alpha_out (the reference saves _alpha before the softmax), beta_save and kept do not
+ * depend on p.  The backward regenerates the mask from (p_drop, seed) -- pass the forward's; nothing more is stored --:
+ *   dV[b,g,4t+c] += P keep / (1 - p) dout[b,s,4t+c],  dP[b,e,t] = sum_c keep / (1 - p) dout[b,s,4t+c] V[b,g,4t+c],
+ * then the softmax backward and the rest as in rd_graph_beta_bwd; the dalpha path (NULL allowed) does not see the mask.  Fixed
+ * order of every sum, no atomics: two calls give the same bits.  p_drop = 0 runs rd_graph_beta_fwd / _bwd(_alpha) themselves.  Both
+ * forms; the rounds 2-5 kernels (env RD_BETA_V1=1) refuse p_drop > 0 with RD_EUNSUPPORTED.
+ * rd_graph_beta_keep writes that mask for EVERY edge of the input list: keep [B,E,T,4] bytes (1 = kept), through the same device
+ * function the kernels call. */
+int rd_graph_beta_fwd_dropout(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V, const float* H,
+                              const float* map_weights, const float* p_t, int64_t pt_bstride, const int64_t* edge_index,
+                              int64_t row_stride, const float* edge_weights, int64_t w_bstride, float p_drop, uint64_t seed,
+                              float* out, int64_t* edge_index_out, float* alpha_out, float* beta_save, int32_t* kept,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int rd_graph_beta_bwd_dropout(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V, const float* H,
+                              const float* map_weights, const float* p_t, int64_t pt_bstride, const int64_t* edge_index,
+                              int64_t row_stride, const float* edge_weights, int64_t w_bstride, float p_drop, uint64_t seed,
+                              const float* beta_save, const int32_t* kept, const float* dout, const float* dalpha, float* dV,
+                              float* dH, float* dmap_part, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+int rd_graph_beta_keep(int32_t B, int32_t T, int32_t E, float p_drop, uint64_t seed, uint8_t* keep, void* stream);
 /* code/models_rd.py:345-346: distance = mean(cdist(alpha_all.T, alpha_all.T, p=2)) for alpha_all [E,B] (one column of edge
  * scores per sample); workspace B floats.  Identically 0 on the shipped path (equal columns); evaluated here in general. */
 int rd_structure_distance(int32_t E, int32_t B, const float* alpha_all, float* workspace, float* distance, void* stream);
@@ -538,6 +574,25 @@ int rd_beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, con
                       const void* saved, size_t saved_bytes, const float* dz, int32_t lddz, const float* dist_grad, float* dR_u,
                       float* dW1, float* db1, float* dWinc, float* dbinc, float* dmap_weights, float* dW2, float* db2,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* The pair with coefficient dropout on layer 1's operator (Raindrop_v2(use_beta=True) whose ob_propagation.dropout was set; training
+ * mode): p_edge1 drops layer 1's post-softmax coefficients (rd_graph_beta_fwd_dropout under `seed` + the registered seed cell); the
+ * backward takes p_edge1 and the forward's seed and regenerates the mask.  p_edge1 = 0: rd_beta_stage_fwd / _bwd exactly.
+ * Layer 2's coefficient dropout is NOT built into the stage: with it the per-target coefficient sum no longer equals 1 and the
+ * edge scores get a gradient through it (d coef / d alpha), which no backward here forms; the model and the steps refuse
+ * ob_propagation_layer2.dropout > 0 in training mode. */
+int rd_beta_stage_fwd_dropout(const rd_shape* s, const float* src, const float* times, const int64_t* lengths, const float* timescales,
+                              const float* R_u, const float* W1, const float* b1, const float* Winc, const float* binc,
+                              const float* map_weights, const float* W2, const float* b2, const int64_t* edge_index, int64_t row_stride,
+                              const float* edge_weights, int32_t E, float p_drop, float p_edge1, uint64_t seed, float* z,
+                              uint8_t* mask, int64_t* edge_index_out, float* alpha_out, float* distance, void* saved,
+                              size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int rd_beta_stage_bwd_dropout(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
+                              const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
+                              const float* edge_weights, int32_t E, float p_drop, float p_edge1, uint64_t seed,
+                              const int64_t* edge_index_kept, const float* alpha, const void* saved, size_t saved_bytes,
+                              const float* dz, int32_t lddz, const float* dist_grad, float* dR_u, float* dW1, float* db1,
+                              float* dWinc, float* dbinc, float* dmap_weights, float* dW2, float* db2, void* workspace,
+                              size_t workspace_bytes, void* stream);
 /* The stage's two layout kernels on their own.  _fwd: z[row(t,b), f*4+c] = y2[b,f,t*4+c] * coef[b,f], coef = the per-target softmax
  * sum over sample b's kept edges (edge_index_kept [B][2,Kk], alpha [B,Kk]): bit-identical to rd_edge_softmax_list_batched(norm_row
  * = 1)'s ssum followed by rd_rows_to_tokens_fwd on the padded layout; with a token plan registered only the live rows are written,

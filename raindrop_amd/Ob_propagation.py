@@ -88,23 +88,18 @@ class Observation_progation(nn.Module):
         if isinstance(x, (tuple, list)):
             x = x[1]
         # code/Ob_propagation.py:196: F.dropout of the edge coefficients AFTER the softmax (the shipped model builds the operator with
-        # dropout = 0., models_rd.py:243-247).  Default branch: round 6 (the mask is a function of torch's seed and a per-module call
-        # counter, like the model's own dropout); the use_beta branch with coefficient dropout is not built.
+        # dropout = 0., models_rd.py:243-247).  Both branches: the mask is a function of torch's seed and a per-module call counter, like
+        # the model's own dropout (default branch: one decision per edge; use_beta: four per (edge, step), rd_graph_beta_fwd_dropout).
         p_edge = float(self.dropout) if self.training else 0.0
-        if p_edge > 0.0 and use_beta:
-            raise _lib.RaindropHipError("RD_EUNSUPPORTED: Observation_progation(dropout > 0) with use_beta=True in training mode is not built")
         if use_beta:
-            return self._forward_beta(x, p_t, edge_index, edge_weights, return_attention_weights)
+            return self._forward_beta(x, p_t, edge_index, edge_weights, return_attention_weights, p_edge)
         if edge_weights is None:
             raise ValueError("edge_weights is required (the reference raises UnboundLocalError at "
                              "code/Ob_propagation.py:193 without it)")
         if self.heads != 1:
             raise _lib.RaindropHipError("RD_EUNSUPPORTED: heads != 1")
         n = x.shape[0]
-        seed = 0
-        if p_edge > 0.0:
-            self._drop_calls = getattr(self, "_drop_calls", 0) + 1
-            seed = (torch.initial_seed() * 1000003 + 7919 * self._drop_calls + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF
+        seed = self._edge_seed(p_edge)
         _, ssum = ops.edge_softmax_list(edge_index, edge_weights, n, norm_row=1, p_drop=p_edge, seed=seed)
         v = ops.linear(x, self.lin_value.weight, self.lin_value.bias, act=1)
         out = v * ssum[:, None]
@@ -113,11 +108,21 @@ class Observation_progation(nn.Module):
             return out, (edge_index, edge_weights.unsqueeze(-1))
         return out
 
-    def _forward_beta(self, x, p_t, edge_index, edge_weights, return_attention_weights):
+    def _edge_seed(self, p_edge):
+        """Seed of this call's coefficient-dropout mask (0 and no counter bump where nothing is dropped): torch's seed and the
+        module's count of dropping calls, so equal `torch.manual_seed` and `_drop_calls` give equal masks and the next call a new one."""
+        if p_edge <= 0.0:
+            return 0
+        self._drop_calls = getattr(self, "_drop_calls", 0) + 1
+        return (torch.initial_seed() * 1000003 + 7919 * self._drop_calls + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF
+
+    def _forward_beta(self, x, p_t, edge_index, edge_weights, return_attention_weights, p_edge=0.0):
         """use_beta branch (code/Ob_propagation.py:161-185,190-191,195,200,207-208,227): per-time-step edge scores
         beta * w, pruning to the top half of the edges, per-channel softmax over the edges of a SOURCE node, aggregation
         of the TARGETS' values.  lin_value and increase_dim run once per node (rd_linear_fwd); the graph part is
-        rd_graph_beta_fwd.  Returns out [N,K] or (out, (edge_index' [2,E/2], alpha [E/2])) like the reference."""
+        rd_graph_beta_fwd.  Returns out [N,K] or (out, (edge_index' [2,E/2], alpha [E/2])) like the reference.
+        p_edge > 0 (training mode of an operator built with dropout > 0): F.dropout of the post-softmax coefficients (:195-196), the
+        mask of rd_graph_beta_fwd_dropout under this call's seed; the returned list and scores do not depend on it."""
         if edge_weights is None:
             raise ValueError("edge_weights is required on the use_beta branch")
         if self.heads != 1:
@@ -125,7 +130,7 @@ class Observation_progation(nn.Module):
         V = ops.linear(x, self.lin_value.weight, self.lin_value.bias, act=1)
         H = ops.linear(x, self.increase_dim.weight, self.increase_dim.bias, exact=True)     # feeds the top-K pruning: exact fp32 in every mode
         out, ei2, alpha = ops.graph_beta(V.unsqueeze(0), H.unsqueeze(0), self.map_weights, p_t.unsqueeze(0).float(), edge_index,
-                                         edge_weights.reshape(1, -1).float(), self.ob_dim)
+                                         edge_weights.reshape(1, -1).float(), self.ob_dim, p_drop=p_edge, seed=self._edge_seed(p_edge))
         out = out[0]
         out = out.view(-1, self.heads * self.out_channels) if self.concat else out
         if isinstance(return_attention_weights, bool):

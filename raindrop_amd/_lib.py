@@ -64,6 +64,8 @@ SIGNATURES = {
     "rd_aggregate_bwd": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
     "rd_edge_softmax_list_batched": (c_int32, [c_int32, c_int32, c_int32, _P, ctypes.c_int64, ctypes.c_int64, c_int32, _P,
                                                ctypes.c_int64, _P, _P, _P]),
+    "rd_edge_softmax_list_batched_dropout": (c_int32, [c_int32, c_int32, c_int32, _P, ctypes.c_int64, ctypes.c_int64, c_int32, _P,
+                                                       ctypes.c_int64, c_float, ctypes.c_uint64, _P, _P, _P]),
     "rd_edge_gamma_dense": (c_int32, [c_int32, c_int32, _P, ctypes.c_int64, _P, _P, _P]),
     "rd_aggregate_batched_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "rd_aggregate_batched_bwd": (c_int32, [c_int32, c_int32, c_int32, _P, _P, _P, _P]),
@@ -120,6 +122,11 @@ SIGNATURES = {
                           + [_P] * 7 + [_P, c_size_t, _P]),
     "rd_graph_beta_bwd_alpha": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64]
                                 + [_P] * 8 + [_P, c_size_t, _P]),
+    "rd_graph_beta_fwd_dropout": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64,
+                                                           c_float, ctypes.c_uint64] + [_P] * 5 + [_P, c_size_t, _P]),
+    "rd_graph_beta_bwd_dropout": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64,
+                                                           c_float, ctypes.c_uint64] + [_P] * 8 + [_P, c_size_t, _P]),
+    "rd_graph_beta_keep": (c_int32, [c_int32, c_int32, c_int32, c_float, ctypes.c_uint64, _P, _P]),
     "rd_structure_distance": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
     "rd_structure_distance_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "rd_structure_distance_bwd": (c_int32, [c_int32, c_int32, _P, _P, _P, c_size_t, _P, _P]),
@@ -129,6 +136,10 @@ SIGNATURES = {
                           + [_P, c_size_t, _P, c_size_t, _P]),
     "rd_beta_stage_bwd": (c_int32, [_SHP] + [_P] * 6 + [_P, ctypes.c_int64, _P, c_int32, c_float, _P, _P, _P, c_size_t, _P, c_int32, _P]
                           + [_P] * 8 + [_P, c_size_t, _P]),
+    "rd_beta_stage_fwd_dropout": (c_int32, [_SHP] + [_P] * 12 + [_P, ctypes.c_int64, _P, c_int32, c_float, c_float, ctypes.c_uint64]
+                                  + [_P] * 5 + [_P, c_size_t, _P, c_size_t, _P]),
+    "rd_beta_stage_bwd_dropout": (c_int32, [_SHP] + [_P] * 6 + [_P, ctypes.c_int64, _P, c_int32, c_float, c_float, ctypes.c_uint64, _P, _P, _P,
+                                                           c_size_t, _P, c_int32, _P] + [_P] * 8 + [_P, c_size_t, _P]),
     "rd_beta_l2_tokens_fwd": (c_int32, [_SHP, c_int32, _P, _P, _P, _P, c_int32, _P, _P]),
     "rd_beta_l2_tokens_bwd": (c_int32, [_SHP, c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "rd_prep_stats_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),

@@ -334,12 +334,13 @@ extern "C" int rd_beta_l2_tokens_bwd(const rd_shape* s, int32_t Kk, const int64_
   return launch_l2_tokens(s, Kk, edge_index_kept, alpha, y2, const_cast<float*>(dz), lddz, dY, nullptr, coef, (hipStream_t)stream);
 }
 
-extern "C" int rd_beta_stage_fwd(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
-                                 const float* timescales, const float* R_u, const float* W1, const float* b1, const float* Winc,
-                                 const float* binc, const float* map_weights, const float* W2, const float* b2,
-                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int32_t E, float p_drop,
-                                 uint64_t seed, float* z, uint8_t* mask, int64_t* edge_index_out, float* alpha_out, float* distance,
-                                 void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+static int beta_stage_fwd(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                          const float* timescales, const float* R_u, const float* W1, const float* b1, const float* Winc,
+                          const float* binc, const float* map_weights, const float* W2, const float* b2,
+                          const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int32_t E, float p_drop,
+                          float p_edge1, uint64_t seed, float* z, uint8_t* mask, int64_t* edge_index_out,
+                          float* alpha_out, float* distance, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
+                          void* stream) {
   int rc = check_stage_shape(s, E);
   if (rc) return rc;
   if (s->B == 0) return RD_OK;
@@ -347,6 +348,7 @@ extern "C" int rd_beta_stage_fwd(const rd_shape* s, const float* src, const floa
              edge_weights && z && mask && saved && workspace, "NULL tensor");
   RD_REQUIRE((edge_index_out && alpha_out) || rd_graph_beta_kept(E) == 0, "NULL tensor");
   RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
+  RD_REQUIRE(p_edge1 >= 0.f && p_edge1 < 1.f, "edge dropout probability must be in [0,1)");
   const StageSaved v = carve_saved(s, E, saved);
   const StageWs w = carve_ws(s, E, workspace);
   RD_REQUIRE(saved_bytes >= v.bytes, "saved buffer too small: %zu < %zu", saved_bytes, v.bytes);
@@ -359,8 +361,12 @@ extern "C" int rd_beta_stage_fwd(const rd_shape* s, const float* src, const floa
   if ((rc = rd_obs_embed_fwd(s, src, R_u, p_drop, seed, v.X, stream))) return rc;
   if ((rc = rd_linear_fwd(M, K, K, v.X, K, W1, b1, v.V, K, 1, stream))) return rc;
   if ((rc = rd_linear_fwd_fp32(M, 32 * T, K, v.X, K, Winc, binc, v.H, 32 * T, 0, stream))) return rc;
-  if ((rc = rd_graph_beta_fwd(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride, edge_weights, 0, v.y1,
-                              edge_index_out, alpha_out, v.beta, v.kept, w.gb, w.gb_bytes, stream))) return rc;
+  if (p_edge1 > 0.f) rc = rd_graph_beta_fwd_dropout(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride,
+                                                    edge_weights, 0, p_edge1, seed, v.y1, edge_index_out, alpha_out, v.beta, v.kept,
+                                                    w.gb, w.gb_bytes, stream);
+  else rc = rd_graph_beta_fwd(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride, edge_weights, 0, v.y1,
+                              edge_index_out, alpha_out, v.beta, v.kept, w.gb, w.gb_bytes, stream);
+  if (rc) return rc;
   if ((rc = rd_linear_fwd(M, K, K, v.y1, K, W2, b2, v.y2, K, 1, stream))) return rc;
   if ((rc = launch_l2_tokens(s, Kk, edge_index_out, alpha_out, v.y2, z, D, nullptr, v.coef, nullptr, st))) return rc;     // + the coefficient table for the backward
   if (distance) {
@@ -373,12 +379,35 @@ extern "C" int rd_beta_stage_fwd(const rd_shape* s, const float* src, const floa
   return RD_OK;
 }
 
-extern "C" int rd_beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
-                                 const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
-                                 const float* edge_weights, int32_t E, float p_drop, const int64_t* edge_index_kept, const float* alpha,
-                                 const void* saved, size_t saved_bytes, const float* dz, int32_t lddz, const float* dist_grad,
-                                 float* dR_u, float* dW1, float* db1, float* dWinc, float* dbinc, float* dmap_weights, float* dW2,
-                                 float* db2, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int rd_beta_stage_fwd(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                 const float* timescales, const float* R_u, const float* W1, const float* b1, const float* Winc,
+                                 const float* binc, const float* map_weights, const float* W2, const float* b2,
+                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int32_t E, float p_drop,
+                                 uint64_t seed, float* z, uint8_t* mask, int64_t* edge_index_out, float* alpha_out, float* distance,
+                                 void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+  return beta_stage_fwd(s, src, times, lengths, timescales, R_u, W1, b1, Winc, binc, map_weights, W2, b2, edge_index, row_stride,
+                        edge_weights, E, p_drop, 0.f, seed, z, mask, edge_index_out, alpha_out, distance, saved, saved_bytes,
+                        workspace, workspace_bytes, stream);
+}
+extern "C" int rd_beta_stage_fwd_dropout(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                         const float* timescales, const float* R_u, const float* W1, const float* b1,
+                                         const float* Winc, const float* binc, const float* map_weights, const float* W2,
+                                         const float* b2, const int64_t* edge_index, int64_t row_stride, const float* edge_weights,
+                                         int32_t E, float p_drop, float p_edge1, uint64_t seed, float* z, uint8_t* mask,
+                                         int64_t* edge_index_out, float* alpha_out, float* distance, void* saved, size_t saved_bytes,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return beta_stage_fwd(s, src, times, lengths, timescales, R_u, W1, b1, Winc, binc, map_weights, W2, b2, edge_index, row_stride,
+                        edge_weights, E, p_drop, p_edge1, seed, z, mask, edge_index_out, alpha_out, distance, saved,
+                        saved_bytes, workspace, workspace_bytes, stream);
+}
+
+static int beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
+                          const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
+                          const float* edge_weights, int32_t E, float p_drop, float p_edge1, uint64_t seed,
+                          const int64_t* edge_index_kept, const float* alpha,
+                          const void* saved, size_t saved_bytes, const float* dz, int32_t lddz, const float* dist_grad,
+                          float* dR_u, float* dW1, float* db1, float* dWinc, float* dbinc, float* dmap_weights, float* dW2,
+                          float* db2, void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_stage_shape(s, E);
   if (rc) return rc;
   RD_REQUIRE(dR_u && dW1 && db1 && dWinc && dbinc && dmap_weights && dW2 && db2, "NULL gradient output");
@@ -415,7 +444,10 @@ extern "C" int rd_beta_stage_bwd(const rd_shape* s, const float* src, const floa
     if ((rc = check_launch("k_beta_transpose"))) return rc;
     dalpha = w.dalpha;
   }
-  if (dalpha) rc = rd_graph_beta_bwd_alpha(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride, edge_weights, 0,
+  if (p_edge1 > 0.f) rc = rd_graph_beta_bwd_dropout(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride,
+                                                    edge_weights, 0, p_edge1, seed, v.beta, v.kept, w.b, dalpha, w.c, w.h, w.dmap_part,
+                                                    nullptr, w.gb, w.gb_bytes, stream);
+  else if (dalpha) rc = rd_graph_beta_bwd_alpha(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride, edge_weights, 0,
                                            v.beta, v.kept, w.b, dalpha, w.c, w.h, w.dmap_part, nullptr, w.gb, w.gb_bytes, stream);
   else rc = rd_graph_beta_bwd(B, F, K, T, 4, E, v.V, v.H, map_weights, v.p_t, 16L * T, edge_index, row_stride, edge_weights, 0, v.beta,
                               v.kept, w.b, w.c, w.h, w.dmap_part, nullptr, w.gb, w.gb_bytes, stream);
@@ -432,4 +464,28 @@ extern "C" int rd_beta_stage_bwd(const rd_shape* s, const float* src, const floa
   hipLaunchKernelGGL(k_beta_add, dim3(ew_blocks(n4)), dim3(256), 0, st, w.a, w.b, n4);
   if ((rc = check_launch("k_beta_add"))) return rc;
   return rd_obs_embed_bwd(s, src, v.X, w.a, p_drop, dR_u, w.obs, w.obs_bytes, stream);
+}
+
+extern "C" int rd_beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
+                                 const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
+                                 const float* edge_weights, int32_t E, float p_drop, const int64_t* edge_index_kept, const float* alpha,
+                                 const void* saved, size_t saved_bytes, const float* dz, int32_t lddz, const float* dist_grad,
+                                 float* dR_u, float* dW1, float* db1, float* dWinc, float* dbinc, float* dmap_weights, float* dW2,
+                                 float* db2, void* workspace, size_t workspace_bytes, void* stream) {
+  return beta_stage_bwd(s, src, R_u, W1, Winc, map_weights, W2, edge_index, row_stride, edge_weights, E, p_drop, 0.f, 0, edge_index_kept,
+                        alpha, saved, saved_bytes, dz, lddz, dist_grad, dR_u, dW1, db1, dWinc, dbinc, dmap_weights, dW2, db2, workspace,
+                        workspace_bytes, stream);
+}
+// the backward of rd_beta_stage_fwd_dropout: layer 1's mask is regenerated from (p_edge1, seed), the forward's
+extern "C" int rd_beta_stage_bwd_dropout(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,
+                                         const float* map_weights, const float* W2, const int64_t* edge_index, int64_t row_stride,
+                                         const float* edge_weights, int32_t E, float p_drop, float p_edge1, uint64_t seed,
+                                         const int64_t* edge_index_kept, const float* alpha, const void* saved, size_t saved_bytes,
+                                         const float* dz, int32_t lddz, const float* dist_grad, float* dR_u, float* dW1, float* db1,
+                                         float* dWinc, float* dbinc, float* dmap_weights, float* dW2, float* db2, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  RD_REQUIRE(p_edge1 >= 0.f && p_edge1 < 1.f, "edge dropout probability must be in [0,1)");
+  return beta_stage_bwd(s, src, R_u, W1, Winc, map_weights, W2, edge_index, row_stride, edge_weights, E, p_drop, p_edge1, seed,
+                        edge_index_kept, alpha, saved, saved_bytes, dz, lddz, dist_grad, dR_u, dW1, db1, dWinc, dbinc, dmap_weights, dW2,
+                        db2, workspace, workspace_bytes, stream);
 }

@@ -262,6 +262,23 @@ extern "C" int rd_edge_softmax_list_batched(int32_t B, int32_t N, int32_t E, con
   return check_launch("k_edge_softmax_list");
 }
 
+// the batched form with dropout of the coefficients after the softmax: sample b, list position e draws element e of the quads
+// b * ceil(E / 4) + e / 4 of SITE_EDGE_COEFF (B = 1: rd_edge_softmax_list_dropout's mask); ssum sums the dropped coefficients
+extern "C" int rd_edge_softmax_list_batched_dropout(int32_t B, int32_t N, int32_t E, const int64_t* edge_index, int64_t batch_stride,
+                                                    int64_t row_stride, int32_t norm_row, const float* edge_weights, int64_t w_bstride,
+                                                    float p_drop, uint64_t seed, float* gamma_e, float* ssum, void* stream) {
+  RD_REQUIRE(B >= 0 && N > 0 && E >= 0, "bad B=%d N=%d E=%d", B, N, E);
+  RD_REQUIRE(norm_row == 0 || norm_row == 1, "norm_row must be 0 (source) or 1 (target)");
+  RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
+  if (B == 0) return RD_OK;
+  RD_REQUIRE(B <= 65535, "B=%d exceeds the grid's y extent", B);
+  RD_REQUIRE(edge_index && edge_weights && gamma_e && ssum, "NULL tensor");
+  hipLaunchKernelGGL(k_edge_softmax_list, dim3(cdiv(N, 4), B), dim3(256), 0, (hipStream_t)stream,
+                     edge_index + (long)norm_row * row_stride, E, edge_weights, N, gamma_e, ssum, (long)batch_stride, (long)w_bstride,
+                     p_drop, seed, p_drop > 0.f ? seed_cell() : nullptr);
+  return check_launch("k_edge_softmax_list");
+}
+
 extern "C" int rd_edge_gamma_dense(int32_t N, int32_t E, const int64_t* edge_index, int64_t row_stride, const float* gamma_e,
                                    float* gamma_dense, void* stream) {
   RD_REQUIRE(N > 0 && N <= 4096 && E >= 0, "bad N=%d E=%d", N, E);

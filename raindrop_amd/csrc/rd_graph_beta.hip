@@ -322,23 +322,29 @@ struct Lds2 {
   float *V;                                  // forward: [N][K] staged values (or null)
   float *mx, *inv, *S, *db, *dmacc, *dwacc, *W, *DG;   // backward
 };
-size_t lds2_fwd(int N, int T, int K, int P2, int Kk, bool stage_v) {
+// drop (coefficient dropout): + the quad base of every kept edge (8 bytes), backward also a byte of keep decisions per (edge, step)
+size_t lds2_fwd(int N, int T, int K, int P2, int Kk, bool stage_v, bool drop = false) {
   auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
-  return r((size_t)N * T * 4) + r((size_t)P2 * 8) + 6 * r((size_t)Kk * 4) + r((size_t)(N + 1) * 4) + (stage_v ? r((size_t)N * K * 4) : 0);
+  return r((size_t)N * T * 4) + r((size_t)P2 * 8) + 6 * r((size_t)Kk * 4) + r((size_t)(N + 1) * 4) + (stage_v ? r((size_t)N * K * 4) : 0) +
+         (drop ? r((size_t)Kk * 8) : 0);
 }
-size_t lds2_bwd(int N, int Tc, int Kk, bool with_alpha = false) {
+size_t lds2_bwd(int N, int Tc, int Kk, bool with_alpha = false, bool drop = false) {
   auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
   return 5 * r((size_t)N * Tc * 4) + 7 * r((size_t)Kk * 4) + 2 * r((size_t)(N + 1) * 4) + r((size_t)N * 16 * 4) + r((size_t)Kk * 4) +
-         2 * r((size_t)Kk * Tc * 4) + (with_alpha ? r((size_t)Kk * 4) + 2 * r((size_t)N * 4) : 0);
+         2 * r((size_t)Kk * Tc * 4) + (with_alpha ? r((size_t)Kk * 4) + 2 * r((size_t)N * 4) : 0) +
+         (drop ? r((size_t)Kk * 8) + r((size_t)Kk * Tc) : 0);
 }
-int bwd2_chunk(int N, int T, int Kk, bool with_alpha = false) {   // steps per pass: the largest that fits, then evened out over the passes
+int bwd2_chunk(int N, int T, int Kk, bool with_alpha = false, bool drop = false) {   // steps per pass: the largest that fits, then evened out over the passes
   int tc = T;
-  while (tc > 1 && lds2_bwd(N, tc, Kk, with_alpha) > 160 * 1024) --tc;
+  while (tc > 1 && lds2_bwd(N, tc, Kk, with_alpha, drop) > 160 * 1024) --tc;
   const int np = (T + tc - 1) / tc;
   return (T + np - 1) / np;
 }
 
-template <bool STAGE_V>
+// DROP: coefficient dropout (rd_graph_beta.h) -- the softmax weight of an (edge, step) times 0 or 1 / (1 - p) per channel, in the
+// aggregation only: pruning, the returned lists and scores and beta_save do not see it.  The DROP = false instantiation is the
+// kernel as it was.
+template <bool STAGE_V, bool DROP>
 __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -351,6 +357,8 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2)
   int* slist = (int*)take((size_t)Kk * 4); int* soff = (int*)take((size_t)(N + 1) * 4);
   int* ltg = (int*)take((size_t)Kk * 4); float* lkw = (float*)take((size_t)Kk * 4);      // target / weight of the kept edges in SOURCE-LIST order
   float* Vs = STAGE_V ? (float*)take((size_t)N * K * 4) : nullptr;
+  uint64_t* lqb = DROP ? (uint64_t*)take((size_t)Kk * 8) : nullptr;                         // quad base of the kept edges, SOURCE-LIST order
+  const uint64_t seed_eff = DROP ? eff_seed(a.seed, a.cell) : 0;
   const float* H = a.H + (size_t)b * N * T * 32;
   const float* V = a.V + (size_t)b * N * K;
   const float* pt = a.p_t + (size_t)b * a.pt_bstride;
@@ -420,7 +428,10 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2)
   }
   __syncthreads();
   build_lists2(ksrc, Kk, N, soff, slist, tid);
-  for (int q = tid; q < Kk; q += GB2_THR) { const int e = slist[q]; ltg[q] = ktgt[e]; lkw[q] = kw[e]; }
+  for (int q = tid; q < Kk; q += GB2_THR) {
+    const int e = slist[q]; ltg[q] = ktgt[e]; lkw[q] = kw[e];
+    if (DROP) lqb[q] = beta_drop_base(b, E, (int)(keys[e] & 0xFFFFFFFFu), T);              // keys[e]: the input id of kept position e
+  }
   __syncthreads();
   // ---- (source n, step t): max, normaliser, then the d = 4 channels of the step ----
   // (consecutive threads = consecutive steps of one source: the list entries are broadcast reads, the scores consecutive floats)
@@ -439,7 +450,12 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2)
       const int tg = ltg[q];
       const float wi = expf(beta[tg * T + t] * lkw[q] - m) * iv;
       const float4 v = *reinterpret_cast<const float4*>(Vr + (size_t)tg * K + 4 * t);
-      acc.x += wi * v.x; acc.y += wi * v.y; acc.z += wi * v.z; acc.w += wi * v.w;
+      if (DROP) {
+        const float4 ks = beta_keep_scale(beta_keep_code(seed_eff, lqb[q] + (uint64_t)t, a.p_drop), a.inv_keep);
+        acc.x += (wi * ks.x) * v.x; acc.y += (wi * ks.y) * v.y; acc.z += (wi * ks.z) * v.z; acc.w += (wi * ks.w) * v.w;
+      } else {
+        acc.x += wi * v.x; acc.y += wi * v.y; acc.z += wi * v.z; acc.w += wi * v.w;
+      }
     }
     *reinterpret_cast<float4*>(out + (size_t)n * K + 4 * t) = acc;
   }
@@ -449,7 +465,11 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_fwd2(BetaArgs a, int P2)
 //   alpha[q] = (sum_t beta[tgt][t] * w) / T  ->  dbeta[n][t] += (sum over kept edges q into n of dalpha[q] * w[q]) / T (the same for
 //   every step: formed once from the target lists, before the chunks), d w[q] += dalpha[q] * (sum_t beta[tgt][t]) / T.
 // The ALPHA = false instantiation is the operator's own backward, unchanged.
-template <bool ALPHA>
+// DROP: the forward's coefficient dropout, regenerated (nothing stored by the forward): the four keep decisions of an (edge, step)
+// are drawn ONCE per chunk beside weight[e][t] as a 4-bit code (a byte plane KC [kept edges][chunk]);
+//   d weight[e][t] = sum_c keep_c / (1 - p) dout[src][4t + c] V[tgt][4t + c],  dV[tgt][4t + c] += weight keep_c / (1 - p) dout[src][4t + c];
+// the softmax backward and everything after it are as without dropout, and so is the alpha cotangent's path.
+template <bool ALPHA, bool DROP>
 __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
   const int tid = threadIdx.x, b = blockIdx.x;
@@ -467,6 +487,9 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
   float* dal = ALPHA ? (float*)take((size_t)Kk * 4) : nullptr;                               // dalpha of the kept edges
   float* cbt = ALPHA ? (float*)take((size_t)N * 4) : nullptr;                                // per-target dbeta term
   float* bsum = ALPHA ? (float*)take((size_t)N * 4) : nullptr;                               // sum_t beta[n][t], over the chunks
+  uint64_t* qb = DROP ? (uint64_t*)take((size_t)Kk * 8) : nullptr;                           // quad base of the kept edges, pruning order
+  unsigned char* KC = DROP ? (unsigned char*)take((size_t)Kk * Tc) : nullptr;                // keep codes [Kk][Tc]
+  const uint64_t seed_eff = DROP ? eff_seed(a.seed, a.cell) : 0;
   const float* H = a.H + (size_t)b * N * T * 32;
   const float* V = a.V + (size_t)b * N * K;
   const float* dout = a.dout + (size_t)b * N * K;
@@ -477,6 +500,7 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
     ksrc[q] = node_of(a.ei[e], N); ktgt[q] = node_of(a.ei[a.ei_stride + e], N); kw[q] = w[e];
     dwacc[q] = 0.f;
     if (ALPHA) dal[q] = a.dalpha[(size_t)b * Kk + q];
+    if (DROP) qb[q] = beta_drop_base(b, a.E, e, T);
   }
   for (int i = tid; i < N * 16; i += GB2_THR) dmacc[i] = 0.f;
   __syncthreads();
@@ -517,7 +541,13 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
       const float4 po = *reinterpret_cast<const float4*>(dout + (size_t)n * K + 4 * (t0 + tt));
       const float4 pv = *reinterpret_cast<const float4*>(V + (size_t)tg * K + 4 * (t0 + tt));
       float s = 0.f;
-      s += po.x * pv.x; s += po.y * pv.y; s += po.z * pv.z; s += po.w * pv.w;
+      if (DROP) {
+        const unsigned kc = beta_keep_code(seed_eff, qb[e] + (uint64_t)(t0 + tt), a.p_drop);
+        KC[e * Tc + tt] = (unsigned char)kc;
+        s = beta_dwgt_drop(po, pv, beta_keep_scale(kc, a.inv_keep));
+      } else {
+        s += po.x * pv.x; s += po.y * pv.y; s += po.z * pv.z; s += po.w * pv.w;
+      }
       W[e * Tc + tt] = wi; DG[e * Tc + tt] = s;
     }
     __syncthreads();
@@ -542,7 +572,12 @@ __global__ __launch_bounds__(GB2_THR) void k_graph_beta_bwd2(BetaArgs a, int Tc)
         const int e = tlist[q];
         const float wi = W[e * Tc + tt];
         const float4 po = *reinterpret_cast<const float4*>(dout + (size_t)ksrc[e] * K + 4 * t);
-        acc.x += wi * po.x; acc.y += wi * po.y; acc.z += wi * po.z; acc.w += wi * po.w;
+        if (DROP) {
+          const float4 ks = beta_keep_scale(KC[e * Tc + tt], a.inv_keep);
+          acc.x += (wi * ks.x) * po.x; acc.y += (wi * ks.y) * po.y; acc.z += (wi * ks.z) * po.z; acc.w += (wi * ks.w) * po.w;
+        } else {
+          acc.x += wi * po.x; acc.y += wi * po.y; acc.z += wi * po.z; acc.w += wi * po.w;
+        }
         s += kw[e] * DG[e * Tc + tt];
       }
       *reinterpret_cast<float4*>(dV + (size_t)n * K + 4 * t) = acc;
@@ -669,7 +704,26 @@ __global__ __launch_bounds__(256) void k_distance_bwd(const float* __restrict__ 
   }
 }
 
+// keep [B,E,T,4] bytes: the mask the operator's kernels draw (1 = kept), for every edge of the input list, through the same functions
+__global__ __launch_bounds__(256) void k_graph_beta_keep(int T, int E, long n, float p, uint64_t seed, const uint64_t* cell,
+                                                         uint8_t* __restrict__ keep) {
+  const uint64_t seed_eff = eff_seed(seed, cell);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {      // i = (b * E + e) * T + t
+    const long be = i / T;
+    const int t = (int)(i - be * T), b = (int)(be / E), e = (int)(be - (long)b * E);
+    const unsigned kc = beta_keep_code(seed_eff, beta_drop_base(b, E, e, T) + (uint64_t)t, p);
+    *reinterpret_cast<uchar4*>(keep + 4 * i) = make_uchar4(kc & 1u, (kc >> 1) & 1u, (kc >> 2) & 1u, (kc >> 3) & 1u);
+  }
+}
+
 int next_pow2(int x) { return beta_next_pow2(x); }
+
+// p_drop, seed of the _dropout entry points -> the argument block (p == 0: no dropout, the plain kernels)
+int set_dropout(BetaArgs& a, float p_drop, uint64_t seed) {
+  RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
+  if (p_drop > 0.f) { a.p_drop = p_drop; a.inv_keep = 1.0f / (1.0f - p_drop); a.seed = seed; a.cell = seed_cell(); }
+  return RD_OK;
+}
 
 int check_beta(int B, int N, int K, int T, int d, int E) {
   RD_REQUIRE(B >= 0 && N > 0 && K > 0 && T > 0 && d > 0 && E >= 0, "bad dims");
@@ -705,11 +759,11 @@ extern "C" size_t rd_graph_beta_workspace_bytes(int32_t B, int32_t N, int32_t K,
   return beta_large_ws_bytes(B, N, T, E);
 }
 
-extern "C" int rd_graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
-                                 const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
-                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
-                                 float* out, int64_t* edge_index_out, float* alpha_out, float* beta_save, int32_t* kept,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
+static int graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                          const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                          const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
+                          float p_drop, uint64_t seed, float* out, int64_t* edge_index_out, float* alpha_out, float* beta_save,
+                          int32_t* kept, void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_beta(B, N, K, T, d_ob, E);
   if (rc) return rc;
   if (B == 0) return RD_OK;
@@ -720,14 +774,27 @@ extern "C" int rd_graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int
   a.w = edge_weights; a.w_bstride = w_bstride; a.out = out; a.ei_out = edge_index_out; a.alpha_out = alpha_out;
   a.beta_save = beta_save; a.kept = kept;
   a.B = B; a.N = N; a.K = K; a.T = T; a.d = d_ob; a.E = E; a.Kk = rd_graph_beta_kept(E);
+  if ((rc = set_dropout(a, p_drop, seed))) return rc;
+  const bool drop = a.p_drop > 0.f;
   if (!fits_lds(N, T, E, false)) return beta_large_fwd(a, workspace, workspace_bytes, (hipStream_t)stream);
   const int P2 = next_pow2(E > 1 ? E : 2);
+  if (!beta_v1() && (K & 3) == 0 && drop) {                      // the same kernel, instantiated with the coefficient dropout
+    const int Kc = a.Kk > 0 ? a.Kk : 1;
+    const bool stage = lds2_fwd(N, T, K, P2, Kc, true, true) <= 160 * 1024;
+    const size_t lds2 = lds2_fwd(N, T, K, P2, Kc, stage, true);
+    RD_REQUIRE(lds2 <= 160 * 1024, "rd_graph_beta_fwd_dropout: %zu bytes of LDS", lds2);   // (cannot happen where fits_lds holds)
+    if (stage) { RD_LDS_ATTR((k_graph_beta_fwd2<true, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
+    else { RD_LDS_ATTR((k_graph_beta_fwd2<false, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
+    return check_launch("k_graph_beta_fwd2");
+  }
+  if (drop && !beta_v1()) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: K = %d is not a multiple of 4", K);   // (d_ob == 4: cannot happen)
+  if (drop) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: the rounds 2-5 kernels (RD_BETA_V1=1) have no coefficient dropout");
   if (!beta_v1() && (K & 3) == 0) {                              // round 6: 16 waves, every (edge, step) quantity once; the same bits
     const int Kc = a.Kk > 0 ? a.Kk : 1;
     const bool stage = lds2_fwd(N, T, K, P2, Kc, true) <= 160 * 1024;
     const size_t lds2 = lds2_fwd(N, T, K, P2, Kc, stage);
-    if (stage) { RD_LDS_ATTR(k_graph_beta_fwd2<true>, 160 * 1024); hipLaunchKernelGGL(k_graph_beta_fwd2<true>, dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
-    else { RD_LDS_ATTR(k_graph_beta_fwd2<false>, 160 * 1024); hipLaunchKernelGGL(k_graph_beta_fwd2<false>, dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
+    if (stage) { RD_LDS_ATTR((k_graph_beta_fwd2<true, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, false>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
+    else { RD_LDS_ATTR((k_graph_beta_fwd2<false, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, false>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
     return check_launch("k_graph_beta_fwd2");
   }
   const size_t lds = lds_bytes(N, T, P2, a.Kk > 0 ? a.Kk : 1, false);
@@ -736,11 +803,42 @@ extern "C" int rd_graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int
   return check_launch("k_graph_beta_fwd");
 }
 
+extern "C" int rd_graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                                 const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                                 const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int64_t w_bstride,
+                                 float* out, int64_t* edge_index_out, float* alpha_out, float* beta_save, int32_t* kept,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  return graph_beta_fwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride, 0.f, 0,
+                        out, edge_index_out, alpha_out, beta_save, kept, workspace, workspace_bytes, stream);
+}
+
+// the same with F.dropout of the post-softmax coefficients (rd_graph_beta.h: the mask's numbering); p_drop == 0: rd_graph_beta_fwd
+extern "C" int rd_graph_beta_fwd_dropout(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                                         const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                                         const int64_t* edge_index, int64_t row_stride, const float* edge_weights,
+                                         int64_t w_bstride, float p_drop, uint64_t seed, float* out, int64_t* edge_index_out,
+                                         float* alpha_out, float* beta_save, int32_t* kept, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return graph_beta_fwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride, p_drop,
+                        seed, out, edge_index_out, alpha_out, beta_save, kept, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rd_graph_beta_keep(int32_t B, int32_t T, int32_t E, float p_drop, uint64_t seed, uint8_t* keep, void* stream) {
+  RD_REQUIRE(B >= 0 && T > 0 && E >= 0, "bad dims B=%d T=%d E=%d", B, T, E);
+  RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
+  const long n = (long)B * E * T;
+  if (n == 0) return RD_OK;
+  RD_REQUIRE(keep, "NULL tensor");
+  const long blocks = (n + 255) / 256 < (1L << 20) ? (n + 255) / 256 : (1L << 20);       // grid-stride beyond
+  hipLaunchKernelGGL(k_graph_beta_keep, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, T, E, n, p_drop, seed, seed_cell(), keep);
+  return check_launch("k_graph_beta_keep");
+}
+
 static int graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V, const float* H,
                           const float* map_weights, const float* p_t, int64_t pt_bstride, const int64_t* edge_index,
                           int64_t row_stride, const float* edge_weights, int64_t w_bstride, const float* beta_save,
                           const int32_t* kept, const float* dout, const float* dalpha, float* dV, float* dH, float* dmap_part,
-                          float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+                          float* dw, void* workspace, size_t workspace_bytes, void* stream, float p_drop = 0.f, uint64_t seed = 0) {
   int rc = check_beta(B, N, K, T, d_ob, E);
   if (rc) return rc;
   if (B == 0) return RD_OK;
@@ -751,17 +849,35 @@ static int graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_
   a.w = edge_weights; a.w_bstride = w_bstride; a.beta_save = const_cast<float*>(beta_save); a.kept = const_cast<int32_t*>(kept);
   a.dout = dout; a.dV = dV; a.dH = dH; a.dmap_part = dmap_part; a.dw = dw; a.dalpha = dalpha;
   a.B = B; a.N = N; a.K = K; a.T = T; a.d = d_ob; a.E = E; a.Kk = rd_graph_beta_kept(E);
+  if ((rc = set_dropout(a, p_drop, seed))) return rc;
   if (!fits_lds(N, T, E, true)) return beta_large_bwd(a, workspace, workspace_bytes, (hipStream_t)stream);
   const int Kc = a.Kk > 0 ? a.Kk : 1;
   const bool al = dalpha != nullptr;
+  if (a.p_drop > 0.f) {
+    if (beta_v1()) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: the rounds 2-5 kernels (RD_BETA_V1=1) have no coefficient dropout");
+    if ((K & 3) != 0) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: K = %d is not a multiple of 4", K);   // (d_ob == 4: cannot happen)
+    // one step per pass always fits: N <= 64 and Kk <= 2048 bound the layout by ~125 KB with the keep-code plane and the alpha arrays
+    if (lds2_bwd(N, 1, Kc, al, true) > 160 * 1024)
+      return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: %zu bytes of LDS for one step per pass", lds2_bwd(N, 1, Kc, al, true));
+    const int Tc2 = bwd2_chunk(N, T, Kc, al, true);
+    const size_t lds2 = lds2_bwd(N, Tc2, Kc, al, true);
+    if (al) {
+      RD_LDS_ATTR((k_graph_beta_bwd2<true, true>), 160 * 1024);
+      hipLaunchKernelGGL((k_graph_beta_bwd2<true, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, Tc2);
+    } else {
+      RD_LDS_ATTR((k_graph_beta_bwd2<false, true>), 160 * 1024);
+      hipLaunchKernelGGL((k_graph_beta_bwd2<false, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, Tc2);
+    }
+    return check_launch("k_graph_beta_bwd2");
+  }
   if (!beta_v1() && (K & 3) == 0 && lds2_bwd(N, 1, Kc, al) <= 160 * 1024) {
     const int Tc2 = bwd2_chunk(N, T, Kc, al);
     if (al) {
-      RD_LDS_ATTR(k_graph_beta_bwd2<true>, 160 * 1024);
-      hipLaunchKernelGGL(k_graph_beta_bwd2<true>, dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc, true), (hipStream_t)stream, a, Tc2);
+      RD_LDS_ATTR((k_graph_beta_bwd2<true, false>), 160 * 1024);
+      hipLaunchKernelGGL((k_graph_beta_bwd2<true, false>), dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc, true), (hipStream_t)stream, a, Tc2);
     } else {
-      RD_LDS_ATTR(k_graph_beta_bwd2<false>, 160 * 1024);
-      hipLaunchKernelGGL(k_graph_beta_bwd2<false>, dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc), (hipStream_t)stream, a, Tc2);
+      RD_LDS_ATTR((k_graph_beta_bwd2<false, false>), 160 * 1024);
+      hipLaunchKernelGGL((k_graph_beta_bwd2<false, false>), dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc), (hipStream_t)stream, a, Tc2);
     }
     return check_launch("k_graph_beta_bwd2");
   }
@@ -790,6 +906,17 @@ extern "C" int rd_graph_beta_bwd_alpha(int32_t B, int32_t N, int32_t K, int32_t 
                                        void* stream) {
   return graph_beta_bwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride,
                         beta_save, kept, dout, dalpha, dV, dH, dmap_part, dw, workspace, workspace_bytes, stream);
+}
+
+// rd_graph_beta_bwd_alpha (dalpha may be NULL) under the forward's (p_drop, seed): the mask is regenerated
+extern "C" int rd_graph_beta_bwd_dropout(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_ob, int32_t E, const float* V,
+                                         const float* H, const float* map_weights, const float* p_t, int64_t pt_bstride,
+                                         const int64_t* edge_index, int64_t row_stride, const float* edge_weights,
+                                         int64_t w_bstride, float p_drop, uint64_t seed, const float* beta_save, const int32_t* kept,
+                                         const float* dout, const float* dalpha, float* dV, float* dH, float* dmap_part, float* dw,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return graph_beta_bwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride,
+                        beta_save, kept, dout, dalpha, dV, dH, dmap_part, dw, workspace, workspace_bytes, stream, p_drop, seed);
 }
 
 extern "C" int rd_structure_distance(int32_t E, int32_t B, const float* alpha_all, float* workspace, float* distance,

@@ -228,7 +228,16 @@ __device__ __forceinline__ View view_of(const LArgs& g, int b) {
   return v;
 }
 
+// the keep scales (0 or 1 / (1 - p) per channel) of kept position e at step t of sample b: the mask of rd_graph_beta.h, regenerated
+// at the point of use (the input id of the kept edge comes from a.kept)
+__device__ __forceinline__ float4 keep_scale_of(const BetaArgs& a, uint64_t seed_eff, int b, int e, int t) {
+  const int eid = a.kept[(size_t)b * a.Kk + e];
+  return beta_keep_scale(beta_keep_code(seed_eff, beta_drop_base(b, a.E, eid, a.T) + (uint64_t)t, a.p_drop), a.inv_keep);
+}
+
 // ---- out[n][t*4 + c] = sum over n's kept out-edges of softmax weight[e][t] * V[tgt(e)][t*4 + c]  (d_ob == 4) --------------------
+// DROP (here and below): the coefficient dropout; the DROP = false instantiations are the kernels as they were
+template <bool DROP>
 __global__ __launch_bounds__(BL_THR) void k_bl_out(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K;
@@ -239,12 +248,18 @@ __global__ __launch_bounds__(BL_THR) void k_bl_out(LArgs g) {
   const float* V = a.V + (size_t)b * N * K;
   const int* soff = wsp<int>(g, b, g.L.soff); const int* slist = wsp<int>(g, b, g.L.slist);
   const float m = v.mx[i], iv = v.inv[i];
+  const uint64_t seed_eff = DROP ? eff_seed(a.seed, a.cell) : 0;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   for (int q = soff[n]; q < soff[n + 1]; ++q) {
     const int e = slist[q], tg = v.ktgt[e];
     const float wg = expf(v.beta[(size_t)tg * T + t] * v.kw[e] - m) * iv;
     const float4 x = *reinterpret_cast<const float4*>(V + (size_t)tg * K + 4 * t);
-    acc[0] += wg * x.x; acc[1] += wg * x.y; acc[2] += wg * x.z; acc[3] += wg * x.w;
+    if (DROP) {
+      const float4 ks = keep_scale_of(a, seed_eff, b, e, t);
+      acc[0] += (wg * ks.x) * x.x; acc[1] += (wg * ks.y) * x.y; acc[2] += (wg * ks.z) * x.z; acc[3] += (wg * ks.w) * x.w;
+    } else {
+      acc[0] += wg * x.x; acc[1] += wg * x.y; acc[2] += wg * x.z; acc[3] += wg * x.w;
+    }
   }
   *reinterpret_cast<float4*>(a.out + (size_t)b * N * K + (size_t)n * K + 4 * t) = make_float4(acc[0], acc[1], acc[2], acc[3]);
 }
@@ -258,7 +273,14 @@ __device__ __forceinline__ float dwgt_of(const float* dout, const float* V, int 
   s += o.x * x.x; s += o.y * x.y; s += o.z * x.z; s += o.w * x.w;
   return s;
 }
+// the same under the mask: sum_c keep_c / (1 - p) dout[src][4t + c] * V[tgt][4t + c]
+__device__ __forceinline__ float dwgt_drop_of(const float* dout, const float* V, int K, int sr, int tg, int t, const float4 ks) {
+  const float4 o = *reinterpret_cast<const float4*>(dout + (size_t)sr * K + 4 * t);
+  const float4 x = *reinterpret_cast<const float4*>(V + (size_t)tg * K + 4 * t);
+  return beta_dwgt_drop(o, x, ks);
+}
 // S[n][t] = sum over n's out-edges of weight * dweight
+template <bool DROP>
 __global__ __launch_bounds__(BL_THR) void k_bl_S(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K;
@@ -268,14 +290,20 @@ __global__ __launch_bounds__(BL_THR) void k_bl_S(LArgs g) {
   const View v = view_of(g, b);
   const float* V = a.V + (size_t)b * N * K; const float* dout = a.dout + (size_t)b * N * K;
   const int* soff = wsp<int>(g, b, g.L.soff); const int* slist = wsp<int>(g, b, g.L.slist);
+  const uint64_t seed_eff = DROP ? eff_seed(a.seed, a.cell) : 0;
   float s = 0.f;
-  for (int q = soff[n]; q < soff[n + 1]; ++q) { const int e = slist[q]; s += v.weight(e, t) * dwgt_of(dout, V, K, n, v.ktgt[e], t); }
+  for (int q = soff[n]; q < soff[n + 1]; ++q) {
+    const int e = slist[q];
+    if (DROP) s += v.weight(e, t) * dwgt_drop_of(dout, V, K, n, v.ktgt[e], t, keep_scale_of(a, seed_eff, b, e, t));
+    else s += v.weight(e, t) * dwgt_of(dout, V, K, n, v.ktgt[e], t);
+  }
   wsp<float>(g, b, g.L.S)[i] = s;
 }
 // dV[i][4t + c] = sum over kept edges INTO i of weight[e][t] * dout[src(e)][4t + c];
 // dbeta[i][t] = sum over kept edges into i of w[e] * weight * (dweight - S[src]);  dH[i][t][c] = dbeta / 32 * cat(map_w[i], p_t[t])[c]
 // With an alpha cotangent (alpha[e] = sum_t beta[tgt][t] w[e] / T): dbeta[i][t] += (sum over kept edges into i of dalpha[e] w[e]) / T,
 // the same for every step (each thread forms it over the list it walks anyway: the LDS form's order)
+template <bool DROP>
 __global__ __launch_bounds__(BL_THR) void k_bl_dv_dbeta(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K;
@@ -286,14 +314,21 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dv_dbeta(LArgs g) {
   const float* V = a.V + (size_t)b * N * K; const float* dout = a.dout + (size_t)b * N * K;
   const int* toff = wsp<int>(g, b, g.L.toff); const int* tlist = wsp<int>(g, b, g.L.tlist);
   const float* S = wsp<float>(g, b, g.L.S);
+  const uint64_t seed_eff = DROP ? eff_seed(a.seed, a.cell) : 0;
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   float s = 0.f;
   for (int q = toff[n]; q < toff[n + 1]; ++q) {
     const int e = tlist[q], sr = v.ksrc[e];
     const float wg = v.weight(e, t);
     const float4 o = *reinterpret_cast<const float4*>(dout + (size_t)sr * K + 4 * t);
-    acc[0] += wg * o.x; acc[1] += wg * o.y; acc[2] += wg * o.z; acc[3] += wg * o.w;
-    s += v.kw[e] * (wg * (dwgt_of(dout, V, K, sr, n, t) - S[(size_t)sr * T + t]));
+    if (DROP) {
+      const float4 ks = keep_scale_of(a, seed_eff, b, e, t);
+      acc[0] += (wg * ks.x) * o.x; acc[1] += (wg * ks.y) * o.y; acc[2] += (wg * ks.z) * o.z; acc[3] += (wg * ks.w) * o.w;
+      s += v.kw[e] * (wg * (dwgt_drop_of(dout, V, K, sr, n, t, ks) - S[(size_t)sr * T + t]));
+    } else {
+      acc[0] += wg * o.x; acc[1] += wg * o.y; acc[2] += wg * o.z; acc[3] += wg * o.w;
+      s += v.kw[e] * (wg * (dwgt_of(dout, V, K, sr, n, t) - S[(size_t)sr * T + t]));
+    }
   }
   *reinterpret_cast<float4*>(a.dV + (size_t)b * N * K + (size_t)n * K + 4 * t) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   if (a.dalpha) {
@@ -330,6 +365,7 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dw_zero(LArgs g) {
 }
 // d loss / d w[e] = sum_t weight (dweight - S[src]) beta[tgt][t] for kept edges (0 for pruned ones: k_bl_dw_zero),
 // + dalpha[e] * (sum_t beta[tgt][t]) / T with an alpha cotangent
+template <bool DROP>
 __global__ __launch_bounds__(BL_THR) void k_bl_dw(LArgs g) {
   const BetaArgs& a = g.a;
   const int b = blockIdx.y, N = a.N, T = a.T, K = a.K, Kk = a.Kk;
@@ -340,7 +376,16 @@ __global__ __launch_bounds__(BL_THR) void k_bl_dw(LArgs g) {
   const float* S = wsp<float>(g, b, g.L.S);
   const int sr = v.ksrc[q], tg = v.ktgt[q];
   float s = 0.f;
-  for (int t = 0; t < T; ++t) s += v.weight(q, t) * (dwgt_of(dout, V, K, sr, tg, t) - S[(size_t)sr * T + t]) * v.beta[(size_t)tg * T + t];
+  if (DROP) {
+    const uint64_t seed_eff = eff_seed(a.seed, a.cell);
+    const uint64_t qb = beta_drop_base(b, a.E, a.kept[(size_t)b * Kk + q], T);
+    for (int t = 0; t < T; ++t) {
+      const float4 ks = beta_keep_scale(beta_keep_code(seed_eff, qb + (uint64_t)t, a.p_drop), a.inv_keep);
+      s += v.weight(q, t) * (dwgt_drop_of(dout, V, K, sr, tg, t, ks) - S[(size_t)sr * T + t]) * v.beta[(size_t)tg * T + t];
+    }
+  } else {
+    for (int t = 0; t < T; ++t) s += v.weight(q, t) * (dwgt_of(dout, V, K, sr, tg, t) - S[(size_t)sr * T + t]) * v.beta[(size_t)tg * T + t];
+  }
   if (a.dalpha) {
     float bs = 0.f;
     for (int t = 0; t < T; ++t) bs += v.beta[(size_t)tg * T + t];
@@ -393,7 +438,8 @@ int beta_large_fwd(const BetaArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
   hipLaunchKernelGGL(k_bl_lists, dim3(a.B), dim3(BL_LTHR), 0, st, g, 0);
   if ((rc = check_launch("k_bl_lists"))) return rc;
   BL_LAUNCH(k_bl_stats, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
-  BL_LAUNCH(k_bl_out, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+  if (a.p_drop > 0.f) BL_LAUNCH(k_bl_out<true>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+  else BL_LAUNCH(k_bl_out<false>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
   return RD_OK;
 }
 
@@ -409,12 +455,19 @@ int beta_large_bwd(const BetaArgs& a, void* ws, size_t ws_bytes, hipStream_t st)
   hipLaunchKernelGGL(k_bl_lists, dim3(a.B), dim3(BL_LTHR), 0, st, g, 1);
   if ((rc = check_launch("k_bl_lists"))) return rc;
   BL_LAUNCH(k_bl_stats, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
-  BL_LAUNCH(k_bl_S, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
-  BL_LAUNCH(k_bl_dv_dbeta, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+  const bool drop = a.p_drop > 0.f;
+  if (drop) {
+    BL_LAUNCH(k_bl_S<true>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+    BL_LAUNCH(k_bl_dv_dbeta<true>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+  } else {
+    BL_LAUNCH(k_bl_S<false>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+    BL_LAUNCH(k_bl_dv_dbeta<false>, (nt + BL_THR - 1) / BL_THR, BL_THR, g);
+  }
   BL_LAUNCH(k_bl_dmap, cdiv(a.N * 16, BL_THR), BL_THR, g);
   if (a.dw) {
     if (a.E > 0) BL_LAUNCH(k_bl_dw_zero, cdiv(a.E, BL_THR), BL_THR, g);
-    if (a.Kk > 0) BL_LAUNCH(k_bl_dw, cdiv(a.Kk, BL_THR), BL_THR, g);
+    if (a.Kk > 0 && drop) BL_LAUNCH(k_bl_dw<true>, cdiv(a.Kk, BL_THR), BL_THR, g);
+    else if (a.Kk > 0) BL_LAUNCH(k_bl_dw<false>, cdiv(a.Kk, BL_THR), BL_THR, g);
   }
   return RD_OK;
 }

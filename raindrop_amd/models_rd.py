@@ -174,6 +174,18 @@ class Raindrop(nn.Module):
         return output, distance, None
 
 
+def edge_dropout_of(model):
+    """Layer 1's coefficient-dropout probability of a use_beta model: `ob_propagation.dropout` in training mode, 0 in evaluation
+    mode.  Layer 2's (`ob_propagation_layer2.dropout > 0`, training mode) is refused: its dropped coefficients no longer sum to 1
+    per target, so the edge scores get a gradient through them that no backward of this project forms."""
+    if not model.training:
+        return 0.0
+    if float(model.ob_propagation_layer2.dropout) > 0.0:
+        raise _lib.RaindropHipError("RD_EUNSUPPORTED: ob_propagation_layer2.dropout > 0 with use_beta=True in training mode is not "
+                                    "built (the gradient of layer 2's dropped coefficient sum w.r.t. the edge scores)")
+    return float(model.ob_propagation.dropout)
+
+
 class Raindrop_v2(nn.Module):
     """code/models_rd.py:194-387.  Transformer-over-time on top of per-sample sensor-graph message
     passing; see the module docstring for the boundary contract."""
@@ -283,6 +295,12 @@ class Raindrop_v2(nn.Module):
             self._graph_cache = (key, dict(adj=adj, edge_index=ei, edge_weights=ew, gamma=gamma, ssum=ssum))
         return self._graph_cache[1]
 
+    def forward_seed(self, calls):
+        """The dropout seed of the forward that is this model's `calls`-th (`_drop_calls` after it): every mask of that forward --
+        observation embedding, encoder, the use_beta operators' coefficients -- is a function of it.  A captured step whose
+        seed + seed cell equals it draws the same masks."""
+        return (torch.initial_seed() * 1000003 + int(calls) + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF
+
     def _sensor_stage_beta(self, src, times, lengths, shp, p_drop, seed, g):
         """code/models_rd.py:313-346 with `use_beta = True`, batched over the samples (the reference loops):
         X = dropout(relu(src * R_u)) as [B,F,K]; layer 1 = the use_beta operator with p_t = the sample's positional
@@ -291,7 +309,12 @@ class Raindrop_v2(nn.Module):
         target keeps an edge, 0 where pruning removed them all); then the [F,T*d] -> [T,F*d] layout and the PE columns.
         `distance` = mean pairwise distance of the samples' returned scores (:345-346) when `compute_distance`, differentiable
         through those scores (ops.graph_beta(alpha_grad=True) -> ops.structure_distance).  Layer 2's edge weights stay constants:
-        the per-target softmax over them sums to 1 (or is absent), so their true gradient is 0."""
+        the per-target softmax over them sums to 1 (or is absent), so their true gradient is 0.
+        Coefficient dropout (training mode only): `self.ob_propagation.dropout` drops layer 1's post-softmax coefficients (four keep
+        decisions per (sample, edge, step): rd_graph_beta_fwd_dropout) under the forward's one `seed`; upstream users set the
+        attribute, the constructor has no keyword for it.  `self.ob_propagation_layer2.dropout > 0` is refused in training mode
+        (edge_dropout_of): with it layer 2's coefficient sum is no longer 1, its edge weights get a true gradient through
+        d ssum / d alpha, and the constant treatment above would silently drop that term."""
         dev = src.device
         B, T, F_, d = shp.B, shp.T, shp.F, shp.d_ob
         K, D = T * d, F_ * d + self.d_pe
@@ -302,12 +325,13 @@ class Raindrop_v2(nn.Module):
         _lib.call("rd_pe_mask", ctypes.byref(shp), ops._ptr(times), ops._ptr(lengths), ops._ptr(ts), ops._ptr(z), ops._ptr(mask),
                   ops._stream())
         l1, l2 = self.ob_propagation, self.ob_propagation_layer2
+        pe1 = edge_dropout_of(self)
         X = ops.obs_embed(src, self.R_u, shp, p_drop, seed).view(B * F_, K)
         V = ops.linear(X, l1.lin_value.weight, l1.lin_value.bias, act=1).view(B, F_, K)
         H = ops.linear(X, l1.increase_dim.weight, l1.increase_dim.bias, exact=True).view(B, F_, T * 32)   # edge scores -> top-K: exact fp32
         p_t = z[:, :, F_ * d:].permute(1, 0, 2).contiguous()                       # [B,T,16]: layout only
         y1, ei2, alpha1 = ops.graph_beta(V, H, l1.map_weights, p_t, g["edge_index"], g["edge_weights"].view(1, -1), d,
-                                         alpha_grad=self.compute_distance)
+                                         alpha_grad=self.compute_distance, p_drop=pe1, seed=seed)
         _, ssum2 = ops.edge_softmax_list_batched(ei2, alpha1, F_, norm_row=1)
         y2 = ops.linear(y1.reshape(B * F_, K), l2.lin_value.weight, l2.lin_value.bias, act=1).view(B, F_, K)
         z = ops.rows_to_tokens(y2, ssum2, z, shp)
@@ -339,7 +363,7 @@ class Raindrop_v2(nn.Module):
                 return out, torch.zeros((), dtype=torch.float32, device=dev), None
         p_drop = float(self.dropout.p) if self.training else 0.0
         self._drop_calls += 1
-        seed = (torch.initial_seed() * 1000003 + self._drop_calls + ops.rank_seed_offset()) & 0x7FFFFFFFFFFFFFFF
+        seed = self.forward_seed(self._drop_calls)
         lengths = lengths.to(device=dev, dtype=torch.int64)
         if self.use_beta:
             z, mask, distance = self._sensor_stage_beta(src.float(), times.float(), lengths, shp, p_drop, seed, g)

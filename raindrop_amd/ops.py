@@ -306,8 +306,10 @@ def edge_attention(q, k, v, edge_feat, edge_index, heads, channels, p_drop=0.0, 
                                 float(p_drop), int(seed))
 
 
-def edge_softmax_list_batched(edge_index, edge_weights, n_nodes, norm_row=1):
-    """B edge lists in one launch: edge_index int64 [B,2,E] (or [2,E] shared), edge_weights [B,E] -> (gamma_e [B,E], ssum [B,N])."""
+def edge_softmax_list_batched(edge_index, edge_weights, n_nodes, norm_row=1, p_drop=0.0, seed=0):
+    """B edge lists in one launch: edge_index int64 [B,2,E] (or [2,E] shared), edge_weights [B,E] -> (gamma_e [B,E], ssum [B,N]).
+    p_drop > 0: F.dropout of the coefficients after the softmax per (sample, list position) (rd_edge_softmax_list_batched_dropout);
+    ssum is then the sum of the dropped-and-rescaled coefficients.  Forward only: the results are constants to autograd."""
     ei = edge_index.contiguous()
     w = edge_weights.contiguous()
     _check(ei, dtype=torch.int64)
@@ -318,8 +320,12 @@ def edge_softmax_list_batched(edge_index, edge_weights, n_nodes, norm_row=1):
         raise ValueError("edge_softmax_list_batched: edge_index must be [B,2,E] or [2,E], got %s" % (tuple(ei.shape),))
     gamma = torch.empty((B, E), dtype=torch.float32, device=w.device)
     ssum = torch.empty((B, n_nodes), dtype=torch.float32, device=w.device)
-    _lib.call("rd_edge_softmax_list_batched", B, int(n_nodes), E, _ptr(ei), 0 if shared else 2 * E, E, int(norm_row), _ptr(w), E,
-              _ptr(gamma), _ptr(ssum), _stream())
+    if p_drop > 0.0:
+        _lib.call("rd_edge_softmax_list_batched_dropout", B, int(n_nodes), E, _ptr(ei), 0 if shared else 2 * E, E, int(norm_row), _ptr(w), E,
+                  float(p_drop), int(seed) & 0x7FFFFFFFFFFFFFFF, _ptr(gamma), _ptr(ssum), _stream())
+    else:
+        _lib.call("rd_edge_softmax_list_batched", B, int(n_nodes), E, _ptr(ei), 0 if shared else 2 * E, E, int(norm_row), _ptr(w), E,
+                  _ptr(gamma), _ptr(ssum), _stream())
     return gamma, ssum
 
 
@@ -444,10 +450,12 @@ class _GraphBeta(torch.autograd.Function):
     """The use_beta graph operator (rd_graph_beta_fwd / _bwd), batched: V [B,N,K], H [B,N,T*32], map_w [N,16],
     p_t [B or 1, T, 16], edge_index int64 [2,E], edge_weights [B or 1, E] -> out [B,N,K], edge_index' [B,2,Kk], alpha [B,Kk].
     alpha_grad: alpha is differentiable (rd_graph_beta_bwd_alpha); gradients are then not materialised, so an unused alpha
-    arrives as None (the kernel gets NULL) and so does an unused out (a loss of the structure distance alone)."""
+    arrives as None (the kernel gets NULL) and so does an unused out (a loss of the structure distance alone).
+    p_drop > 0: coefficient dropout (rd_graph_beta_fwd_dropout / _bwd_dropout); the backward regenerates the forward's mask from
+    the same (p_drop, seed)."""
 
     @staticmethod
-    def forward(ctx, V, H, map_w, p_t, edge_index, edge_weights, d_ob, alpha_grad=False):
+    def forward(ctx, V, H, map_w, p_t, edge_index, edge_weights, d_ob, alpha_grad=False, p_drop=0.0, seed=0):
         _check(V, H, map_w, p_t, edge_weights)
         _check(edge_index, dtype=torch.int64)
         B, N, K = V.shape
@@ -464,9 +472,14 @@ class _GraphBeta(torch.autograd.Function):
         pts = 0 if p_t.shape[0] == 1 else T * 16
         ws = 0 if edge_weights.shape[0] == 1 else E
         scratch = _workspace(lib.rd_graph_beta_workspace_bytes(B, N, K, T, E), dev)     # 0 bytes where the graph fits LDS
-        _lib.call("rd_graph_beta_fwd", B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index),
-                  edge_index.stride(0), _ptr(edge_weights), ws, _ptr(out), _ptr(ei_out), _ptr(alpha), _ptr(beta), _ptr(kept),
-                  _ptr(scratch), scratch.numel(), _stream())
+        head = (B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index), edge_index.stride(0),
+                _ptr(edge_weights), ws)
+        tail = (_ptr(out), _ptr(ei_out), _ptr(alpha), _ptr(beta), _ptr(kept), _ptr(scratch), scratch.numel(), _stream())
+        ctx.drop = (float(p_drop), int(seed) & 0x7FFFFFFFFFFFFFFF)
+        if ctx.drop[0] > 0.0:
+            _lib.call("rd_graph_beta_fwd_dropout", *head, *ctx.drop, *tail)
+        else:
+            _lib.call("rd_graph_beta_fwd", *head, *tail)
         ctx.save_for_backward(V, H, map_w, p_t, edge_index, edge_weights, beta, kept)
         ctx.dims = (B, N, K, T, d_ob, E, pts, ws)
         ctx.alpha_grad = bool(alpha_grad)
@@ -488,10 +501,18 @@ class _GraphBeta(torch.autograd.Function):
         want_dw = ctx.needs_input_grad[5]
         dw = torch.empty((B, E), dtype=torch.float32, device=V.device) if want_dw else None
         scratch = _workspace(_lib.load().rd_graph_beta_workspace_bytes(B, N, K, T, E), V.device)
-        args = (B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index), edge_index.stride(0),
-                _ptr(edge_weights), ws, _ptr(beta), _ptr(kept), _ptr(dout))
+        head = (B, N, K, T, d_ob, E, _ptr(V), _ptr(H), _ptr(map_w), _ptr(p_t), pts, _ptr(edge_index), edge_index.stride(0),
+                _ptr(edge_weights), ws)
+        args = head + (_ptr(beta), _ptr(kept), _ptr(dout))
         tail = (_ptr(dV), _ptr(dH), _ptr(dmap_part), _ptr(dw), _ptr(scratch), scratch.numel(), _stream())
-        if dalpha is None or not ctx.alpha_grad:                                 # (a non-differentiable alpha gets zeros here)
+        if ctx.drop[0] > 0.0:                                                    # the forward's mask, regenerated
+            if dalpha is not None and ctx.alpha_grad:
+                dalpha = dalpha.contiguous()
+                _check(dalpha)
+            else:
+                dalpha = None
+            _lib.call("rd_graph_beta_bwd_dropout", *head, *ctx.drop, _ptr(beta), _ptr(kept), _ptr(dout), _ptr(dalpha), *tail)
+        elif dalpha is None or not ctx.alpha_grad:                               # (a non-differentiable alpha gets zeros here)
             _lib.call("rd_graph_beta_bwd", *args, *tail)
         else:
             dalpha = dalpha.contiguous()
@@ -500,7 +521,7 @@ class _GraphBeta(torch.autograd.Function):
         dmap = dmap_part[0] if B == 1 else _colsum_rows(dmap_part.view(B, N * 16)).view(N, 16)
         if want_dw and edge_weights.shape[0] == 1 and B > 1:
             dw = _colsum_rows(dw).view(1, E)
-        return None if only_alpha else dV, dH, dmap, None, None, dw, None, None
+        return None if only_alpha else dV, dH, dmap, None, None, dw, None, None, None, None
 
 
 def _colsum_rows(x):
@@ -539,13 +560,24 @@ def _validate_edges(edge_index, N, who):
     _EDGES_CHECKED.add(key)
 
 
-def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4, alpha_grad=False):
+def graph_beta_keep(B, T, E, p_drop, seed, device):
+    """The coefficient-dropout mask of `graph_beta(p_drop, seed)` (rd_graph_beta_keep): uint8 [B,E,T,4], 1 = kept, for every edge of
+    the input list -- one generator quad per (sample, input edge id, step): quad = (b*E + e)*T + t, its four uniforms the channels."""
+    keep = torch.empty((B, E, T, 4), dtype=torch.uint8, device=device)
+    _lib.call("rd_graph_beta_keep", int(B), int(T), int(E), float(p_drop), int(seed) & 0x7FFFFFFFFFFFFFFF, _ptr(keep), _stream())
+    return keep
+
+
+def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4, alpha_grad=False, p_drop=0.0, seed=0):
     """use_beta branch of Observation_progation.message, batched (include/raindrop_hip.h: rd_graph_beta_fwd).  V [B,N,K],
     H [B,N,T*32], map_w [N,16], p_t [B or 1, T, 16], edge_index int64 [2,E], edge_weights [B or 1, E].  Shapes and edge
     endpoints are validated here (one device read for the endpoint range: the reference's index_select syncs and raises
     IndexError at the same point).  Returns (out [B,N,K], edge_index' [B,2,Kk], alpha [B,Kk]); alpha is a constant unless
     `alpha_grad`, which makes it differentiable as the reference's is (the structure distance's path to the parameters,
-    rd_graph_beta_bwd_alpha)."""
+    rd_graph_beta_bwd_alpha).  p_drop > 0: F.dropout of the post-softmax coefficients (code/Ob_propagation.py:195-196), four
+    independent keep decisions per (edge, step) under `seed` (+ the registered seed cell); only `out` sees it (graph_beta_keep)."""
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError("graph_beta: p_drop must be in [0, 1), got %r" % (p_drop,))
     if V.dim() != 3 or H.dim() != 3 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
         raise ValueError("graph_beta: V [B,N,K], H [B,N,T*32], edge_index [2,E] expected")
     B, N, K = V.shape
@@ -562,7 +594,7 @@ def graph_beta(V, H, map_w, p_t, edge_index, edge_weights, d_ob=4, alpha_grad=Fa
         raise ValueError("graph_beta: edge_weights must be [1 or B, E], got %s" % (tuple(edge_weights.shape),))
     _validate_edges(edge_index, N, "graph_beta")
     return _GraphBeta.apply(V.contiguous(), H.contiguous(), map_w.contiguous(), p_t.contiguous(), edge_index.contiguous(),
-                            edge_weights.contiguous(), int(d_ob), bool(alpha_grad))
+                            edge_weights.contiguous(), int(d_ob), bool(alpha_grad), float(p_drop), int(seed))
 
 
 def _structure_distance_fwd(a):

@@ -348,12 +348,13 @@ class Step:
         prep = self.prep_enc or self.prep_k1
         prep_args = (self.nl if self.prep_enc else 0, self._prep_w, self._prep_saved, self._prep_bytes,
                      _p(W1) if self.prep_k1 else None, _p(W2) if self.prep_k1 else None, _p(self.k1_saved), self.k1_saved.numel(), st)
-        cell = _p(self.seed_cell) if self.p_drop > 0.0 else None
+        drops = self.p_drop > 0.0 or getattr(self.sensor, "edge_drop", False)   # (the use_beta stage's coefficient dropout)
+        cell = _p(self.seed_cell) if drops else None
         if self.plan is not None and prep and self.one_begin:
             return c("rd_step_begin", sp, _p(b["lengths"]), _p(self.plan), cell, 1, *prep_args)
         if self.plan is not None:                                          # lengths -> token plan (+ the seed bump: one launch)
             c("rd_token_plan", sp, _p(b["lengths"]), _p(self.plan), cell, 1, st)
-        elif self.p_drop > 0.0:
+        elif drops:
             c("rd_seed_cell_advance", _p(self.seed_cell), 1, st)           # fresh masks per replay
         if prep:
             c("rd_step_prepare", sp, *prep_args)

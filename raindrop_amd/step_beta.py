@@ -21,6 +21,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
+from .models_rd import edge_dropout_of
 from .step import SensorStage, TrainStep, _p
 
 BETA_EXTRA = ("ob_propagation.increase_dim.weight", "ob_propagation.increase_dim.bias", "ob_propagation.map_weights")
@@ -28,11 +29,21 @@ BETA_EXTRA = ("ob_propagation.increase_dim.weight", "ob_propagation.increase_dim
 
 class BetaSensorStage(SensorStage):
     """The sensor stage of `Raindrop_v2(use_beta=True)`.  distance_weight != 0 (fixed at construction: it selects the backward that
-    gets captured) pushes lambda * d distance through the graph operator; lambda itself lives in the device cell `lam_cell`."""
+    gets captured) pushes lambda * d distance through the graph operator; lambda itself lives in the device cell `lam_cell`.
+    Coefficient dropout: `pe1`, the model's `ob_propagation.dropout` read when the step is built (training-mode model and a step
+    with a backward; an evaluation step never drops), selects rd_beta_stage_fwd_dropout / _bwd_dropout
+    (`ob_propagation_layer2.dropout > 0` is refused, raindrop_amd.models_rd.edge_dropout_of); the masks follow the step's seed and seed cell like the model's own dropout (fresh per replay, the rank offset in
+    the data-parallel form)."""
     prepared_tiles = False        # rd_step_prepare's K1 weight tiles belong to the default branch's fused stage
 
     def __init__(self, distance_weight=0.0):
         self.distance_weight, self.with_distance = float(distance_weight), float(distance_weight) != 0.0
+        self.pe1 = 0.0
+
+    @property
+    def edge_drop(self):
+        """the step draws coefficient-dropout masks: its seed cell must advance per replay even with the model's dropout at 0"""
+        return self.pe1 > 0.0
 
     def check(self, model):
         if not getattr(model, "use_beta", False):
@@ -48,6 +59,10 @@ class BetaSensorStage(SensorStage):
 
     def alloc(self, step):
         g, dev = step.graph_info, step.dev
+        if step.has_backward:
+            self.pe1 = edge_dropout_of(step.model)
+            if not 0.0 <= self.pe1 < 1.0:
+                raise _lib.RaindropHipError("BetaTrainStep: ob_propagation.dropout must be in [0, 1), got %r" % (self.pe1,))
         self.ei = g["edge_index"].contiguous()                    # [2,E] int64, rows E apart
         self.ew = g["edge_weights"].contiguous()
         self.E = int(self.ei.shape[1])
@@ -61,19 +76,23 @@ class BetaSensorStage(SensorStage):
     def forward(self, s, st):
         b, P = s.batch, s.P
         l1, l2 = "ob_propagation.", "ob_propagation_layer2."
-        s._call("rd_beta_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
+        drop = (self.pe1,) if self.edge_drop else ()
+        s._call("rd_beta_stage_fwd_dropout" if self.edge_drop else "rd_beta_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]),
+                _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
                 _p(P[l1 + "lin_value.weight"]), _p(P[l1 + "lin_value.bias"]), _p(P[l1 + "increase_dim.weight"]),
                 _p(P[l1 + "increase_dim.bias"]), _p(P[l1 + "map_weights"]), _p(P[l2 + "lin_value.weight"]), _p(P[l2 + "lin_value.bias"]),
-                _p(self.ei), self.E, _p(self.ew), self.E, s.p_drop, s.seed, _p(s.z), _p(s.mask), _p(self.ei2),
+                _p(self.ei), self.E, _p(self.ew), self.E, s.p_drop, *drop, s.seed, _p(s.z), _p(s.mask), _p(self.ei2),
                 _p(self.alpha), _p(self.distance) if s.model.compute_distance else None, _p(s.k1_saved), s.k1_saved.numel(),
                 _p(s.k1_ws), s.k1_ws.numel(), st)
 
     def backward(self, s, cur, st):
         b, P, G = s.batch, s.P, s.G
         l1, l2 = "ob_propagation.", "ob_propagation_layer2."
-        s._call("rd_beta_stage_bwd", s.sp, _p(b["src"]), _p(P["R_u"]), _p(P[l1 + "lin_value.weight"]),
+        drop = (self.pe1, s.seed) if self.edge_drop else ()
+        s._call("rd_beta_stage_bwd_dropout" if self.edge_drop else "rd_beta_stage_bwd", s.sp, _p(b["src"]), _p(P["R_u"]),
+                _p(P[l1 + "lin_value.weight"]),
                 _p(P[l1 + "increase_dim.weight"]), _p(P[l1 + "map_weights"]), _p(P[l2 + "lin_value.weight"]), _p(self.ei), self.E,
-                _p(self.ew), self.E, s.p_drop, _p(self.ei2), _p(self.alpha), _p(s.k1_saved), s.k1_saved.numel(),
+                _p(self.ew), self.E, s.p_drop, *drop, _p(self.ei2), _p(self.alpha), _p(s.k1_saved), s.k1_saved.numel(),
                 _p(cur), s.D, _p(self.lam_cell) if self.with_distance else None, _p(G["R_u"]),
                 _p(G[l1 + "lin_value.weight"]), _p(G[l1 + "lin_value.bias"]), _p(G[l1 + "increase_dim.weight"]),
                 _p(G[l1 + "increase_dim.bias"]), _p(G[l1 + "map_weights"]), _p(G[l2 + "lin_value.weight"]),
