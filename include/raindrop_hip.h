@@ -605,6 +605,42 @@ int rd_beta_l2_tokens_fwd(const rd_shape* s, int32_t Kk, const int64_t* edge_ind
 int rd_beta_l2_tokens_bwd(const rd_shape* s, int32_t Kk, const int64_t* edge_index_kept, const float* alpha, const float* y2,
                           const float* dz, int32_t lddz, const float* coef, float* dY, void* stream);
 
+/* ---- inference forward: the forward of the model's stages without the save-for-backward buffers ---------------------------------
+ * The training forwards above write, next to their results, what only a backward reads (row tiles and gate bits of the sensor stage;
+ * pre-norm sums, statistics, FFN hidden / gate bytes, row tiles and the log-sum-exp of an encoder layer; X .. coef of the use_beta
+ * stage).  The entry points here produce the SAME z / mask / y / kept edges / alpha / distance, bit for bit (dropout off: inference
+ * never drops), and write none of that.  `saved` is then ONE smaller buffer per stage, rd_*_infer_bytes: the forward's weight operand
+ * tiles and what one forward launch hands to the next.
+ *  - rd_infer_covers: 1 / 0 per stage -- the shape has save-free kernel instantiations in the current arithmetic mode and switches
+ *    (sensor stage: the fused message passing at the P19 shape; encoder: the fused row-local chain at the P19 widths on the
+ *    row-block path, with the fused in_proj + attention launch on a token plan and the attention kernels of the training forward on
+ *    the padded layout).  Where it says 0 the size query returns the training size and the entry point runs the saving forward into
+ *    that buffer.  The use_beta stage has an inference form at every shape it supports.
+ *  - A buffer of the inference size is carved differently from a training one; rd_encoder_layer_prepare, rd_step_prepare and
+ *    rd_step_begin follow the SAME rule as the forward -- a buffer too small for the training carve holds the inference carve, and
+ *    then receives the forward's tiles only --, so pass them the size you pass the forward.
+ *  - rd_sensor_stage_fwd_infer: `prepared` != 0 after rd_step_prepare / rd_step_begin wrote this step's tiles (rd_sensor_stage_fwd_prepared's
+ *    contract).  rd_encoder_layer_fwd_infer honours RD_LAYER_WEIGHTS_PREPARED; where rd_infer_covers says 1 it does not touch
+ *    `workspace` (NULL / 0 allowed).  rd_beta_stage_fwd_infer keeps its large intermediates in `workspace`
+ *    (rd_beta_stage_workspace_bytes), which may be shared with any call that does not overlap it.
+ *  - A buffer smaller than the query's size is RD_EINVAL before any launch.  Token plan and seed-cell registrations are read as in
+ *    the training forwards (the seed cell is ignored: nothing drops). */
+int rd_infer_covers(const rd_shape* s, int32_t* sensor_stage, int32_t* encoder);
+size_t rd_msgpass_infer_bytes(const rd_shape* s);
+size_t rd_encoder_layer_infer_bytes(const rd_shape* s);
+size_t rd_beta_stage_infer_bytes(const rd_shape* s, int32_t E);
+int rd_sensor_stage_fwd_infer(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                              const float* timescales, const float* R_u, const float* W1, const float* b1, const float* W2,
+                              const float* b2, const float* ssum, float* z, uint8_t* mask, void* saved, size_t saved_bytes,
+                              int32_t prepared, void* stream);
+int rd_encoder_layer_fwd_infer(const rd_shape* s, int32_t layer, const float* x, const uint8_t* mask, const rd_encoder_weights* w,
+                               float* y, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int rd_beta_stage_fwd_infer(const rd_shape* s, const float* src, const float* times, const int64_t* lengths, const float* timescales,
+                            const float* R_u, const float* W1, const float* b1, const float* Winc, const float* binc,
+                            const float* map_weights, const float* W2, const float* b2, const int64_t* edge_index, int64_t row_stride,
+                            const float* edge_weights, int32_t E, float* z, uint8_t* mask, int64_t* edge_index_out, float* alpha_out,
+                            float* distance, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- host preprocessing on the device: code/utils_rd.py:149-257, code/Raindrop.py:215-231 ------------
  * Inputs are float64 (the reference's numpy arrays), outputs float32 (its torch.Tensor casts).  Every result is
  * bit-identical to the reference: elementwise steps use the same IEEE float64 operations in the same order, and the

@@ -127,6 +127,15 @@ SIGNATURES = {
     "rd_graph_beta_bwd_dropout": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64,
                                                            c_float, ctypes.c_uint64] + [_P] * 8 + [_P, c_size_t, _P]),
     "rd_graph_beta_keep": (c_int32, [c_int32, c_int32, c_int32, c_float, ctypes.c_uint64, _P, _P]),
+    # inference forward: no save-for-backward buffers (include/raindrop_hip.h "inference forward")
+    "rd_infer_covers": (c_int32, [_SHP, _P, _P]),
+    "rd_msgpass_infer_bytes": (c_size_t, [_SHP]),
+    "rd_encoder_layer_infer_bytes": (c_size_t, [_SHP]),
+    "rd_beta_stage_infer_bytes": (c_size_t, [_SHP, c_int32]),
+    "rd_sensor_stage_fwd_infer": (c_int32, [_SHP] + [_P] * 10 + [_P, _P, _P, c_size_t, c_int32, _P]),
+    "rd_encoder_layer_fwd_infer": (c_int32, [_SHP, c_int32, _P, _P, _ENC, _P, _P, c_size_t, _P, c_size_t, _P]),
+    "rd_beta_stage_fwd_infer": (c_int32, [_SHP] + [_P] * 12 + [_P, ctypes.c_int64, _P, c_int32] + [_P] * 5
+                                + [_P, c_size_t, _P, c_size_t, _P]),
     "rd_structure_distance": (c_int32, [c_int32, c_int32, _P, _P, _P, _P]),
     "rd_structure_distance_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "rd_structure_distance_bwd": (c_int32, [c_int32, c_int32, _P, _P, _P, c_size_t, _P, _P]),

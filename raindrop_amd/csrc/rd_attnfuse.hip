@@ -318,10 +318,11 @@ __device__ __forceinline__ void zero_pad_rows(__bf16* Tp, int tid) {
 // ------------------------------------------------------------------------------------------------------------------------------
 // ONE: RD_PREC_BF16's one-product form as its own instantiation (a runtime flag put a branch in front of every product: rd_encfuse.hip
 // k_enc_post_fwd has the measurement)
-template <int NTH, int KCX, bool ONE>
+// SAVE = false (rd_encoder_layer_fwd_infer): the log-sum-exp, which only the backward reads, is neither formed nor stored.
+template <int NTH, int KCX, bool ONE, bool SAVE = true>
 __global__ __launch_bounds__(AF_THR) void k_attn_fwd_fused(FAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
-  RD_TOUCH_CODE(ONE ? RD_TL_ATTN_FWD_B : RD_TL_ATTN_FWD);                                      // own code -> L2 (rd_common.h; 14 140-byte kernel: ALL of it -- an uncovered tail is fetched cold, line by line, on the pool's slow boxes)
+  RD_TOUCH_CODE(SAVE ? (ONE ? RD_TL_ATTN_FWD_B : RD_TL_ATTN_FWD) : (ONE ? RD_TL_ATTN_INF_B : RD_TL_ATTN_INF));   // own code -> L2 (rd_common.h; 14 140-byte kernel: ALL of it -- an uncovered tail is fetched cold, line by line, on the pool's slow boxes)
   constexpr int HDP = 32 * ((16 * NTH + 31) / 32), LDX = 32 * KCX + 16, NA = (NTH + 1) / 2;
   constexpr int LDO = 16 * NTH + 4;                          // fp32 row stride of the output stage
   __bf16* Xh = reinterpret_cast<__bf16*>(fsm);
@@ -438,7 +439,9 @@ __global__ __launch_bounds__(AF_THR) void k_attn_fwd_fused(FAttnArgs a) {
 #pragma unroll
       for (int j = 0; j < NA; ++j)
         if (t0 + j < NTH) ost[q * LDO + 16 * (t0 + j) + (lane & 15)] = o[j][r] * inv;
-      if (wh == 0 && (lane & 15) == 0 && q < Tv) a.lse[(long)bh * a.T + q] = m_i[r] + logf(l_i[r]);
+      if constexpr (SAVE) {
+        if (wh == 0 && (lane & 15) == 0 && q < Tv) a.lse[(long)bh * a.T + q] = m_i[r] + logf(l_i[r]);
+      }
     }
     AFSTAMP(8 + 8 * h);
     lds_barrier();
@@ -887,12 +890,19 @@ static void fill_args(FAttnArgs& a, const float* x, const void* wf, const void* 
 }
 
 int launch_attn_fused_fwd(const float* x, const void* wf, const float* bias, const int32_t* plan, int T, int B, int D, int H, int hd,
-                          float p_drop, uint64_t seed, uint32_t site, float* out, float* lse, hipStream_t st) {
+                          float p_drop, uint64_t seed, uint32_t site, float* out, float* lse, hipStream_t st, bool save) {
   if (!plan) return fail(RD_EINVAL, "fused attention: needs a token plan");
   FAttnArgs a{};
   fill_args(a, x, wf, nullptr, bias, plan, T, B, D, H, hd, p_drop, seed, site);
   a.out = out; a.lse = lse;
   constexpr size_t lds = fwd_lds<AF_NTH, AF_KCX>();
+  if (!save) {                                               // the save-free instantiation: lse is not written (may be null)
+    if (a.one) { RD_LDS_ATTR((k_attn_fwd_fused<AF_NTH, AF_KCX, true, false>), lds);
+                 hipLaunchKernelGGL((k_attn_fwd_fused<AF_NTH, AF_KCX, true, false>), dim3(B), dim3(AF_THR), lds, st, a); }
+    else { RD_LDS_ATTR((k_attn_fwd_fused<AF_NTH, AF_KCX, false, false>), lds);
+           hipLaunchKernelGGL((k_attn_fwd_fused<AF_NTH, AF_KCX, false, false>), dim3(B), dim3(AF_THR), lds, st, a); }
+    return check_launch("k_attn_fwd_fused<save-free>");
+  }
   if (a.one) { RD_LDS_ATTR((k_attn_fwd_fused<AF_NTH, AF_KCX, true>), lds);
                hipLaunchKernelGGL((k_attn_fwd_fused<AF_NTH, AF_KCX, true>), dim3(B), dim3(AF_THR), lds, st, a); }
   else { RD_LDS_ATTR((k_attn_fwd_fused<AF_NTH, AF_KCX, false>), lds);

@@ -171,10 +171,14 @@ __global__ __launch_bounds__(BT_THR) void k_beta_l2_tokens_bwd(const BtArgs a) {
 
 // p_t [B,T,16] = the positional encoding of every (sample, step), padded steps included (the graph operator scores every step):
 // the expression of k_pe_mask (rd_graph.hip), so these are the bits of z's PE columns.  Also the ones column of the d map_weights sum.
+// ONES = false (the inference forward): `ones`, the backward's reduction operand, is not written
+template <bool ONES = true>
 __global__ __launch_bounds__(256) void k_beta_pt(const float* __restrict__ times, const float* __restrict__ ts, float* __restrict__ p_t,
                                                  float* __restrict__ ones, int T, int B, int H) {
   const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i < B) ones[i] = 1.f;
+  if constexpr (ONES) {
+    if (i < B) ones[i] = 1.f;
+  }
   if (i >= (long)T * B) return;
   const int t = (int)(i / B), b = (int)(i - (long)t * B);
   const float tm = times[i];
@@ -273,10 +277,18 @@ struct Carver {
   template <class P> P* take(size_t nbytes) { P* p = base ? reinterpret_cast<P*>(base + off) : nullptr; off += align_up(nbytes > 0 ? nbytes : 1, 256); return p; }
 };
 
-StageSaved carve_saved(const rd_shape* s, int E, void* base) {
+// infer: the buffer of the inference forward (rd_beta_stage_infer_bytes) holds the graph operator's small per-sample tensors only
+// (beta, p_t, kept); X, V, H, y1, y2 live in the workspace's backward scratch (carve_infer_scratch), coef and ones do not exist
+StageSaved carve_saved(const rd_shape* s, int E, void* base, bool infer = false) {
   const size_t B = s->B, F = s->F, T = s->T, M = B * F, K = T * 4, Kk = (size_t)rd_graph_beta_kept(E);
   Carver c{static_cast<char*>(base), 0};
   StageSaved v;
+  if (infer) {
+    v = StageSaved{};
+    v.beta = c.take<float>(M * T * 4); v.p_t = c.take<float>(B * T * 16 * 4); v.kept = c.take<int32_t>(B * (Kk > 0 ? Kk : 1) * 4);
+    v.bytes = c.off;
+    return v;
+  }
   v.X = c.take<float>(M * K * 4); v.V = c.take<float>(M * K * 4); v.H = c.take<float>(M * T * 32 * 4);
   v.y1 = c.take<float>(M * K * 4); v.y2 = c.take<float>(M * K * 4); v.beta = c.take<float>(M * T * 4);
   v.p_t = c.take<float>(B * T * 16 * 4); v.coef = c.take<float>(B * F * 4); v.ones = c.take<float>(B * 4);
@@ -340,7 +352,7 @@ static int beta_stage_fwd(const rd_shape* s, const float* src, const float* time
                           const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int32_t E, float p_drop,
                           float p_edge1, uint64_t seed, float* z, uint8_t* mask, int64_t* edge_index_out,
                           float* alpha_out, float* distance, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
-                          void* stream) {
+                          void* stream, bool infer = false) {
   int rc = check_stage_shape(s, E);
   if (rc) return rc;
   if (s->B == 0) return RD_OK;
@@ -349,14 +361,18 @@ static int beta_stage_fwd(const rd_shape* s, const float* src, const float* time
   RD_REQUIRE((edge_index_out && alpha_out) || rd_graph_beta_kept(E) == 0, "NULL tensor");
   RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
   RD_REQUIRE(p_edge1 >= 0.f && p_edge1 < 1.f, "edge dropout probability must be in [0,1)");
-  const StageSaved v = carve_saved(s, E, saved);
+  StageSaved v = carve_saved(s, E, saved, infer);
   const StageWs w = carve_ws(s, E, workspace);
   RD_REQUIRE(saved_bytes >= v.bytes, "saved buffer too small: %zu < %zu", saved_bytes, v.bytes);
   RD_REQUIRE(workspace_bytes >= w.bytes, "workspace too small: %zu < %zu", workspace_bytes, w.bytes);
+  // inference: the stage's large intermediates in the workspace's backward scratch (same sizes; no forward launch uses it), y2 over X,
+  // which is dead once V and H are formed
+  if (infer) { v.X = w.a; v.V = w.b; v.y1 = w.c; v.H = w.h; v.y2 = w.a; }
   hipStream_t st = (hipStream_t)stream;
   const int B = s->B, T = s->T, F = s->F, K = 4 * T, M = B * F, Kk = rd_graph_beta_kept(E), D = 4 * F + 16;
   if ((rc = rd_pe_mask(s, times, lengths, timescales, z, mask, stream))) return rc;          // PE columns (either layout) + mask
-  hipLaunchKernelGGL(k_beta_pt, dim3((unsigned)(((long)T * B + 255) / 256)), dim3(256), 0, st, times, timescales, v.p_t, v.ones, T, B, 8);
+  if (infer) hipLaunchKernelGGL(k_beta_pt<false>, dim3((unsigned)(((long)T * B + 255) / 256)), dim3(256), 0, st, times, timescales, v.p_t, nullptr, T, B, 8);
+  else hipLaunchKernelGGL(k_beta_pt<true>, dim3((unsigned)(((long)T * B + 255) / 256)), dim3(256), 0, st, times, timescales, v.p_t, v.ones, T, B, 8);
   if ((rc = check_launch("k_beta_pt"))) return rc;
   if ((rc = rd_obs_embed_fwd(s, src, R_u, p_drop, seed, v.X, stream))) return rc;
   if ((rc = rd_linear_fwd(M, K, K, v.X, K, W1, b1, v.V, K, 1, stream))) return rc;
@@ -368,7 +384,7 @@ static int beta_stage_fwd(const rd_shape* s, const float* src, const float* time
                               edge_index_out, alpha_out, v.beta, v.kept, w.gb, w.gb_bytes, stream);
   if (rc) return rc;
   if ((rc = rd_linear_fwd(M, K, K, v.y1, K, W2, b2, v.y2, K, 1, stream))) return rc;
-  if ((rc = launch_l2_tokens(s, Kk, edge_index_out, alpha_out, v.y2, z, D, nullptr, v.coef, nullptr, st))) return rc;     // + the coefficient table for the backward
+  if ((rc = launch_l2_tokens(s, Kk, edge_index_out, alpha_out, v.y2, z, D, nullptr, v.coef, nullptr, st))) return rc;     // + the coefficient table for the backward (inference: none)
   if (distance) {
     if (Kk > 0) {
       hipLaunchKernelGGL(k_beta_transpose, dim3((unsigned)(((long)B * Kk + 255) / 256)), dim3(256), 0, st, alpha_out, w.alpha_t, B, Kk);
@@ -399,6 +415,22 @@ extern "C" int rd_beta_stage_fwd_dropout(const rd_shape* s, const float* src, co
   return beta_stage_fwd(s, src, times, lengths, timescales, R_u, W1, b1, Winc, binc, map_weights, W2, b2, edge_index, row_stride,
                         edge_weights, E, p_drop, p_edge1, seed, z, mask, edge_index_out, alpha_out, distance, saved,
                         saved_bytes, workspace, workspace_bytes, stream);
+}
+
+// ---- inference forward (include/raindrop_hip.h "inference forward"): same z, mask, kept edges, alpha and distance ------------------
+extern "C" size_t rd_beta_stage_infer_bytes(const rd_shape* s, int32_t E) {
+  if (check_stage_shape(s, E) || s->B == 0) return 256;
+  return carve_saved(s, E, nullptr, true).bytes;
+}
+extern "C" int rd_beta_stage_fwd_infer(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                       const float* timescales, const float* R_u, const float* W1, const float* b1, const float* Winc,
+                                       const float* binc, const float* map_weights, const float* W2, const float* b2,
+                                       const int64_t* edge_index, int64_t row_stride, const float* edge_weights, int32_t E, float* z,
+                                       uint8_t* mask, int64_t* edge_index_out, float* alpha_out, float* distance, void* saved,
+                                       size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+  return beta_stage_fwd(s, src, times, lengths, timescales, R_u, W1, b1, Winc, binc, map_weights, W2, b2, edge_index, row_stride,
+                        edge_weights, E, 0.f, 0.f, 0, z, mask, edge_index_out, alpha_out, distance, saved, saved_bytes, workspace,
+                        workspace_bytes, stream, true);
 }
 
 static int beta_stage_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1, const float* Winc,

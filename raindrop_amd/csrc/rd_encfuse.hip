@@ -306,7 +306,8 @@ __device__ __forceinline__ void ln_load3(float4 (&r)[LNQ], const float* src, int
 // to `keep` ([rows][KPD] in LDS; null: not wanted).
 // bs / gg / bb: the bias, gamma, beta vectors in LDS (zero padded to KPD).
 // PRE: the dropout keep bits come from mk (drop_masks); otherwise from Threefry calls here (seed, site).
-template <bool PRE>
+// SAVE = false (the inference chain): the pre-norm sum and the statistics, which only a backward reads, are not stored.
+template <bool PRE, bool SAVE = true>
 __device__ __forceinline__ void ln_rows4(const float* stage, const float4 (&res)[LNQ], const float* bs, const float* gg, const float* bb, int D,
                                          int m0, int M, int wave, int lane, float p, float inv_keep, const uint8_t* mk, uint64_t seed,
                                          uint32_t site, float* s_out, float* y_out, float* stats, __bf16* Ph, __bf16* Pl, float* keep = nullptr) {
@@ -340,7 +341,7 @@ __device__ __forceinline__ void ln_rows4(const float* stage, const float4 (&res)
     sv[k] = zero4;
     if (ok) {
       sv[k] = make_float4(res[k].x + t.x, res[k].y + t.y, res[k].z + t.z, res[k].w + t.w);
-      *reinterpret_cast<float4*>(s_out + m * D + c) = sv[k];
+      if constexpr (SAVE) *reinterpret_cast<float4*>(s_out + m * D + c) = sv[k];
     }
     part += (sv[k].x + sv[k].y) + (sv[k].z + sv[k].w);
   }
@@ -367,7 +368,9 @@ __device__ __forceinline__ void ln_rows4(const float* stage, const float4 (&res)
     if (Ph && c < KPD) split_store4(Ph + rl * LDD + c, Pl + rl * LDD + c, o);
     if (keep && c < KPD) *reinterpret_cast<float4*>(keep + rl * KPD + c) = o;   // fp32 copy for the next LayerNorm's residual (this lane reads it back)
   }
-  if (i16 == 0 && rok) { stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
+  if constexpr (SAVE) {
+    if (i16 == 0 && rok) { stats[2 * m] = mean; stats[2 * m + 1] = rstd; }
+  }
 }
 
 // DC / HC: model width and FFN width as compile-time constants (0: read from the arguments).  These chains are instruction-issue
@@ -376,7 +379,9 @@ __device__ __forceinline__ void ln_rows4(const float* stage, const float4 (&res)
 // or the chain itself would read is not written -- the FFN hidden h leaves as row tiles (weight gradient) and as one gate BYTE
 // per column quad (the backward needs h > 0, nothing else: 9.2 MB of fp32 written and read back per layer at P19), and the
 // normalised x1 (residual of LayerNorm2) is recomputed from the saved pre-norm sum and statistics instead of stored and re-read.
-template <int RT, int DC, int HC, bool LEAN, bool ONE>
+// SAVE = false (k_enc_post_infer, rd_encoder_layer_fwd_infer): the same chain writing y alone -- no pre-norm sums, statistics, x1, h or
+// gate bytes, no row tiles.  Every operation that reaches y is the same, in the same order.  An instantiation (DESIGN rule 40).
+template <int RT, int DC, int HC, bool LEAN, bool ONE, bool SAVE = true>
 __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned char* esm, int M) {
   constexpr int ROWS = 16 * RT;
   __bf16* Ah = reinterpret_cast<__bf16*>(esm);                 // [ROWS][LDD]: attn, then x1
@@ -397,7 +402,7 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
   const int D = DC ? DC : a.D, H = HC ? HC : a.H;
   const int ntD = (D + 15) >> 4, ntH = (H + 15) >> 4;
   if (m0 >= M) {
-    zero_dead_groups<RT>(a.xt_attn, ntD, m0, M, tid); zero_dead_groups<RT>(a.xt_x1, ntD, m0, M, tid); zero_dead_groups<RT>(a.xt_h, ntH, m0, M, tid);
+    if constexpr (SAVE) { zero_dead_groups<RT>(a.xt_attn, ntD, m0, M, tid); zero_dead_groups<RT>(a.xt_x1, ntD, m0, M, tid); zero_dead_groups<RT>(a.xt_h, ntH, m0, M, tid); }
     return;
   }
   uint64_t seed = a.seed;
@@ -457,7 +462,7 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
   EFSTAMP(1);
   lds_barrier();
   EFSTAMP(2);
-  if (a.xt_attn) export_tiles<RT>(Ah, Al, LDD, a.xt_attn, ntD, m0, M, wave, lane);
+  if (SAVE && a.xt_attn) export_tiles<RT>(Ah, Al, LDD, a.xt_attn, ntD, m0, M, wave, lane);
 
   // ---- out_proj ----
   constexpr int HW0 = 10, NHW = EF_WV - HW0;                    // helper waves 10 .. 15: no column tile in a D-wide product (D <= 160)
@@ -477,12 +482,12 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
   Panel<KCD> p1;                                               // linear1 (column tiles 0..15) streams in under the LayerNorm epilogue
   load_panel<KCD, 0, KCD, true>(p1, a.W1, ntH, wave, lane);    // (requested BEHIND the barrier: issuing it blocks a wave for a while)
   // ---- + bias, dropout, + x, LayerNorm1 -> s1, x1 (global), x1 planes ----
-  if (lnw) ln_rows4<false>(stage, xr, cst, cst + KPD, cst + 2 * KPD, D, m0, M, wave, lane, a.p, inv_keep, nullptr, seed, a.site_ao, a.s1, LEAN ? nullptr : a.x1,
-                    a.st1, Ah, Al, x1r);
+  if (lnw) ln_rows4<false, SAVE>(stage, xr, cst, cst + KPD, cst + 2 * KPD, D, m0, M, wave, lane, a.p, inv_keep, nullptr, seed, a.site_ao, a.s1,
+                                 LEAN || !SAVE ? nullptr : a.x1, a.st1, Ah, Al, x1r);
   EFSTAMP(5);
   lds_barrier();
   EFSTAMP(6);
-  if (a.xt_x1) export_tiles<RT>(Ah, Al, LDD, a.xt_x1, ntD, m0, M, wave, lane);
+  if (SAVE && a.xt_x1) export_tiles<RT>(Ah, Al, LDD, a.xt_x1, ntD, m0, M, wave, lane);
 
   // ---- linear1 -> + bias, ReLU, dropout -> h: the epilogue runs on the ACCUMULATORS (no fp32 stage, no barrier between product and
   // epilogue) -- a lane holds the column quad 16 j + 4 G .. + 3 of row 16 rt + i (mma), which is one dropout quad, one gate byte (LEAN)
@@ -503,7 +508,8 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
           o.x = u.x >= a.p ? o.x * inv_keep : 0.f; o.y = u.y >= a.p ? o.y * inv_keep : 0.f;
           o.z = u.z >= a.p ? o.z * inv_keep : 0.f; o.w = u.w >= a.p ? o.w * inv_keep : 0.f;
         }
-        if (LEAN)
+        if constexpr (!SAVE) { (void)qpr; }
+        else if (LEAN)
           a.hgate[(long)m * qpr + (n >> 2)] = (uint8_t)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
         else
           *reinterpret_cast<float4*>(a.h + (long)m * H + n) = o;
@@ -549,7 +555,7 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
   EFSTAMP(7);
   lds_barrier();
   EFSTAMP(8);
-  if (a.xt_h) export_tiles<RT>(Hh, Hl, LDH, a.xt_h, ntH, m0, M, wave, lane);
+  if (SAVE && a.xt_h) export_tiles<RT>(Hh, Hl, LDH, a.xt_h, ntH, m0, M, wave, lane);
 
   // ---- linear2; LayerNorm2's dropout decisions by the waves without a column tile ----
   if (wave < ntD) {
@@ -572,8 +578,8 @@ __device__ __forceinline__ void post_fwd_body(const PostFwdArgs& a, unsigned cha
       if (c < KPD) xr[k] = *reinterpret_cast<const float4*>(x1r + rl * KPD + c);
     }
   }
-  if (lnw) ln_rows4<true>(stage, xr, cst + 3 * KPD, cst + 4 * KPD, cst + 5 * KPD, D, m0, M, wave, lane, a.p, inv_keep, mk, 0, 0, a.s2, a.y, a.st2,
-                    nullptr, nullptr);
+  if (lnw) ln_rows4<true, SAVE>(stage, xr, cst + 3 * KPD, cst + 4 * KPD, cst + 5 * KPD, D, m0, M, wave, lane, a.p, inv_keep, mk, 0, 0, a.s2, a.y, a.st2,
+                                nullptr, nullptr);
   EFSTAMP(11);
   if (a.stamps && tid == 0) { a.stamps[256 + 1024 + 2 * blockIdx.x] = wall_clock64(); a.stamps[256 + 1024 + 2 * blockIdx.x + 1] = clock64(); }
 }
@@ -595,6 +601,17 @@ __global__ __launch_bounds__(EF_THR) void k_enc_post_fwd(PostFwdArgs a) {
   if (a.mlive) M = min(M, __builtin_amdgcn_readfirstlane(*a.mlive));
   if (pick_rt(M, a.ncu) == 3) post_fwd_body<3, DC, HC, LEAN, ONE>(a, esm, M);
   else post_fwd_body<2, DC, HC, LEAN, ONE>(a, esm, M);
+}
+
+// the save-free chain (post_fwd_body<.., SAVE = false>); compiled for the P19 widths (other widths keep the saving form: rd_infer_covers)
+template <int DC, int HC, bool ONE>
+__global__ __launch_bounds__(EF_THR) void k_enc_post_infer(PostFwdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char esm[];
+  RD_TOUCH_CODE(ONE ? RD_TL_EF_INF_P19_B : RD_TL_EF_INF_P19);   // own code -> L2, all of it, per instantiation (see k_enc_post_fwd)
+  int M = a.M;
+  if (a.mlive) M = min(M, __builtin_amdgcn_readfirstlane(*a.mlive));
+  if (pick_rt(M, a.ncu) == 3) post_fwd_body<3, DC, HC, false, ONE, false>(a, esm, M);
+  else post_fwd_body<2, DC, HC, false, ONE, false>(a, esm, M);
 }
 
 constexpr size_t post_fwd_lds(int rt) {
@@ -962,7 +979,7 @@ int launch_enc_post_fwd(long M, int D, int H, const float* attn, const float* x,
                         const float* bo, const float* b1, const float* b2, const float* g1, const float* be1, const float* g2,
                         const float* be2, float* s1, float* x1, float* st1, float* h, float* s2, float* y, float* st2,
                         void* xt_attn, void* xt_x1, void* xt_h, float p, uint64_t seed, uint32_t site_ao, uint32_t site_fh,
-                        uint32_t site_fo, const int32_t* mlive, void* hgate, hipStream_t st) {
+                        uint32_t site_fo, const int32_t* mlive, void* hgate, hipStream_t st, bool save) {
   PostFwdArgs a{};
   a.attn = attn; a.x = x; a.Wo = (const __bf16*)Wo; a.W1 = (const __bf16*)W1; a.W2 = (const __bf16*)W2;
   a.bo = bo; a.b1 = b1; a.b2 = b2; a.g1 = g1; a.be1 = be1; a.g2 = g2; a.be2 = be2;
@@ -981,6 +998,14 @@ int launch_enc_post_fwd(long M, int D, int H, const float* attn, const float* x,
     if (hgate) { if (a.one) RD_POST_FWD1(DCV, HCV, true, true); else RD_POST_FWD1(DCV, HCV, true, false); }          \
     else { if (a.one) RD_POST_FWD1(DCV, HCV, false, true); else RD_POST_FWD1(DCV, HCV, false, false); }              \
   } while (0)
+  if (!save) {
+    if (spec != 1) return fail(RD_EUNSUPPORTED, "fused encoder chain: no save-free instantiation for D = %d, nhid = %d", D, H);
+    if (a.one) { RD_LDS_ATTR((k_enc_post_infer<152, 272, true>), lds);
+                 hipLaunchKernelGGL((k_enc_post_infer<152, 272, true>), dim3(cdiv((int)M, 32)), dim3(EF_THR), lds, st, a); }
+    else { RD_LDS_ATTR((k_enc_post_infer<152, 272, false>), lds);
+           hipLaunchKernelGGL((k_enc_post_infer<152, 272, false>), dim3(cdiv((int)M, 32)), dim3(EF_THR), lds, st, a); }
+    return check_launch("k_enc_post_infer");
+  }
   if (spec == 1) RD_POST_FWD(152, 272);
   else if (spec == 2) RD_POST_FWD(160, 288);
   else RD_POST_FWD(0, 0);
@@ -988,6 +1013,9 @@ int launch_enc_post_fwd(long M, int D, int H, const float* attn, const float* x,
 #undef RD_POST_FWD1
   return check_launch("k_enc_post_fwd");
 }
+
+// the widths with a save-free chain instantiation, in the current mode and switches
+bool encfuse_infer_ok(int D, int H) { return encfuse_ok(D, H) && ef_specialize(D, H) == 1; }
 
 int encfuse_part_rows(long M) { return (int)((M + 31) / 32); }
 

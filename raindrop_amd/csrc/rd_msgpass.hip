@@ -29,7 +29,8 @@ int fused_wprep(const k1::Layout& L, const float* W1, const float* W2, void* wt,
 int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, const float* b1, const float* b2,
                       const float* ssum, const void* wt, float p_drop, uint64_t seed, void* tpX, void* tpY1,
                       void* m1, void* m2, void* mx, float* z, int ldz, hipStream_t st, const float* times,
-                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe);
+                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save = true);
+bool fused_msgpass_infer_ok(const rd_shape* s);
 int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, const void* wt, float p_drop,
                       const void* m1, const void* m2, const void* mx, const float* dz, int ldz, void* tpD1, void* tpD2,
                       void* ones, float* rupart, hipStream_t st, const void* tpX = nullptr, const void* tpY1 = nullptr);
@@ -205,11 +206,14 @@ MsgSaved carve_saved(const rd_shape* s, void* base) {
 
 // fused path (rd_k1_layout.h): forward -> backward hand-over and backward scratch
 struct FusedSaved { void *wt, *tpX, *tpY1, *m1, *m2, *mx; size_t bytes; };
-FusedSaved carve_fused_saved(const k1::Layout& L, void* base) {
+// infer: the buffer of the save-free forward (rd_msgpass_infer_bytes) -- the weight tiles, at the same offset, and nothing else
+FusedSaved carve_fused_saved(const k1::Layout& L, void* base, bool infer = false) {
   FusedSaved v; size_t off = 0;
   auto take = [&](size_t bytes) { void* p = base ? (void*)((char*)base + off) : nullptr;
                                   off += align_up(bytes, 256); return p; };
-  v.wt = take(L.wt_bytes); v.tpX = take(L.tp_bytes); v.tpY1 = take(L.tp_bytes);
+  v.wt = take(L.wt_bytes);
+  if (infer) { v.tpX = v.tpY1 = v.m1 = v.m2 = v.mx = nullptr; v.bytes = off; return v; }
+  v.tpX = take(L.tp_bytes); v.tpY1 = take(L.tp_bytes);
   v.m1 = take(L.g1_bytes); v.m2 = take(L.g2_bytes); v.mx = take(L.mx_bytes);
   v.bytes = off;
   return v;
@@ -363,13 +367,42 @@ extern "C" int rd_sensor_stage_fwd_prepared(const rd_shape* s, const float* src,
                                stream, true);
 }
 
+// ---- inference forward: nothing that only a backward reads is written (include/raindrop_hip.h "inference forward") -------------
+extern "C" size_t rd_msgpass_infer_bytes(const rd_shape* s) {
+  if (!s || s->T <= 0 || s->F <= 0 || s->d_ob <= 0 || s->B < 0) return 0;
+  if (!fused_msgpass_infer_ok(s)) return rd_msgpass_saved_bytes(s);
+  return carve_fused_saved(k1::make_layout(s->B, s->T, s->F), nullptr, true).bytes;
+}
+
+extern "C" int rd_sensor_stage_fwd_infer(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                         const float* timescales, const float* R_u, const float* W1, const float* b1,
+                                         const float* W2, const float* b2, const float* ssum, float* z, uint8_t* mask,
+                                         void* saved, size_t saved_bytes, int32_t prepared, void* stream) {
+  int rc = check_shape(s);
+  if (rc) return rc;
+  if (!fused_msgpass_infer_ok(s))                    // no save-free instantiation: the saving forward into the buffer the query sized
+    return sensor_stage_fwd_impl(s, src, times, lengths, timescales, R_u, W1, b1, W2, b2, ssum, 0.f, 0, z, mask, saved, saved_bytes,
+                                 stream, prepared != 0);
+  if (s->B == 0) return RD_OK;
+  RD_REQUIRE(times && lengths && timescales && mask, "NULL tensor");
+  RD_REQUIRE(src && R_u && W1 && b1 && W2 && b2 && ssum && z && saved, "NULL tensor");
+  const k1::Layout L = k1::make_layout(s->B, s->T, s->F);
+  FusedSaved fv = carve_fused_saved(L, saved, true);
+  RD_REQUIRE(saved_bytes >= fv.bytes, "inference buffer too small: %zu < %zu", saved_bytes, fv.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  if (!prepared && (rc = fused_wprep(L, W1, W2, fv.wt, st))) return rc;
+  return fused_msgpass_fwd(L, src, R_u, b1, b2, ssum, fv.wt, 0.f, 0, nullptr, nullptr, nullptr, nullptr, nullptr, z,
+                           s->F * s->d_ob + s->d_pe, st, times, lengths, timescales, mask, s->d_pe, false);
+}
+
 namespace rd {
 // the operand-tile jobs of the fused message-passing stage (W1, W2: forward and transposed orientation) for rd_step_prepare;
 // 0 when this shape / mode does not run the fused path (its weights are then read as fp32)
 int k1_weight_split_specs(const rd_shape* s, const float* W1, const float* W2, void* saved, size_t saved_bytes, WsplitSpec* out) {
   if (!s || !fused_msgpass_ok(s) || !saved) return 0;
   const k1::Layout L = k1::make_layout(s->B, s->T, s->F);
-  FusedSaved fv = carve_fused_saved(L, saved);
+  // the tiles come first in both carves: a buffer of the inference size (rd_msgpass_infer_bytes) holds them at the same offset
+  FusedSaved fv = carve_fused_saved(L, saved, saved_bytes < carve_fused_saved(L, nullptr).bytes);
   if (saved_bytes < fv.bytes) return 0;
   const size_t per = (size_t)L.nct * k1::NKC * 2 * k1::TILE;           // bf16 elements of one (layer, orientation) tile set
   __bf16* wt = (__bf16*)fv.wt;

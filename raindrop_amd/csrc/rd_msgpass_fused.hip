@@ -497,10 +497,13 @@ __device__ __forceinline__ void tstore_leftover_planes(const __bf16* Ph, const _
 // barrier group B does the work that depends on nothing a product makes (positional encoding: off the kernel's tail) while the
 // matrix pipe serves group A's product first (older waves win the arbitration), and group A exports X's row tiles behind its
 // product while group B multiplies.
-template <int RT, int FC, int TC>
+// SAVE = false (rd_sensor_stage_fwd_infer; compiled for the P19 shape only, other shapes keep the saving form: rd_infer_covers): the same forward without what only a backward reads -- the row tiles of
+// X and Y1, the three gate tensors, the per-sample `lin` and the plan's slack cell.  Every operation that reaches z is the same, in
+// the same order: z, the PE columns and the mask are bit-identical.  An instantiation, not a flag (DESIGN rule 40).
+template <int RT, int FC, int TC, bool SAVE = true>
 __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  RD_TOUCH_CODE(FC == 34 && TC == 60 ? RD_TL_K1_FWD_P19 : RD_TL_K1_FWD);   // own code -> L2 (rd_common.h)
+  RD_TOUCH_CODE(!SAVE ? RD_TL_K1_INF_P19 : FC == 34 && TC == 60 ? RD_TL_K1_FWD_P19 : RD_TL_K1_FWD);   // own code -> L2 (rd_common.h)
   constexpr int ROWS = RT * 16;
   constexpr size_t PLANES = (size_t)4 * ROWS * LDX * sizeof(__bf16);
   __bf16* Xh = reinterpret_cast<__bf16*>(smem_raw);
@@ -573,8 +576,9 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
       }
       const int o = pofs(f, 4 * t);                           // the cell's 4 channels: half a 16-byte chunk of row f
       split_store4(Xh + o, Xl + o, x);
-      a.mx[(size_t)(m24(sb, total) + m24(t, F) + f)] =        // [slot][t][f]: consecutive lanes, consecutive bytes
-          (uint8_t)((x[0] > 0.f ? 1 : 0) | (x[1] > 0.f ? 2 : 0) | (x[2] > 0.f ? 4 : 0) | (x[3] > 0.f ? 8 : 0));
+      if constexpr (SAVE)
+        a.mx[(size_t)(m24(sb, total) + m24(t, F) + f)] =      // [slot][t][f]: consecutive lanes, consecutive bytes
+            (uint8_t)((x[0] > 0.f ? 1 : 0) | (x[1] > 0.f ? 2 : 0) | (x[2] > 0.f ? 4 : 0) | (x[3] > 0.f ? 8 : 0));
     }
   };
   // dropout masks: one generator call = the 4 channel masks of a (t, f) cell; no memory traffic
@@ -628,9 +632,11 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   for (int w = 0; w < NWAVE; ++w) lin = max(lin, LinW[w]);
   lin = __builtin_amdgcn_readfirstlane(lin);
   const int kclim1 = (4 * lin + 31) >> 5;
-  if (tid == 0) {
-    a.lin[sb] = lin;
-    if (a.plan && lin > L) atomicMax(const_cast<int*>(a.plan) + plan::I_SLACK, lin - L);
+  if constexpr (SAVE) {
+    if (tid == 0) {
+      a.lin[sb] = lin;
+      if (a.plan && lin > L) atomicMax(const_cast<int*>(a.plan) + plan::I_SLACK, lin - L);
+    }
   }
 
   // ---- layer 1: Y1 = relu(X W1^T + b1) * ssum;  X leaves as row tiles for dW1 (group B, straight from the planes) --------
@@ -662,7 +668,7 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   RD_STAMP(3);
   if (live2) load_panel_kc<NKC / 2, NKC>(pw, wtiles(a, dm, 1, 0), nct, wave, lane);   // second half
   RD_STAMP(12);
-  if (!grpB) {                                               // ... and group A, whose product the matrix pipe served first, exports X's row tiles
+  if (SAVE && !grpB) {                                       // ... and group A, whose product the matrix pipe served first, exports X's row tiles
     tstore_planes_main(Xh, Xl, a.tpX, dm, sb, gw, GWAVE, lane, nct);
     tstore_leftover_planes(Xh, Xl, a.tpX, dm, sb, gt, GTHR, K);
     tzero_uncovered(a.tpX, dm, sb, gt, GTHR);
@@ -684,20 +690,23 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
         const float y[4] = {fmaxf(acc[jj][rt][0] + bias.x, 0.f) * srow[rt], fmaxf(acc[jj][rt][1] + bias.y, 0.f) * srow[rt],
                             fmaxf(acc[jj][rt][2] + bias.z, 0.f) * srow[rt], fmaxf(acc[jj][rt][3] + bias.w, 0.f) * srow[rt]};
         store_split_quad(Yh, Yl, rt * 16 + (lane & 15), n0, y);
+        if constexpr (!SAVE) continue;
         // (rt is a compile-time constant after unrolling; the collector slots are immediates)
         if (rt == 0) { collect_mask<0>(gv, __ballot(y[0] > 0.f)); collect_mask<1>(gv, __ballot(y[1] > 0.f)); collect_mask<2>(gv, __ballot(y[2] > 0.f)); collect_mask<3>(gv, __ballot(y[3] > 0.f)); }
         if (rt == 1) { collect_mask<4>(gv, __ballot(y[0] > 0.f)); collect_mask<5>(gv, __ballot(y[1] > 0.f)); collect_mask<6>(gv, __ballot(y[2] > 0.f)); collect_mask<7>(gv, __ballot(y[3] > 0.f)); }
         if (rt == 2) { collect_mask<8>(gv, __ballot(y[0] > 0.f)); collect_mask<9>(gv, __ballot(y[1] > 0.f)); collect_mask<10>(gv, __ballot(y[2] > 0.f)); collect_mask<11>(gv, __ballot(y[3] > 0.f)); }
       }
-      if (lane < RT * 8) reinterpret_cast<int*>(a.m1 + (size_t)(m24(sb, nct) + j) * (RT * 4))[lane] = gv;
+      if (SAVE && lane < RT * 8) reinterpret_cast<int*>(a.m1 + (size_t)(m24(sb, nct) + j) * (RT * 4))[lane] = gv;
     }
   }
   RD_STAMP(4);
   lds_barrier();
   RD_STAMP(5);
   // Y1 -> row tiles for dW2, straight from the planes (every wave takes its share of the 2 q nct tile parts; the leftover rows as before)
-  tstore_planes_main(Yh, Yl, a.tpY1, dm, sb, __builtin_amdgcn_readfirstlane(wave), NWAVE, lane, nct);
-  tstore_leftover_planes(Yh, Yl, a.tpY1, dm, sb, tid, NTHR, K);
+  if constexpr (SAVE) {
+    tstore_planes_main(Yh, Yl, a.tpY1, dm, sb, __builtin_amdgcn_readfirstlane(wave), NWAVE, lane, nct);
+    tstore_leftover_planes(Yh, Yl, a.tpY1, dm, sb, tid, NTHR, K);
+  }
 
   // ---- layer 2: Y2 = relu(Y1 W2^T + b2) * ssum -> fp32 staging (live column tiles only) ------------
   zero_acc<RT>(acc);
@@ -734,8 +743,9 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
     float* dst = a.z + (size_t)(m24(tk.row0 + m24(t, tk.rstride), ldz) + 4 * f);
     if ((ldz & 3) == 0) st16f(dst, y);
     else { dst[0] = y.x; dst[1] = y.y; dst[2] = y.z; dst[3] = y.w; }
-    a.m2[(size_t)(m24(sb, total) + m24(t, F) + f)] =
-        (uint8_t)((y.x > 0.f ? 1 : 0) | (y.y > 0.f ? 2 : 0) | (y.z > 0.f ? 4 : 0) | (y.w > 0.f ? 8 : 0));
+    if constexpr (SAVE)
+      a.m2[(size_t)(m24(sb, total) + m24(t, F) + f)] =
+          (uint8_t)((y.x > 0.f ? 1 : 0) | (y.y > 0.f ? 2 : 0) | (y.z > 0.f ? 4 : 0) | (y.w > 0.f ? 8 : 0));
   }
   RD_STAMP(9);
   RD_STAMP_WG_END();
@@ -994,11 +1004,29 @@ int launch_fused(const FusedArgs& a, bool bwd, hipStream_t st) {
   return check_launch("k_msg_bwd_fused");
 }
 
+// the save-free forward: the P19 instantiation only (fused_msgpass_infer_ok is the host-side test)
+int launch_fused_infer(const FusedArgs& a, hipStream_t st) {
+  const size_t lds = (size_t)4 * 3 * 16 * LDX * sizeof(__bf16) + (size_t)3 * 16 * sizeof(float) + (size_t)NWAVE * sizeof(int);
+  RD_LDS_ATTR((k_msg_fwd_fused<3, 34, 60, false>), lds);
+  hipLaunchKernelGGL((k_msg_fwd_fused<3, 34, 60, false>), dim3(a.B), dim3(NTHR), lds, st, a);
+  return check_launch("k_msg_fwd_fused<save-free>");
+}
+
+static bool k1_specialize_on() {
+  const char* e = getenv("RD_K1_SPECIALIZE");          // read per call
+  return !(e && atoi(e) == 0);
+}
+
 // RD_K1_SPECIALIZE=0 runs the P19 shape on the generic instantiation (A/B, and the parity test of the two)
-int launch_fused_shape(const FusedArgs& a, const k1::Layout& L, bool bwd, hipStream_t st) {
+int launch_fused_shape(const FusedArgs& a, const k1::Layout& L, bool bwd, hipStream_t st, bool save = true) {
   if (a.ldz >= 1024) return fail(RD_EUNSUPPORTED, "fused message passing: ldz (%d) must be < 1024", a.ldz);
   const char* e = getenv("RD_K1_SPECIALIZE");
   const bool model_layout = a.ldz == 4 * L.F + 16 && (bwd || a.times == nullptr || a.d_pe == 16);
+  if (!save) {
+    if (bwd || !(L.F == 34 && L.T == 60 && model_layout && k1_specialize_on()))
+      return fail(RD_EUNSUPPORTED, "fused message passing: no save-free instantiation for this shape");
+    return launch_fused_infer(a, st);
+  }
   if (L.F == 34 && L.T == 60 && model_layout && !(e && atoi(e) == 0)) return launch_fused<3, 34, 60>(a, bwd, st);
   switch (L.RT) {
     case 1: return launch_fused<1, 0, 0>(a, bwd, st);
@@ -1036,10 +1064,16 @@ int fused_wprep(const k1::Layout& L, const float* W1, const float* W2, void* wt,
   return check_launch("k_wprep");
 }
 
+// the sensor stage of this shape has a save-free forward (model layout: ldz = 4 F + 16, d_pe = 16) in the current mode and switches
+bool fused_msgpass_infer_ok(const rd_shape* s) {
+  return fused_msgpass_ok(s) && s->F == 34 && s->T == 60 && s->d_pe == 16 && k1_specialize_on();
+}
+
+// save = false: the save-free instantiation (tpX .. mx are not touched and may be null)
 int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, const float* b1, const float* b2,
                       const float* ssum, const void* wt, float p_drop, uint64_t seed, void* tpX, void* tpY1,
                       void* m1, void* m2, void* mx, float* z, int ldz, hipStream_t st, const float* times,
-                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe) {
+                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save) {
   FusedArgs a{};
   fill_layout(a, L);
   a.times = times; a.lengths = lengths; a.tscale = tscale; a.mask = mask; a.d_pe = d_pe;
@@ -1047,8 +1081,8 @@ int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, c
   a.tpX = (__bf16*)tpX; a.tpY1 = (__bf16*)tpY1; a.m1 = (uint64_t*)m1; a.m2 = (uint8_t*)m2; a.mx = (uint8_t*)mx;
   a.z = z; a.ldz = ldz;
   a.p_drop = p_drop; a.seed = seed; a.seed_cell = seed_cell(); a.stamps = g_stamps;
-  a.plan = token_plan(); a.lin = reinterpret_cast<int*>(reinterpret_cast<char*>(mx) + k1::lin_offset(L.B, L.T, L.F));
-  return launch_fused_shape(a, L, false, st);
+  a.plan = token_plan(); a.lin = save ? reinterpret_cast<int*>(reinterpret_cast<char*>(mx) + k1::lin_offset(L.B, L.T, L.F)) : nullptr;
+  return launch_fused_shape(a, L, false, st, save);
 }
 
 int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, const void* wt, float p_drop,

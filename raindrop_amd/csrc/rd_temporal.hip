@@ -50,7 +50,7 @@ int attnfuse_split_specs(const float* in_proj_w, int D, int H, int hd, void* wf,
 int attnfuse_padded_cols(int H);
 int attnfuse_nth();
 int launch_attn_fused_fwd(const float* x, const void* wf, const float* bias, const int32_t* plan, int T, int B, int D, int H, int hd,
-                          float p_drop, uint64_t seed, uint32_t site, float* out, float* lse, hipStream_t st);
+                          float p_drop, uint64_t seed, uint32_t site, float* out, float* lse, hipStream_t st, bool save = true);
 int launch_attn_fused_bwd(const float* x, const void* wf, const void* wb, const float* bias, const int32_t* plan, int T, int B, int D, int H,
                           int hd, float p_drop, uint64_t seed, uint32_t site, const float* out, const float* lse, const float* dout,
                           const float* ds1, float* dx, void* xt, void* dt, hipStream_t st);
@@ -59,7 +59,8 @@ int launch_enc_post_fwd(long M, int D, int H, const float* attn, const float* x,
                         const float* bo, const float* b1, const float* b2, const float* g1, const float* be1, const float* g2,
                         const float* be2, float* s1, float* x1, float* st1, float* h, float* s2, float* y, float* st2,
                         void* xt_attn, void* xt_x1, void* xt_h, float p, uint64_t seed, uint32_t site_ao, uint32_t site_fh,
-                        uint32_t site_fo, const int32_t* mlive, void* hgate, hipStream_t st);
+                        uint32_t site_fo, const int32_t* mlive, void* hgate, hipStream_t st, bool save = true);
+bool encfuse_infer_ok(int D, int H);
 int encfuse_part_rows(long M);
 int launch_enc_pre_bwd(long M, int D, int H, const float* dy, const float* s2, const float* st2, const float* g2, const float* h,
                        const float* s1, const float* st1, const float* g1, const void* W2t, const void* W1t, const void* Wot,
@@ -2409,10 +2410,23 @@ struct EncSaved { float *qkv, *attn, *lse, *s1, *st1, *x1, *h, *s2, *st2; __bf16
                   float *pbig, *pdbig;                // wide heads only: P and dropout(P), [B*H][T][T] each
                   size_t bytes; };
 // weight tiles kept from forward to backward: 0 in_proj, 1 out_proj, 2 lin1, 3 lin2, 4 out_proj^T, 5 lin2^T, 6 lin1^T, 7 in_proj^T
-EncSaved carve_saved(const EncDims& e, void* base) {
+// infer: the buffer of the inference forward (rd_encoder_layer_infer_bytes) -- the four forward weight orientations, the fused
+// attention's forward tiles and what one forward launch hands to the next (attn; qkv and lse on the layouts whose attention is not
+// fused); everything else is null
+EncSaved carve_saved(const EncDims& e, void* base, bool infer = false) {
   EncSaved v; size_t off = 0;
   auto take = [&](size_t n) { float* p = base ? (float*)((char*)base + off) : nullptr;
                               off += align_up(n * sizeof(float), 256); return p; };
+  if (infer) {
+    v = EncSaved{};
+    const int prow[4] = {3 * e.D, e.D, e.nhid, e.D}, pcol[4] = {e.D, e.D, e.D, e.nhid};
+    for (int i = 0; i < 4; ++i)
+      for (int h = 0; h < 2; ++h) v.pl[i][h] = (__bf16*)take((rowgemm_plane_elems(prow[i], pcol[i]) + 1) / 2);
+    v.afw = (__bf16*)take((attnfuse_wf_elems(e.H) + 1) / 2);
+    v.attn = take(e.M * e.D); v.qkv = take(e.M * 3 * e.D); v.lse = take((size_t)e.B * e.H * e.T);
+    v.bytes = off;
+    return v;
+  }
   v.qkv = take(e.M * 3 * e.D); v.attn = take(e.M * e.D); v.lse = take((size_t)e.B * e.H * e.T);
   v.s1 = take(e.M * e.D); v.st1 = take(e.M * 2); v.x1 = take(e.M * e.D);
   v.h = take(e.M * e.nhid); v.s2 = take(e.M * e.D); v.st2 = take(e.M * 2);
@@ -2555,24 +2569,47 @@ extern "C" size_t rd_encoder_layer_workspace_bytes(const rd_shape* s) {
 extern "C" void rd_debug_set_attn_stamps(void* p) { g_attn_stamps = (unsigned long long*)p; }   // not part of the ABI
 
 // weights of a layer -> native bf16 hi/lo operand tiles (both orientations) + the constant tiles of the weight-gradient stream
-static int enc_split_specs(const EncDims& e, const rd_encoder_weights* w, const EncSaved& v, WsplitSpec* out, bool all8 = false) {
+static int enc_split_specs(const EncDims& e, const rd_encoder_weights* w, const EncSaved& v, WsplitSpec* out, bool all8 = false,
+                           bool fwd_only = false) {
   const float* Ws[8] = {w->in_proj_w, w->out_proj_w, w->lin1_w, w->lin2_w, w->out_proj_w, w->lin2_w, w->lin1_w, w->in_proj_w};
   const int Ns[8] = {3 * e.D, e.D, e.nhid, e.D, e.D, e.D, e.nhid, 3 * e.D};
   const int Ks[8] = {e.D, e.D, e.D, e.nhid, e.D, e.nhid, e.D, e.D};
   const int Tr[8] = {0, 0, 0, 0, 1, 1, 1, 1};
-  int njobs = (all8 || rowgemm_ok(e.D, 3 * e.D, 3 * e.D, e.D)) ? 8 : 7;
+  int njobs = fwd_only ? 4 : (all8 || rowgemm_ok(e.D, 3 * e.D, 3 * e.D, e.D)) ? 8 : 7;      // fwd_only: the inference carve (no transposes)
   for (int i = 0; i < njobs; ++i) out[i] = WsplitSpec{Ws[i], Ns[i], Ks[i], Tr[i], v.pl[i][0]};
   // the fused attention's per-head in_proj tiles (6 H more jobs of a few tiles each; whether a call takes that path depends on the
   // token plan, which a prepare call does not see: split whenever the shape is in its envelope)
-  if (!all8 && attnfuse_ok(e.T, e.D, e.H, e.Hd)) njobs += attnfuse_split_specs(w->in_proj_w, e.D, e.H, e.Hd, v.afw, v.abw, out + njobs);
+  if (fwd_only && attnfuse_ok(e.T, e.D, e.H, e.Hd)) {
+    WsplitSpec both[12];
+    const int nb = e.H <= 2 ? attnfuse_split_specs(w->in_proj_w, e.D, e.H, e.Hd, v.afw, v.afw, both) : 0;
+    for (int i = 0; i < nb; i += 2) out[njobs++] = both[i];                // (forward form, input-gradient form) pairs: the first of each
+  } else if (!all8 && attnfuse_ok(e.T, e.D, e.H, e.Hd)) njobs += attnfuse_split_specs(w->in_proj_w, e.D, e.H, e.Hd, v.afw, v.abw, out + njobs);
   return njobs;
 }
 constexpr int ENC_MAX_SPECS = 8 + 12;                  // per layer: 8 orientations + (fused attention, H = 2) 6 H
-static int enc_prepare(const EncDims& e, const rd_encoder_weights* w, const EncSaved& v, bool tw, hipStream_t st) {
+static int enc_prepare(const EncDims& e, const rd_encoder_weights* w, const EncSaved& v, bool tw, hipStream_t st, bool fwd_only = false) {
   WsplitSpec specs[ENC_MAX_SPECS];
-  const int n = enc_split_specs(e, w, v, specs);
+  const int n = enc_split_specs(e, w, v, specs, false, fwd_only);
   void* on[1] = {v.ones};
-  return launch_wsplit_specs(n, specs, tw ? 1 : 0, on, st);
+  return launch_wsplit_specs(n, specs, tw && !fwd_only ? 1 : 0, on, st);
+}
+
+// The encoder layer of this shape has an inference forward in the current mode and switches: the row-block + tile-stream path with
+// the LayerNorm epilogues and a save-free instantiation of the fused chain (P19 widths).  The attention launch is the fused
+// save-free one on a token plan, the saving kernels (into the inference buffer's qkv / lse) on the padded layout.
+static bool enc_infer_ok(const EncDims& e) {
+  const char* lf = getenv("RD_LN_FUSE");
+  const bool rg = rowgemm_ok(3 * e.D, e.D, e.D, 3 * e.D) && rowgemm_ok(e.D, e.D, e.D, e.D) &&
+                  rowgemm_ok(e.nhid, e.D, e.D, e.nhid) && rowgemm_ok(e.D, e.nhid, e.nhid, e.D);
+  return rg && tile_path(e) && !(lf && atoi(lf) == 0) && rowgemm_ln_ok(e.D, e.D) && rowgemm_ln_ok(e.D, e.nhid) && !attn_big(e) &&
+         e.H <= 2 && encfuse_infer_ok(e.D, e.nhid);
+}
+// The carve a buffer of `bytes` holds: the training carve when it is large enough for it, else the inference carve -- ONE rule for
+// rd_encoder_layer_prepare / rd_step_prepare / rd_step_begin and rd_encoder_layer_fwd_infer, so the tile offsets cannot disagree.
+static EncSaved carve_for_bytes(const EncDims& e, void* base, size_t bytes, bool* infer) {
+  const bool small = enc_infer_ok(e) && bytes < carve_saved(e, nullptr).bytes;
+  if (infer) *infer = small;
+  return carve_saved(e, base, small);
 }
 
 extern "C" int rd_encoder_layer_prepare(const rd_shape* s, const rd_encoder_weights* w, void* saved, size_t saved_bytes,
@@ -2582,12 +2619,13 @@ extern "C" int rd_encoder_layer_prepare(const rd_shape* s, const rd_encoder_weig
   if (s->B == 0) return RD_OK;
   RD_REQUIRE(w && saved, "NULL tensor");
   const EncDims e = enc_dims(s);
-  EncSaved v = carve_saved(e, saved);
+  bool infer = false;
+  EncSaved v = carve_for_bytes(e, saved, saved_bytes, &infer);
   RD_REQUIRE(saved_bytes >= v.bytes, "saved buffer too small");
   const bool rg = rowgemm_ok(3 * e.D, e.D, e.D, 3 * e.D) && rowgemm_ok(e.D, e.D, e.D, e.D) &&
                   rowgemm_ok(e.nhid, e.D, e.D, e.nhid) && rowgemm_ok(e.D, e.nhid, e.nhid, e.D);
   if (!rg) return RD_OK;                             // the tiled path reads the fp32 weights directly
-  return enc_prepare(e, w, v, tile_path(e), (hipStream_t)stream);
+  return enc_prepare(e, w, v, tile_path(e), (hipStream_t)stream, infer);
 }
 
 namespace rd {
@@ -2612,10 +2650,11 @@ static int step_prepare_impl(const rd_shape* s, int32_t nlayers, const rd_encode
   if (rg)
     for (int l = 0; l < nlayers; ++l) {
       RD_REQUIRE(w[l] && enc_saved[l], "NULL tensor");
-      EncSaved v = carve_saved(e, enc_saved[l]);
+      bool infer = false;                              // a buffer of the inference size: the forward's tiles only
+      EncSaved v = carve_for_bytes(e, enc_saved[l], enc_saved_bytes[l], &infer);
       RD_REQUIRE(enc_saved_bytes[l] >= v.bytes, "saved buffer too small");
-      n += enc_split_specs(e, w[l], v, specs + n);
-      if (tw) ones[no++] = v.ones;
+      n += enc_split_specs(e, w[l], v, specs + n, false, infer);
+      if (tw && !infer) ones[no++] = v.ones;
     }
   if (W1 && W2 && k1_saved) n += k1_weight_split_specs(s, W1, W2, k1_saved, k1_saved_bytes, specs + n);
   if (n == 0) return plan_out ? rd_token_plan(s, lengths, plan_out, seed_cell_dev, delta, stream) : RD_OK;
@@ -2745,6 +2784,61 @@ extern "C" int rd_encoder_layer_fwd(const rd_shape* s, int32_t layer, const floa
   }
   return launch_add_ln_fwd(v.x1, ws.f, w->norm2_w, w->norm2_b, v.s2, y, v.st2, (int)e.M, e.D, p_drop, seed,
                            SITE_FFN_OUT + L, st);
+}
+
+// ---- inference forward (include/raindrop_hip.h "inference forward") -----------------------------------------------------------
+namespace rd { bool fused_msgpass_infer_ok(const rd_shape* s); }
+
+extern "C" int rd_infer_covers(const rd_shape* s, int32_t* sensor_stage, int32_t* encoder) {
+  if (check_enc(s)) return RD_EINVAL;
+  if (sensor_stage) *sensor_stage = fused_msgpass_infer_ok(s) ? 1 : 0;
+  if (encoder) *encoder = enc_infer_ok(enc_dims(s)) ? 1 : 0;
+  return RD_OK;
+}
+
+extern "C" size_t rd_encoder_layer_infer_bytes(const rd_shape* s) {
+  if (check_enc(s)) return 0;
+  const EncDims e = enc_dims(s);
+  return carve_saved(e, nullptr, enc_infer_ok(e)).bytes;
+}
+
+extern "C" int rd_encoder_layer_fwd_infer(const rd_shape* s, int32_t layer, const float* x, const uint8_t* mask,
+                                          const rd_encoder_weights* w, float* y, void* saved, size_t saved_bytes, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  int rc = check_enc(s);
+  if (rc) return rc;
+  const EncDims e = enc_dims(s);
+  if (!enc_infer_ok(e))                               // no save-free instantiation: the saving forward into the buffer the query sized
+    return rd_encoder_layer_fwd(s, layer, x, mask, w, 0.f, 0, y, saved, saved_bytes, workspace, workspace_bytes, stream);
+  if (s->B == 0) return RD_OK;
+  RD_REQUIRE(x && mask && w && y && saved, "NULL tensor");
+  EncSaved v = carve_for_bytes(e, saved, saved_bytes, nullptr);
+  RD_REQUIRE(saved_bytes >= v.bytes, "inference buffer too small: %zu < %zu", saved_bytes, v.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const bool prepared = (layer & RD_LAYER_WEIGHTS_PREPARED) != 0;
+  layer &= 0xffff;
+  const uint32_t L = (uint32_t)layer;
+  const int32_t* tp = token_plan();
+  struct MliveScope { MliveScope(const int32_t* p) { rowgemm_set_mlive(p); } ~MliveScope() { rowgemm_set_mlive(nullptr); } } mscope(tp);
+  const bool afuse = tp && attnfuse_ok(e.T, e.D, e.H, e.Hd);
+  if (!prepared && (rc = enc_prepare(e, w, v, true, st, true))) return rc;
+  if (afuse) {
+    if ((rc = launch_attn_fused_fwd(x, v.afw, w->in_proj_b, tp, e.T, e.B, e.D, e.H, e.Hd, 0.f, 0, SITE_ATTN_PROB + L, v.attn, nullptr, st, false)))
+      return rc;
+  } else {                                            // in_proj without its row-tile export, then the attention kernels of the training forward
+    if ((rc = launch_rowgemm(e.M, 3 * e.D, e.D, x, e.D, v.pl[0][0], v.pl[0][1], v.qkv, 3 * e.D, w->in_proj_b, 0, nullptr, 0,
+                             0.f, nullptr, 0, 0.f, 0, 0, st))) return rc;
+    AttnArgs a{};
+    a.qkv = v.qkv; a.mask = mask; a.out = v.attn; a.lse = v.lse;
+    a.T = e.T; a.B = e.B; a.D = e.D; a.H = e.H; a.hd = e.Hd;
+    a.scale = 1.0f / sqrtf((float)e.Hd); a.p_drop = 0.f; a.seed = 0; a.site = SITE_ATTN_PROB + L; a.seed_cell = seed_cell();
+    a.plan = tp;
+    if ((rc = dispatch_attn(a, 0, st))) return rc;
+  }
+  return launch_enc_post_fwd(e.M, e.D, e.nhid, v.attn, x, v.pl[1][0], v.pl[2][0], v.pl[3][0], w->out_proj_b, w->lin1_b, w->lin2_b,
+                             w->norm1_w, w->norm1_b, w->norm2_w, w->norm2_b, nullptr, nullptr, nullptr, nullptr, nullptr, y, nullptr,
+                             nullptr, nullptr, nullptr, 0.f, 0, SITE_ATTN_OUT + L, SITE_FFN_HID + L, SITE_FFN_OUT + L,
+                             tp ? tp + plan::I_MLIVE : nullptr, nullptr, st, false);
 }
 
 extern "C" int rd_encoder_layer_bwd(const rd_shape* s, int32_t layer, const float* x, const uint8_t* mask,

@@ -23,8 +23,14 @@ per chunk:
   the whole token plan costs.  With the operator head the step enqueues the eager surface's head: in the padded layout the logits
   are bit-identical to `model.eval(); model.forward(...)`, on the plan they differ by the plan's summation orders at most
   (tests/test_eval_step_gpu.py has the measured figures).  Three small launches more per chunk than the fused head;
-* the forward kernels still write their save-for-backward buffers (DESIGN.md "EvalStep" has the share); skipping those writes is
-  the follow-up.
+* the forward is the INFERENCE forward of every stage (`rd_sensor_stage_fwd_infer` / `rd_beta_stage_fwd_infer`,
+  `rd_encoder_layer_fwd_infer`): save-free instantiations of the fused kernels where `rd_infer_covers` reports them (the P19 class),
+  the saving kernels elsewhere.  Nothing that only a backward reads is written, and `saved` shrinks to the forward's weight tiles
+  plus what one forward launch hands to the next (DESIGN.md "EvalStep" has the sizes and the timing).  The logits -- and `distance`
+  -- are bit-identical to the saving form, the training forward with its save-for-backward buffers, which `save_free=False` builds
+  (tests/test_infer_forward_gpu.py).  `feed.evaluate_captured` / `feed.validate` ask for the inference form; the CONSTRUCTOR's
+  default is the saving form, because tests/golden/step_launches.json records the launches of a default-constructed `EvalStep`
+  and that fixture is never regenerated: pass `save_free=True`.
 """
 import torch
 
@@ -34,19 +40,21 @@ from .step_beta import BetaSensorStage
 
 
 class EvalStep(Step):
-    """EvalStep(model, batch, token_plan=None, use_graph=True): the forward of `Raindrop_v2` -- default branch or `use_beta=True`,
+    """EvalStep(model, batch, token_plan=None, use_graph=True, save_free=False): the forward of `Raindrop_v2` -- default branch or `use_beta=True`,
     with or without `compute_distance` -- as one captured graph over reused input buffers (module docstring).
     `run()` -> `logits` [B, n_classes] (the step's own buffer: copy what must outlive the next run); `distance`: the structure
     distance of the last run (use_beta + compute_distance), else None.  `plan`: the token plan tensor or None (padded layout);
-    `head_fused`; `captures`: hipGraph captures made so far."""
+    `head_fused`; `captures`: hipGraph captures made so far.  save_free=True: the inference forward on buffers of the inference
+    sizes (module docstring; what `feed.validate` builds); False: the training forward and its save-for-backward buffers.  Same
+    logits bit for bit."""
 
-    def __init__(self, model, batch, token_plan=None, use_graph=True):
+    def __init__(self, model, batch, token_plan=None, use_graph=True, save_free=False):
         src = batch.get("src") if isinstance(batch, dict) else None
         if src is None or not torch.is_tensor(src) or not src.is_cuda:
             raise _lib.RaindropHipError("EvalStep needs a batch of ROCm device tensors (src, times, lengths[, static]); there is no "
                                         "CPU fallback")
         sensor = BetaSensorStage() if getattr(model, "use_beta", False) else SensorStage()
-        super().__init__(model, batch, sensor, has_backward=False, labels=False, token_plan=token_plan)
+        super().__init__(model, batch, sensor, has_backward=False, labels=False, token_plan=token_plan, save_free=save_free)
         self.graph, self.captures = None, 0
         if use_graph:
             self._with_cell(self._capture)

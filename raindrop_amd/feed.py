@@ -211,14 +211,15 @@ def evaluate_sharded(model, ds, chunk=2048, group=None):
 _EVAL_STEPS_MAX = 4       # captured forwards kept per model (each holds a chunk's activations); the oldest goes first
 
 
-def _eval_step(model, ds, B):
+def _eval_step(model, ds, B, save_free=True):
     """The cached `EvalStep` of this model for chunks of B samples of `ds`'s shape (one per distinct chunk size: a split has at
     most two, full chunks and the remainder).  Stale ones -- parameters moved, another arithmetic mode -- are rebuilt."""
     from .evalstep import EvalStep
     import os
     steps = model.__dict__.setdefault("_eval_steps", {})
     key = (int(B), int(ds.T), int(ds.W), int(ds.ds), str(ds.dev), int(_lib.load().rd_get_precision()),
-           os.environ.get("RD_TOKEN_PLAN", "1") != "0", bool(getattr(model, "use_beta", False)), bool(getattr(model, "compute_distance", False)))
+           os.environ.get("RD_TOKEN_PLAN", "1") != "0", bool(getattr(model, "use_beta", False)), bool(getattr(model, "compute_distance", False)),
+           bool(save_free))
     step = steps.get(key)
     if step is not None and step._param_ptrs() != step._ptrs:
         step = None
@@ -230,18 +231,18 @@ def _eval_step(model, ds, B):
         batch = dict(src=torch.zeros((ds.T, B, ds.W), **f32), times=torch.zeros((ds.T, B), **f32),
                      lengths=torch.zeros((B,), dtype=torch.int64, device=ds.dev),
                      static=torch.zeros((B, ds.ds), **f32) if ds.Pstatic is not None else None)
-        step = steps[key] = EvalStep(model, batch)
+        step = steps[key] = EvalStep(model, batch, save_free=save_free)
     return step
 
 
-def _evaluate_range(model, ds, lo, hi, chunk, out):
+def _evaluate_range(model, ds, lo, hi, chunk, out, save_free=True):
     """logits of samples [lo, hi) into out[: hi - lo], chunk by chunk through the cached captured forwards: the data is copied
     into a step's input buffers on the device, lengths are counted there (code/Raindrop.py:317), one graph replay per chunk."""
     if model.static and ds.Pstatic is None:
         raise _lib.RaindropHipError("evaluate_captured: the model has static features, the dataset has none")
     for a in range(lo, hi, chunk):
         b = min(hi, a + chunk)
-        step = _eval_step(model, ds, b - a)
+        step = _eval_step(model, ds, b - a, save_free)
         bt = step.batch
         bt["src"].copy_(ds.P[:, a:b])
         bt["times"].copy_(ds.Ptime[:, a:b])
@@ -252,12 +253,13 @@ def _evaluate_range(model, ds, lo, hi, chunk, out):
 
 
 @torch.no_grad()
-def evaluate_captured(model, ds, chunk=2048, group=None):
+def evaluate_captured(model, ds, chunk=2048, group=None, save_free=True):
     """`evaluate_chunked` (and, with a process group, `evaluate_sharded`: contiguous shards, logits all-gathered) with every chunk
     run as ONE hipGraph replay of a cached `raindrop_amd.evalstep.EvalStep` instead of one C-ABI call per operator: same
     contract, same [N, C] logits (bit-identical in the padded layout; on the token plan equal within the plan's documented
     logit bounds, tests/test_eval_step_gpu.py).  Dropout is off and the model's mode is not touched.  No host round trip per
-    chunk.  torch's gloo backend does not gather device tensors: with a group whose backend is not nccl the gather is staged
+    chunk.  save_free=False: the steps run the training forward with its save-for-backward buffers (A/B; same logits bit for bit).
+    torch's gloo backend does not gather device tensors: with a group whose backend is not nccl the gather is staged
     through the host."""
     import torch.distributed as dist
     C = int(model.n_classes)
@@ -265,13 +267,13 @@ def evaluate_captured(model, ds, chunk=2048, group=None):
         return torch.empty((0, 0), device=ds.dev)
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         out = torch.empty((ds.N, C), dtype=torch.float32, device=ds.dev)
-        _evaluate_range(model, ds, 0, ds.N, int(chunk), out)
+        _evaluate_range(model, ds, 0, ds.N, int(chunk), out, save_free)
         return out
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     per = (ds.N + world - 1) // world
     lo, hi = min(ds.N, rank * per), min(ds.N, (rank + 1) * per)
     mine = torch.zeros((per, C), dtype=torch.float32, device=ds.dev)          # equal-sized shards for the collective
-    _evaluate_range(model, ds, lo, hi, int(chunk), mine)
+    _evaluate_range(model, ds, lo, hi, int(chunk), mine, save_free)
     if dist.get_backend(group) == "nccl":
         parts = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(parts, mine, group=group)
@@ -283,21 +285,21 @@ def evaluate_captured(model, ds, chunk=2048, group=None):
 
 
 @torch.no_grad()
-def validate(model, ds, transform="sigmoid", chunk=2048, group=None):
+def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True):
     """The validation / test block of the reference's loop (`code/Raindrop.py:345-370,385-401`) without leaving the device until
     the end: `evaluate_captured` -> `transform` of the logits with torch ("sigmoid": validation, :349; "softmax": test, :388-389;
     None: the logits) -> `metrics.rank_metrics`, `metrics.confusion` and `rd_softmax_xent` on the TRANSFORMED scores (the
     reference's criterion(sigmoid(out), y), :352; None gives the plain cross entropy of the logits) -> ONE device-to-host copy.
     Ranking equals the reference's only under the same transform: it is the transform that produces the ties.
     Returns Python floats `auroc`, `auprc` (binary: column 1, what roc_auc_score(y, probs[:, 1]) gives; more classes: the
-    macro mean of the one-vs-rest values), `loss`, `accuracy`, `precision`, `recall`, `f1` (macro, over all n_classes classes) and
+    macro mean of the one-vs-rest values; save_free: as in `evaluate_captured`), `loss`, `accuracy`, `precision`, `recall`, `f1` (macro, over all n_classes classes) and
     numpy arrays `auroc_per_class`, `auprc_per_class`, `confusion` [C, C] (rows = true class).  `ds.y` is required."""
     from . import metrics
     if ds.y is None:
         raise _lib.RaindropHipError("validate needs the dataset's labels (DeviceDataset(..., y=...))")
     if transform not in ("sigmoid", "softmax", None):
         raise ValueError("transform must be 'sigmoid', 'softmax' or None")
-    logits = evaluate_captured(model, ds, chunk, group)
+    logits = evaluate_captured(model, ds, chunk, group, save_free=save_free)
     N, C = logits.shape
     scores = torch.sigmoid(logits) if transform == "sigmoid" else torch.softmax(logits, dim=1) if transform == "softmax" else logits
     scores = scores.contiguous()

@@ -19,7 +19,10 @@ How the host layer is laid out:
   `_head_fwd`, `_head_bwd`, `_enc_bwd_top`, `_enc_bwd_rest`, `_sensor_bwd`) and the table `Step.PARTS`, which says which stages
   make up each part a caller may enqueue or capture.  Every stage enqueues through the per-instance hook `_call`.
 * `has_backward` is a constructor-level fact: without it (raindrop_amd/evalstep.py) no gradient table, gradient buffer, backward
-  workspace, seed cell or trailing rider exists, and the head runs operator by operator up to the logits.
+  workspace, seed cell or trailing rider exists, and the head runs operator by operator up to the logits.  Such a step runs the
+  INFERENCE forward of every stage (`rd_sensor_stage_fwd_infer` / `rd_beta_stage_fwd_infer`, `rd_encoder_layer_fwd_infer`: the same
+  z, x and logits bit for bit, nothing written that only a backward reads) on buffers of the `rd_*_infer_bytes` sizes;
+  `save_free=False` keeps the training forward and its buffers (A/B, parity tests).
 * What differs between the default branch and `use_beta` sits in a sensor-stage object (`SensorStage` here, `BetaSensorStage` in
   raindrop_amd/step_beta.py): model validation, buffer sizes, extra buffers, the forward and the backward call, and whether
   rd_step_prepare's K1 weight tiles apply.
@@ -146,6 +149,8 @@ class SensorStage:
 
     def buffer_bytes(self, step):
         """(saved, workspace) bytes: the sizes of step.k1_saved / step.k1_ws (rd_msgpass_workspace_bytes is the backward's)"""
+        if step.infer:                                            # the weight tiles alone where rd_infer_covers says 1
+            return int(step.lib.rd_msgpass_infer_bytes(step.sp)), 0
         return (int(step.lib.rd_msgpass_saved_bytes(step.sp)),
                 int(step.lib.rd_msgpass_workspace_bytes(step.sp)) if step.has_backward else 0)
 
@@ -158,6 +163,10 @@ class SensorStage:
     def forward(self, s, st):
         b, P = s.batch, s.P
         W1, b1, W2, b2 = self._weights(P)
+        if s.infer:
+            return s._call("rd_sensor_stage_fwd_infer", s.sp, _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
+                           _p(W1), _p(b1), _p(W2), _p(b2), _p(s.graph_info["ssum"]), _p(s.z), _p(s.mask), _p(s.k1_saved),
+                           s.k1_saved.numel(), 1 if s.prep_k1 else 0, st)
         s._call("rd_sensor_stage_fwd_prepared" if s.prep_k1 else "rd_sensor_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]),
                 _p(b["lengths"]), _p(s.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2), _p(s.graph_info["ssum"]), s.p_drop,
                 s.seed, _p(s.z), _p(s.mask), _p(s.k1_saved), s.k1_saved.numel(), st)
@@ -234,11 +243,14 @@ class Step:
         "mb":    ("head_bwd", "enc_bwd_top", "enc_bwd_rest", "sensor_bwd"),
     }
 
-    def __init__(self, model, batch, sensor, flat=None, has_backward=True, labels=True, p_drop=None, seed=1234, token_plan=None):
+    def __init__(self, model, batch, sensor, flat=None, has_backward=True, labels=True, p_drop=None, seed=1234, token_plan=None,
+                 save_free=True):
         """sensor: the sensor-stage object of the model's branch.  has_backward=False: a forward-only step -- no gradient tables,
         no dx / dfeat / dhid / dlogits / loss / weight-gradient workspace, no backward workspaces, seed cell or trailing riders,
-        dropout off whatever model.training says, and the eager surface's head operator by operator."""
+        dropout off whatever model.training says, the eager surface's head operator by operator, and (save_free, the default) the
+        inference forward of every stage on buffers of the inference sizes.  save_free has no meaning with a backward."""
         self.model, self.flat, self.batch, self.sensor, self.has_backward = model, flat, batch, sensor, bool(has_backward)
+        self.infer = bool(save_free) and not self.has_backward
         self.dev = batch["src"].device
         self.lib = _lib.load()
         cfgp = float(model.dropout.p) if p_drop is None else float(p_drop)
@@ -301,6 +313,12 @@ class Step:
         self.nl = len(m.transformer_encoder.layers)
         k1_bytes = self.sensor.buffer_bytes(self)
         enc_saved, enc_ws = lib.rd_encoder_layer_saved_bytes(sp), lib.rd_encoder_layer_workspace_bytes(sp)
+        if self.infer:                                            # inference sizes; a covered layer does not touch its workspace
+            k1_cov, enc_cov = ctypes.c_int32(0), ctypes.c_int32(0)
+            _lib.call("rd_infer_covers", sp, ctypes.byref(k1_cov), ctypes.byref(enc_cov))
+            self.infer_covers = (bool(k1_cov.value), bool(enc_cov.value))
+            enc_saved = lib.rd_encoder_layer_infer_bytes(sp)
+            enc_ws = 0 if enc_cov.value else enc_ws
         self._arena = a = _Arena(self.dev, [T * B * D * 4] * (1 + self.nl + (2 if bwd else 0)) + list(k1_bytes)
                                  + [enc_saved] * self.nl + [enc_ws] * self.nl)
         grad = lambda shape: a.zeros(shape) if bwd else None
@@ -367,6 +385,11 @@ class Step:
 
     def _enc_fwd(self):
         for i in range(self.nl):
+            if self.infer:
+                self._call("rd_encoder_layer_fwd_infer", self.sp, i | (0x10000 if self.prep_enc else 0), _p(self.x[i]), _p(self.mask),
+                           ctypes.byref(self.enc_w[i]), _p(self.x[i + 1]), _p(self.enc_saved[i]), self.enc_saved[i].numel(),
+                           _p(self.enc_wss[i]), self.enc_wss[i].numel(), ops._stream())
+                continue
             self._call("rd_encoder_layer_fwd", self.sp, i | (0x10000 if self.prep_enc else 0), _p(self.x[i]), _p(self.mask),
                        ctypes.byref(self.enc_w[i]), self.p_drop, self.seed, _p(self.x[i + 1]), _p(self.enc_saved[i]),
                        self.enc_saved[i].numel(), _p(self.enc_wss[i]), self.enc_wss[i].numel(), ops._stream())

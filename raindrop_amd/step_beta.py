@@ -55,6 +55,8 @@ class BetaSensorStage(SensorStage):
     def buffer_bytes(self, step):
         """step.k1_saved / step.k1_ws are the use_beta stage's buffers (the forward uses the workspace, too)"""
         E = ctypes.c_int32(int(step.graph_info["edge_index"].shape[1]))
+        if step.infer:                                            # beta, p_t, kept; X .. y2 live in the workspace's backward scratch
+            return int(step.lib.rd_beta_stage_infer_bytes(step.sp, E)), int(step.lib.rd_beta_stage_workspace_bytes(step.sp, E))
         return int(step.lib.rd_beta_stage_saved_bytes(step.sp, E)), int(step.lib.rd_beta_stage_workspace_bytes(step.sp, E))
 
     def alloc(self, step):
@@ -77,6 +79,13 @@ class BetaSensorStage(SensorStage):
         b, P = s.batch, s.P
         l1, l2 = "ob_propagation.", "ob_propagation_layer2."
         drop = (self.pe1,) if self.edge_drop else ()
+        if s.infer:
+            return s._call("rd_beta_stage_fwd_infer", s.sp, _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
+                           _p(P[l1 + "lin_value.weight"]), _p(P[l1 + "lin_value.bias"]), _p(P[l1 + "increase_dim.weight"]),
+                           _p(P[l1 + "increase_dim.bias"]), _p(P[l1 + "map_weights"]), _p(P[l2 + "lin_value.weight"]),
+                           _p(P[l2 + "lin_value.bias"]), _p(self.ei), self.E, _p(self.ew), self.E, _p(s.z), _p(s.mask), _p(self.ei2),
+                           _p(self.alpha), _p(self.distance) if s.model.compute_distance else None, _p(s.k1_saved),
+                           s.k1_saved.numel(), _p(s.k1_ws), s.k1_ws.numel(), st)
         s._call("rd_beta_stage_fwd_dropout" if self.edge_drop else "rd_beta_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]),
                 _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
                 _p(P[l1 + "lin_value.weight"]), _p(P[l1 + "lin_value.bias"]), _p(P[l1 + "increase_dim.weight"]),
