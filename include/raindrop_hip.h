@@ -271,6 +271,43 @@ int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* R_u, const 
                    float* db1, float* dW2, float* db2, float* dR_u, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* ---- coefficient dropout on the default branch (code/Ob_propagation.py:195-196 with use_beta = False) ------------------------
+ * The reference calls each layer's operator once per sample and drops the post-softmax edge coefficients gamma [E,1] there: one
+ * keep decision per (sample b, layer l, edge e), shared by all channels.  The value a coefficient multiplies is the TARGET's own,
+ * so the layer's aggregate scale becomes
+ *     s_l[b,i] = sum over the edges e into i of keep[b,l,e] / (1 - p_l) * softmax_i(w)[e]      (0 for a node without in-edges)
+ * in place of ssum[i]:  Y1 = relu(X W1^T + b1) * s_1[b,f],  Y2 = relu(Y1 W2^T + b2) * s_2[b,f];  the backward's gates multiply by
+ * the same numbers (dZ2 = dz * s_2 * (Y2 > 0), dZ1 = (dZ2 W2) * s_1 * (Y1 > 0)); the edge weights are no parameters, so nothing
+ * else changes.
+ *  - rd_msgpass_coef_table: coef [2][B][N] fp32 in ONE launch (one wave per (row, target), fixed-order sums, no atomics).  Row
+ *    l * B + b is, bit for bit, row l * B + b of a 2B-row rd_edge_softmax_list_batched_dropout(batch_stride 0, w_bstride 0,
+ *    norm_row 1, p_drop = p_l, seed) on the shared list (edge_index rows `row_stride` apart) -- the same mask rule, under seed +
+ *    the registered seed cell (read when the kernel RUNS; the pointer is taken at enqueue); b is the sample's index in the CALLER's
+ *    batch, with or without a token plan.  A layer with p_l = 0 gets `ssum` (rd_edge_softmax's).  Capturable.
+ *  - the `_coef` entry points: their plain namesakes with the caller-owned table `coef` behind `ssum`; it is NOT part of `saved`
+ *    (rd_msgpass_saved_bytes does not change) and is handed to rd_msgpass_bwd_coef again.  The plain entry points behave as
+ *    coef == NULL.  The inference forward takes no table: evaluation never drops. */
+int rd_msgpass_coef_table(int32_t B, int32_t N, int32_t E, const int64_t* edge_index, int64_t row_stride,
+                          const float* edge_weights, const float* ssum, float p1, float p2, uint64_t seed, float* coef,
+                          void* stream);
+int rd_msgpass_fwd_coef(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                        const float* b1, const float* W2, const float* b2, const float* ssum, const float* coef,
+                        float p_drop, uint64_t seed, float* z, int32_t ldz, void* saved, size_t saved_bytes,
+                        void* stream);
+int rd_sensor_stage_fwd_coef(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                             const float* timescales, const float* R_u, const float* W1, const float* b1,
+                             const float* W2, const float* b2, const float* ssum, const float* coef, float p_drop,
+                             uint64_t seed, float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream);
+int rd_sensor_stage_fwd_prepared_coef(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                      const float* timescales, const float* R_u, const float* W1, const float* b1,
+                                      const float* W2, const float* b2, const float* ssum, const float* coef, float p_drop,
+                                      uint64_t seed, float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream);
+int rd_msgpass_bwd_coef(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                        const float* W2, const float* ssum, const float* coef, float p_drop, const void* saved,
+                        size_t saved_bytes, const float* z, const float* dz, int32_t ldz, float* dW1,
+                        float* db1, float* dW2, float* db2, float* dR_u, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- a15/a16: temporal self-attention encoder (kernels K2/K3) and masked mean (K5) --------- */
 
 /* Parameters of one nn.TransformerEncoderLayer(D, nhead, nhid) (code/models_rd.py:235-237),

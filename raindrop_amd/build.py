@@ -38,8 +38,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 #   (site, regex over the mangled kernel name, "step" | "x")   step: kernels of the P19 training step (RD_TOUCH_CODE: the WHOLE kernel);
 #   x: the kernels of the other configurations (RD_TOUCH_CODE_X: one length per template = its smallest instantiation).
 TOUCH_SITES = [
-    ("K1_FWD_P19", r"k_msg_fwd_fusedILi3ELi34ELi60ELb1E", "step"), ("K1_BWD_P19", r"k_msg_bwd_fusedILi3ELi34ELi60E", "step"),
-    ("K1_FWD", r"k_msg_fwd_fusedILi\dELi0ELi0ELb1E", "step"), ("K1_BWD", r"k_msg_bwd_fusedILi\dELi0E", "step"),
+    ("K1_FWD_P19", r"k_msg_fwd_fusedILi3ELi34ELi60ELb1ELb0E", "step"), ("K1_BWD_P19", r"k_msg_bwd_fusedILi3ELi34ELi60ELb0E", "step"),
+    ("K1_FWD", r"k_msg_fwd_fusedILi\dELi0ELi0ELb1ELb0E", "step"), ("K1_BWD", r"k_msg_bwd_fusedILi\dELi0ELi0ELb0E", "step"),
+    # the coefficient-dropout twins (template flag COEF): lengths of their own, so the plain instantiations keep theirs
+    ("K1_FWD_P19_C", r"k_msg_fwd_fusedILi3ELi34ELi60ELb1ELb1E", "step"), ("K1_BWD_P19_C", r"k_msg_bwd_fusedILi3ELi34ELi60ELb1E", "step"),
+    # (the runtime-shape twins share one length per direction, the smallest of three, like K1_FWD / K1_BWD: not whole-kernel sites)
+    ("K1_FWD_C", r"k_msg_fwd_fusedILi\dELi0ELi0ELb1ELb1E", "x"), ("K1_BWD_C", r"k_msg_bwd_fusedILi\dELi0ELi0ELb1E", "x"),
     ("ATTN_FWD", r"k_attn_fwd_fusedILi\d+ELi\d+ELb0ELb1E", "step"), ("ATTN_BWD", r"k_attn_bwd_fusedILi\d+ELi\d+ELb0E", "step"),
     ("ATTN_FWD_B", r"k_attn_fwd_fusedILi\d+ELi\d+ELb1ELb1E", "step"), ("ATTN_BWD_B", r"k_attn_bwd_fusedILi\d+ELi\d+ELb1E", "step"),
     ("EF_POST_P19L", r"k_enc_post_fwdILi152ELi272ELb1ELb0E", "step"), ("EF_POST_P19L_B", r"k_enc_post_fwdILi152ELi272ELb1ELb1E", "step"), ("EF_POST_P19", r"k_enc_post_fwdILi152ELi272ELb0ELb0E", "step"), ("EF_POST_P19_B", r"k_enc_post_fwdILi152ELi272ELb0ELb1E", "step"),
@@ -49,7 +53,7 @@ TOUCH_SITES = [
     ("EF_PRE_P12L", r"k_enc_pre_bwdILi160ELi288ELb1ELb0E", "step"), ("EF_PRE_P12L_B", r"k_enc_pre_bwdILi160ELi288ELb1ELb1E", "step"), ("EF_PRE_P12", r"k_enc_pre_bwdILi160ELi288ELb0ELb0E", "step"), ("EF_PRE_P12_B", r"k_enc_pre_bwdILi160ELi288ELb0ELb1E", "step"),
     ("EF_PRE_RTL", r"k_enc_pre_bwdILi0ELi0ELb1ELb0E", "step"), ("EF_PRE_RTL_B", r"k_enc_pre_bwdILi0ELi0ELb1ELb1E", "step"), ("EF_PRE_RT", r"k_enc_pre_bwdILi0ELi0ELb0ELb0E", "step"), ("EF_PRE_RT_B", r"k_enc_pre_bwdILi0ELi0ELb0ELb1E", "step"),
     # the save-free (inference) instantiations: kernels of the evaluation step, the whole kernel each
-    ("K1_INF_P19", r"k_msg_fwd_fusedILi3ELi34ELi60ELb0E", "step"), ("ATTN_INF", r"k_attn_fwd_fusedILi\d+ELi\d+ELb0ELb0E", "step"),
+    ("K1_INF_P19", r"k_msg_fwd_fusedILi3ELi34ELi60ELb0ELb0E", "step"), ("ATTN_INF", r"k_attn_fwd_fusedILi\d+ELi\d+ELb0ELb0E", "step"),
     ("ATTN_INF_B", r"k_attn_fwd_fusedILi\d+ELi\d+ELb1ELb0E", "step"),
     ("EF_INF_P19", r"k_enc_post_inferILi152ELi272ELb0E", "step"), ("EF_INF_P19_B", r"k_enc_post_inferILi152ELi272ELb1E", "step"),
     ("DW", r"4k_dwE", "step"), ("DW_REDUCE", r"k_dw_reduce", "step"), ("ADAM", r"6k_adamE", "step"), ("ADAM_DEV", r"10k_adam_devE", "step"),

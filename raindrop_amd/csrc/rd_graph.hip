@@ -163,6 +163,46 @@ __global__ __launch_bounds__(256) void k_edge_softmax_list(const int64_t* __rest
   if (lane == 0) ssum[n] = tot;
 }
 
+// Coefficient table of the default branch under coefficient dropout (code/Ob_propagation.py:195-196 with use_beta = False): the
+// value multiplied by the coefficients is the TARGET's own, so a layer's aggregate scale of target n in sample b is the sum of the
+// dropped-and-rescaled coefficients of the edges into n.  coef [2][B][N]; row r = l * B + b (layer l of sample b) IS row r of a
+// 2B-row k_edge_softmax_list launch on the shared list (strides 0) with p_drop = p_l -- the same loops, lane assignment, quad
+// index and fixed-order wave sums, so the two agree bit for bit --, and the plain ssum where p_l == 0.  One wave per (row, target).
+__global__ __launch_bounds__(256) void k_coef_table(const int64_t* __restrict__ idx, int E, const float* __restrict__ w, int N,
+                                                    const float* __restrict__ ssum, float* __restrict__ coef, int B, float p1, float p2,
+                                                    uint64_t seed, const uint64_t* cell) {
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (n >= N) return;
+  const float p_drop = (int)blockIdx.y < B ? p1 : p2;          // block-uniform
+  coef += (long)blockIdx.y * N;
+  if (!(p_drop > 0.f)) {
+    if (lane == 0) coef[n] = ssum[n];
+    return;
+  }
+  const uint64_t seed_eff = eff_seed(seed, cell);
+  const float inv_keep = 1.0f / (1.0f - p_drop);
+  float m = -INFINITY;
+  for (int e = lane; e < E; e += 64)
+    if (idx[e] == n) m = fmaxf(m, w[e]);
+  m = wave_max(m);
+  float den = 0.f;
+  for (int e = lane; e < E; e += 64)
+    if (idx[e] == n) den += expf(w[e] - m);
+  den = wave_sum(den) + 1e-16f;
+  float tot = 0.f;
+  for (int e = lane; e < E; e += 64)
+    if (idx[e] == n) {
+      float g = expf(w[e] - m) / den;
+      const float4 u = uniform4(seed_eff, SITE_EDGE_COEFF, (uint64_t)blockIdx.y * ((uint64_t)(E + 3) >> 2) + (uint64_t)(e >> 2));
+      const float ue = (e & 3) == 0 ? u.x : (e & 3) == 1 ? u.y : (e & 3) == 2 ? u.z : u.w;
+      g = ue >= p_drop ? g * inv_keep : 0.f;
+      tot += g;
+    }
+  tot = wave_sum(tot);
+  if (lane == 0) coef[n] = tot;
+}
+
 // dense coefficient matrix of an edge list: G[j*N + i] = sum of gamma_e over the edges (j -> i), duplicates added in EDGE ORDER
 // (the scatter-add of code/transformer_conv.py:205 via PyG aggregate, made deterministic).  One wavefront per target i; the edge
 // list is walked by the whole wave (uniform loads), the lane that owns source j = src % 64 adds into its LDS row slot.
@@ -277,6 +317,21 @@ extern "C" int rd_edge_softmax_list_batched_dropout(int32_t B, int32_t N, int32_
                      edge_index + (long)norm_row * row_stride, E, edge_weights, N, gamma_e, ssum, (long)batch_stride, (long)w_bstride,
                      p_drop, seed, p_drop > 0.f ? seed_cell() : nullptr);
   return check_launch("k_edge_softmax_list");
+}
+
+// coef [2][B][N] of the default branch's coefficient dropout (k_coef_table): layer l's rows under p_l; capturable, the registered
+// seed cell travels as a kernel argument like at every other site
+extern "C" int rd_msgpass_coef_table(int32_t B, int32_t N, int32_t E, const int64_t* edge_index, int64_t row_stride,
+                                     const float* edge_weights, const float* ssum, float p1, float p2, uint64_t seed, float* coef,
+                                     void* stream) {
+  RD_REQUIRE(B >= 0 && N > 0 && E >= 0, "bad B=%d N=%d E=%d", B, N, E);
+  RD_REQUIRE(p1 >= 0.f && p1 < 1.f && p2 >= 0.f && p2 < 1.f, "p1, p2 must be in [0,1)");
+  if (B == 0) return RD_OK;
+  RD_REQUIRE(2 * (long)B <= 65535, "2 B = %ld exceeds the grid's y extent", 2 * (long)B);
+  RD_REQUIRE(edge_index && edge_weights && ssum && coef, "NULL tensor");
+  hipLaunchKernelGGL(k_coef_table, dim3(cdiv(N, 4), 2 * B), dim3(256), 0, (hipStream_t)stream, edge_index + row_stride, E,
+                     edge_weights, N, ssum, coef, B, p1, p2, seed, seed_cell());
+  return check_launch("k_coef_table");
 }
 
 extern "C" int rd_edge_gamma_dense(int32_t N, int32_t E, const int64_t* edge_index, int64_t row_stride, const float* gamma_e,

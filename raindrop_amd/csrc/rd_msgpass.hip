@@ -29,11 +29,13 @@ int fused_wprep(const k1::Layout& L, const float* W1, const float* W2, void* wt,
 int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, const float* b1, const float* b2,
                       const float* ssum, const void* wt, float p_drop, uint64_t seed, void* tpX, void* tpY1,
                       void* m1, void* m2, void* mx, float* z, int ldz, hipStream_t st, const float* times,
-                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save = true);
+                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save = true,
+                      const float* coef = nullptr);
 bool fused_msgpass_infer_ok(const rd_shape* s);
 int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, const void* wt, float p_drop,
                       const void* m1, const void* m2, const void* mx, const float* dz, int ldz, void* tpD1, void* tpD2,
-                      void* ones, float* rupart, hipStream_t st, const void* tpX = nullptr, const void* tpY1 = nullptr);
+                      void* ones, float* rupart, hipStream_t st, const void* tpX = nullptr, const void* tpY1 = nullptr,
+                      const float* coef = nullptr);
 int fused_dw(const k1::Layout& L, const k1::DwPlan& P, const void* tpX, const void* tpY1, const void* tpD1,
              const void* tpD2, const void* ones, float* part, const float* rupart, float* dW1, float* db1, float* dW2, float* db2,
              float* dRu, hipStream_t st);
@@ -74,15 +76,18 @@ __global__ __launch_bounds__(256) void k_obs_embed(const float* __restrict__ src
   }
 }
 
-// dz2[b,f,t*d+c] = dz[t,b,f*d+c] * ssum[f] * (z[t,b,f*d+c] > 0)
-// (backward of `out * gamma` + scatter-add + ReLU of layer 2, read through the [T,B,ldz] layout).
+// dz2[b,f,t*d+c] = dz[t,b,f*d+c] * ssum[b*sstride + f] * (z[t,b,f*d+c] > 0)
+// (backward of `out * gamma` + scatter-add + ReLU of layer 2, read through the [T,B,ldz] layout).  sstride = 0: the shared ssum[f];
+// F: layer 2's rows of the coefficient-dropout table (rd_msgpass_bwd_coef).
 __global__ __launch_bounds__(256) void k_msg_dz2(const float* __restrict__ dz,
                                                  const float* __restrict__ z,
                                                  const float* __restrict__ ssum,
                                                  float* __restrict__ dz2, int B, int T, int F, int d,
-                                                 long ldz, const int32_t* __restrict__ sp_row0, const int32_t* __restrict__ sp_len) {
+                                                 long ldz, const int32_t* __restrict__ sp_row0, const int32_t* __restrict__ sp_len,
+                                                 int sstride) {
   const int b = blockIdx.x;
   const int Fd = F * d;
+  ssum += (long)b * sstride;
   const long total = (long)T * Fd;
   // token plan: sample b's step t lives at row sp_row0[b] + t of z / dz; steps >= sp_len[b] have no row and a zero gradient
   const long row0 = sp_row0 ? sp_row0[b] : b;
@@ -269,10 +274,12 @@ extern "C" size_t rd_msgpass_saved_bytes(const rd_shape* s) {
   return n;
 }
 
-extern "C" int rd_msgpass_fwd(const rd_shape* s, const float* src, const float* R_u, const float* W1,
-                              const float* b1, const float* W2, const float* b2, const float* ssum,
-                              float p_drop, uint64_t seed, float* z, int32_t ldz, void* saved,
-                              size_t saved_bytes, void* stream) {
+// coef (null: none): the per-(layer, sample, sensor) aggregate coefficients [2][B][F] of the coefficient dropout
+// (rd_msgpass_coef_table) in place of ssum[f] -- graph row b*F + f of layer l scales by coef[l*B*F + b*F + f]
+static int msgpass_fwd_impl(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                            const float* b1, const float* W2, const float* b2, const float* ssum, const float* coef,
+                            float p_drop, uint64_t seed, float* z, int32_t ldz, void* saved,
+                            size_t saved_bytes, void* stream) {
   int rc = check_shape(s);
   if (rc) return rc;
   if (s->B == 0) return RD_OK;                       // empty batch
@@ -290,7 +297,7 @@ extern "C" int rd_msgpass_fwd(const rd_shape* s, const float* src, const float* 
     RD_REQUIRE(saved_bytes >= fv.bytes, "saved buffer too small: %zu < %zu", saved_bytes, fv.bytes);
     if ((rc = fused_wprep(L, W1, W2, fv.wt, st))) return rc;
     return fused_msgpass_fwd(L, src, R_u, b1, b2, ssum, fv.wt, p_drop, seed, fv.tpX, fv.tpY1, fv.m1, fv.m2, fv.mx, z, ldz,
-                             st, nullptr, nullptr, nullptr, nullptr, 0);
+                             st, nullptr, nullptr, nullptr, nullptr, 0, true, coef);
   }
   // token plan on the unfused path (round 4): the products run on all B*F graph rows as before -- lin_value mixes ALL of a
   // sensor's time steps, observed ones past `lengths` included -- only the last product's scatter follows the plan: step t of
@@ -316,12 +323,28 @@ extern "C" int rd_msgpass_fwd(const rd_shape* s, const float* src, const float* 
   if (tiles) { g.Btiles = v.wt[0]; g.bt_ntile = v.ntile; g.bt_nkc = v.nkc; }
   g.C = y1save; g.sc_m = K;
   g.bias = b1; g.relu = 1; g.rowscale = ssum; g.rs_period = F;
+  if (coef) { g.rowscale = coef; g.rs_period = M; }       // row b*F + f of layer 1
   if ((rc = launch_gemm(g, st))) return rc;
   g.A = y1save; g.B = W2; g.bias = b2;
+  if (coef) g.rowscale = coef + (size_t)M;                 // layer 2's rows
   if (tiles) g.Btiles = v.wt[1];
   g.C = z; g.scatter = 1; g.sB = B; g.sF = F; g.sd = d; g.ldz = ldz;
   if (tp) { g.sp_row0 = tp + plan::brow_base(B, T); g.sp_len = tp + plan::blen_base(B, T); }
   return launch_gemm(g, st);
+}
+
+extern "C" int rd_msgpass_fwd(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                              const float* b1, const float* W2, const float* b2, const float* ssum,
+                              float p_drop, uint64_t seed, float* z, int32_t ldz, void* saved,
+                              size_t saved_bytes, void* stream) {
+  return msgpass_fwd_impl(s, src, R_u, W1, b1, W2, b2, ssum, nullptr, p_drop, seed, z, ldz, saved, saved_bytes, stream);
+}
+extern "C" int rd_msgpass_fwd_coef(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                                   const float* b1, const float* W2, const float* b2, const float* ssum, const float* coef,
+                                   float p_drop, uint64_t seed, float* z, int32_t ldz, void* saved,
+                                   size_t saved_bytes, void* stream) {
+  RD_REQUIRE(!s || s->B == 0 || coef, "NULL coefficient table");
+  return msgpass_fwd_impl(s, src, R_u, W1, b1, W2, b2, ssum, coef, p_drop, seed, z, ldz, saved, saved_bytes, stream);
 }
 
 // PE + padding mask + message passing in one call: on the fused path ONE launch (plus the weight
@@ -329,7 +352,8 @@ extern "C" int rd_msgpass_fwd(const rd_shape* s, const float* src, const float* 
 static int sensor_stage_fwd_impl(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
                                  const float* timescales, const float* R_u, const float* W1, const float* b1,
                                  const float* W2, const float* b2, const float* ssum, float p_drop, uint64_t seed,
-                                 float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream, bool prepared) {
+                                 float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream, bool prepared,
+                                 const float* coef = nullptr) {
   int rc = check_shape(s);
   if (rc) return rc;
   if (s->B == 0) return RD_OK;
@@ -345,10 +369,10 @@ static int sensor_stage_fwd_impl(const rd_shape* s, const float* src, const floa
     hipStream_t st = (hipStream_t)stream;
     if (!prepared && (rc = fused_wprep(L, W1, W2, fv.wt, st))) return rc;
     return fused_msgpass_fwd(L, src, R_u, b1, b2, ssum, fv.wt, p_drop, seed, fv.tpX, fv.tpY1, fv.m1, fv.m2, fv.mx, z, ldz,
-                             st, times, lengths, timescales, mask, s->d_pe);
+                             st, times, lengths, timescales, mask, s->d_pe, true, coef);
   }
   if ((rc = rd_pe_mask(s, times, lengths, timescales, z, mask, stream))) return rc;
-  return rd_msgpass_fwd(s, src, R_u, W1, b1, W2, b2, ssum, p_drop, seed, z, ldz, saved, saved_bytes, stream);
+  return msgpass_fwd_impl(s, src, R_u, W1, b1, W2, b2, ssum, coef, p_drop, seed, z, ldz, saved, saved_bytes, stream);
 }
 
 extern "C" int rd_sensor_stage_fwd(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
@@ -365,6 +389,25 @@ extern "C" int rd_sensor_stage_fwd_prepared(const rd_shape* s, const float* src,
                                             float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream) {
   return sensor_stage_fwd_impl(s, src, times, lengths, timescales, R_u, W1, b1, W2, b2, ssum, p_drop, seed, z, mask, saved, saved_bytes,
                                stream, true);
+}
+
+// the two with the coefficient-dropout table coef [2][B][F] (rd_msgpass_coef_table; caller-owned, handed to rd_msgpass_bwd_coef too)
+extern "C" int rd_sensor_stage_fwd_coef(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                        const float* timescales, const float* R_u, const float* W1, const float* b1,
+                                        const float* W2, const float* b2, const float* ssum, const float* coef, float p_drop,
+                                        uint64_t seed, float* z, uint8_t* mask, void* saved, size_t saved_bytes, void* stream) {
+  RD_REQUIRE(!s || s->B == 0 || coef, "NULL coefficient table");
+  return sensor_stage_fwd_impl(s, src, times, lengths, timescales, R_u, W1, b1, W2, b2, ssum, p_drop, seed, z, mask, saved, saved_bytes,
+                               stream, false, coef);
+}
+extern "C" int rd_sensor_stage_fwd_prepared_coef(const rd_shape* s, const float* src, const float* times, const int64_t* lengths,
+                                                 const float* timescales, const float* R_u, const float* W1, const float* b1,
+                                                 const float* W2, const float* b2, const float* ssum, const float* coef,
+                                                 float p_drop, uint64_t seed, float* z, uint8_t* mask, void* saved,
+                                                 size_t saved_bytes, void* stream) {
+  RD_REQUIRE(!s || s->B == 0 || coef, "NULL coefficient table");
+  return sensor_stage_fwd_impl(s, src, times, lengths, timescales, R_u, W1, b1, W2, b2, ssum, p_drop, seed, z, mask, saved, saved_bytes,
+                               stream, true, coef);
 }
 
 // ---- inference forward: nothing that only a backward reads is written (include/raindrop_hip.h "inference forward") -------------
@@ -413,11 +456,11 @@ int k1_weight_split_specs(const rd_shape* s, const float* W1, const float* W2, v
 }
 }  // namespace rd
 
-extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1,
-                              const float* W2, const float* ssum, float p_drop, const void* saved,
-                              size_t saved_bytes, const float* z, const float* dz, int32_t ldz,
-                              float* dW1, float* db1, float* dW2, float* db2, float* dR_u,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+static int msgpass_bwd_impl(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                            const float* W2, const float* ssum, const float* coef, float p_drop, const void* saved,
+                            size_t saved_bytes, const float* z, const float* dz, int32_t ldz,
+                            float* dW1, float* db1, float* dW2, float* db2, float* dR_u,
+                            void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_shape(s);
   if (rc) return rc;
   RD_REQUIRE(dW1 && db1 && dW2 && db2 && dR_u, "NULL gradient output");
@@ -451,7 +494,7 @@ extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* 
     RD_REQUIRE(saved_bytes >= fv.bytes, "saved buffer too small");
     FusedWs fw = carve_fused_ws(L, P, workspace);
     RD_REQUIRE(workspace && workspace_bytes >= fw.bytes, "workspace too small: %zu < %zu", workspace_bytes, fw.bytes);
-    if ((rc = fused_msgpass_bwd(L, src, ssum, fv.wt, p_drop, fv.m1, fv.m2, fv.mx, dz, ldz, fw.tpD1, fw.tpD2, fw.ones, fw.rupart, st, fv.tpX, fv.tpY1)))
+    if ((rc = fused_msgpass_bwd(L, src, ssum, fv.wt, p_drop, fv.m1, fv.m2, fv.mx, dz, ldz, fw.tpD1, fw.tpD2, fw.ones, fw.rupart, st, fv.tpX, fv.tpY1, coef)))
       return rc;
     return fused_dw(L, P, fv.tpX, fv.tpY1, fw.tpD1, fw.tpD2, fw.ones, fw.part, fw.rupart, dW1, db1, dW2, db2, dR_u, st);
   }
@@ -463,8 +506,8 @@ extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* 
   {
     const long per = (long)F * K;
     int gy = (int)((per + 255) / 256); if (gy > 64) gy = 64;
-    hipLaunchKernelGGL(k_msg_dz2, dim3(B, gy), dim3(256), 0, st, dz, z, ssum, w.dz2, B, T, F, d, (long)ldz,
-                       tp ? tp + plan::brow_base(B, T) : nullptr, tp ? tp + plan::blen_base(B, T) : nullptr);
+    hipLaunchKernelGGL(k_msg_dz2, dim3(B, gy), dim3(256), 0, st, dz, z, coef ? coef + (size_t)M : ssum, w.dz2, B, T, F, d, (long)ldz,
+                       tp ? tp + plan::brow_base(B, T) : nullptr, tp ? tp + plan::blen_base(B, T) : nullptr, coef ? F : 0);
     if ((rc = check_launch("k_msg_dz2"))) return rc;
   }
   // dz1 = (dz2 W2) * ssum[f] * (y1 > 0)
@@ -476,6 +519,7 @@ extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* 
   if (tiles) { g.Btiles = sv.wt[2]; g.bt_ntile = sv.ntile; g.bt_nkc = sv.nkc; }
   g.C = w.dz1; g.sc_m = K;
   g.rowscale = ssum; g.rs_period = F; g.posmask = y1save; g.pm_m = K;
+  if (coef) { g.rowscale = coef; g.rs_period = M; }       // layer 1's rows of the table
   if ((rc = launch_gemm(g, st))) return rc;
   // dx = dz1 W1
   GemmArgs h{};
@@ -506,6 +550,25 @@ extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* 
   }
   if ((rc = launch_wgrad2(M, K, K, w.dz2, y1save, dW2, db2, w.dz1, xsave, dW1, db1, w.splitk, st))) return rc;
   return RD_OK;
+}
+
+extern "C" int rd_msgpass_bwd(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                              const float* W2, const float* ssum, float p_drop, const void* saved,
+                              size_t saved_bytes, const float* z, const float* dz, int32_t ldz,
+                              float* dW1, float* db1, float* dW2, float* db2, float* dR_u,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  return msgpass_bwd_impl(s, src, R_u, W1, W2, ssum, nullptr, p_drop, saved, saved_bytes, z, dz, ldz, dW1, db1, dW2, db2, dR_u, workspace,
+                          workspace_bytes, stream);
+}
+// backward of the `_coef` forwards: `coef` is the table the forward was given (the gates multiply by the same numbers)
+extern "C" int rd_msgpass_bwd_coef(const rd_shape* s, const float* src, const float* R_u, const float* W1,
+                                   const float* W2, const float* ssum, const float* coef, float p_drop, const void* saved,
+                                   size_t saved_bytes, const float* z, const float* dz, int32_t ldz,
+                                   float* dW1, float* db1, float* dW2, float* db2, float* dR_u,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+  RD_REQUIRE(!s || s->B == 0 || coef, "NULL coefficient table");
+  return msgpass_bwd_impl(s, src, R_u, W1, W2, ssum, coef, p_drop, saved, saved_bytes, z, dz, ldz, dW1, db1, dW2, db2, dR_u, workspace,
+                          workspace_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -101,6 +101,7 @@ struct FusedArgs {
   unsigned long long* stamps;    // debug: per-phase clock64() of every wave of the first 4 workgroups
   const int32_t* plan;           // token plan (rd_plan.h) or null: which steps of a sample are live, and where its z rows are
   int* lin;                      // [B] per slot: 1 + last step with a non-zero observation (fwd writes, bwd reads)
+  const float* coef;             // COEF instantiations: [2][B][F] per-(layer, sample, sensor) aggregate coefficients in place of ssum[f]
 };
 
 // Which sample a workgroup owns and where its rows live.  Padded layout (no plan): workgroup i = sample i, every step is
@@ -500,10 +501,16 @@ __device__ __forceinline__ void tstore_leftover_planes(const __bf16* Ph, const _
 // SAVE = false (rd_sensor_stage_fwd_infer; compiled for the P19 shape only, other shapes keep the saving form: rd_infer_covers): the same forward without what only a backward reads -- the row tiles of
 // X and Y1, the three gate tensors, the per-sample `lin` and the plan's slack cell.  Every operation that reaches z is the same, in
 // the same order: z, the PE columns and the mask are bit-identical.  An instantiation, not a flag (DESIGN rule 40).
-template <int RT, int FC, int TC, bool SAVE = true>
+// COEF = true (coefficient dropout on the default branch, rd_sensor_stage_fwd_coef): the aggregate scale is a per-(layer, sample,
+// sensor) table (a.coef [2][B][F], k_coef_table) instead of the shared ssum[f] -- the workgroup stages ITS sample's two rows
+// (indexed by the caller's sample index b, not the plan's rank) and each layer's epilogue reads its own.  An instantiation, not a
+// flag (DESIGN rule 40); the save-free form has no such twin (evaluation never drops).
+template <int RT, int FC, int TC, bool SAVE = true, bool COEF = false>
 __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  RD_TOUCH_CODE(!SAVE ? RD_TL_K1_INF_P19 : FC == 34 && TC == 60 ? RD_TL_K1_FWD_P19 : RD_TL_K1_FWD);   // own code -> L2 (rd_common.h)
+  static_assert(SAVE || !COEF, "the save-free forward never drops coefficients");
+  RD_TOUCH_CODE(!SAVE ? RD_TL_K1_INF_P19 : COEF ? (FC == 34 && TC == 60 ? RD_TL_K1_FWD_P19_C : RD_TL_K1_FWD_C)
+                      : FC == 34 && TC == 60 ? RD_TL_K1_FWD_P19 : RD_TL_K1_FWD);   // own code -> L2 (rd_common.h)
   constexpr int ROWS = RT * 16;
   constexpr size_t PLANES = (size_t)4 * ROWS * LDX * sizeof(__bf16);
   __bf16* Xh = reinterpret_cast<__bf16*>(smem_raw);
@@ -511,8 +518,9 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   __bf16* Yh = Xl + ROWS * LDX;
   __bf16* Yl = Yh + ROWS * LDX;
   float* Ys = reinterpret_cast<float*>(smem_raw);        // fp32 [F][LDS_F] staging of Y2, aliases the X planes (F * 976 <= 2 * ROWS * 512)
-  float* Ss = reinterpret_cast<float*>(smem_raw + PLANES);   // [ROWS]: ssum (0 beyond F)
-  int* LinW = reinterpret_cast<int*>(Ss + ROWS);          // [NWAVE] per-wave "1 + last observed step"
+  float* Ss = reinterpret_cast<float*>(smem_raw + PLANES);   // [ROWS]: ssum (0 beyond F); COEF: [2][ROWS], the sample's row of each layer
+  float* Ss2 = Ss + (COEF ? ROWS : 0);                    // layer 2's coefficients
+  int* LinW = reinterpret_cast<int*>(Ss2 + ROWS);         // [NWAVE] per-wave "1 + last observed step"
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool grpB = __builtin_amdgcn_readfirstlane(wave) >= GWAVE;       // scalar: the group branches are real branches
   const int gt = tid & (GTHR - 1), gw = __builtin_amdgcn_readfirstlane(wave) & (GWAVE - 1);   // index inside the group
@@ -534,7 +542,12 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   Panel pw;
   float sfv = 0.f;                                       // ssum -> LDS (last wave; the epilogues read their rows' coefficients there)
   const int sfi = tid - (NTHR - 64);
-  if (sfi >= 0 && sfi < F) sfv = a.ssum[sfi];
+  [[maybe_unused]] float sfv2 = 0.f;
+  if constexpr (COEF) {
+    if (sfi >= 0 && sfi < F) { sfv = a.coef[m24(b, F) + sfi]; sfv2 = a.coef[m24(B + b, F) + sfi]; }
+  } else {
+    if (sfi >= 0 && sfi < F) sfv = a.ssum[sfi];
+  }
   float4 bias1[NJ], bias2[NJ];                           // both layers' biases of the lane's four columns: ahead of the weight stream
 #pragma unroll
   for (int jj = 0; jj < NJ; ++jj) {
@@ -622,6 +635,9 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   }
   if (lane == 0) LinW[wave] = lin_w;
   if (sfi >= 0 && sfi < ROWS) { pin(sfv); Ss[sfi] = sfv; }
+  if constexpr (COEF) {
+    if (sfi >= 0 && sfi < ROWS) { pin(sfv2); Ss2[sfi] = sfv2; }
+  }
   RD_STAMP(1);
   lds_barrier();
   RD_STAMP(2);
@@ -712,7 +728,7 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
   zero_acc<RT>(acc);
   if (live2) mma_panel<RT>(acc, Yh, Yl, pw, lane);
   RD_STAMP(6);
-  load_srow<RT>(srow, Ss, lane);
+  load_srow<RT>(srow, Ss2, lane);
 #pragma unroll
   for (int jj = 0; jj < NJ; ++jj) {
     const int j = wave + NWAVE * jj;
@@ -756,10 +772,13 @@ __global__ __launch_bounds__(NTHR) void k_msg_fwd_fused(FusedArgs a) {
 // The weight gradients dW_l = dZ_l^T In_l reduce over all B*F rows: rd_msgpass_dw.hip.
 // Same two-group schedule as the forward kernel.
 // ------------------------------------------------------------------------------------------------
-template <int RT, int FC, int TC>
+// COEF = true (rd_msgpass_bwd_coef): the gates multiply by the forward's table -- dZ2 = dz * coef[1][b][f] * (Y2 > 0) in the
+// gather, dZ1 = (dZ2 W2) * coef[0][b][f] * (Y1 > 0) from the row staged in LDS -- the same numbers the forward multiplied by.
+template <int RT, int FC, int TC, bool COEF = false>
 __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  RD_TOUCH_CODE(FC == 34 && TC == 60 ? RD_TL_K1_BWD_P19 : RD_TL_K1_BWD);   // own code -> L2 (rd_common.h)
+  RD_TOUCH_CODE(COEF ? (FC == 34 && TC == 60 ? RD_TL_K1_BWD_P19_C : RD_TL_K1_BWD_C)
+                     : FC == 34 && TC == 60 ? RD_TL_K1_BWD_P19 : RD_TL_K1_BWD);   // own code -> L2 (rd_common.h)
   constexpr int ROWS = RT * 16;
   constexpr size_t PLANES = (size_t)4 * ROWS * LDX * sizeof(__bf16);
   __bf16* Dh = reinterpret_cast<__bf16*>(smem_raw);
@@ -767,7 +786,7 @@ __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
   __bf16* Eh = Dl + ROWS * LDX;
   __bf16* El = Eh + ROWS * LDX;
   float* Sx = reinterpret_cast<float*>(Dh);              // fp32 [F][LDS_F] staging tile of dX, aliases the D planes (dead by then)
-  float* Ss = reinterpret_cast<float*>(smem_raw + PLANES);                    // [ROWS]: ssum (0 beyond F)
+  float* Ss = reinterpret_cast<float*>(smem_raw + PLANES);                    // [ROWS]: ssum (0 beyond F); COEF: the sample's layer-1 row
   float* Rp = reinterpret_cast<float*>(Eh);              // dR_u partial sums [groups][F*4], aliases the E planes (dead by then)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool grpB = __builtin_amdgcn_readfirstlane(wave) >= GWAVE;       // scalar: the group branches are real branches
@@ -825,7 +844,8 @@ __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
       if (vec4) dd[u] = *reinterpret_cast<const float4*>(p);
       else dd[u] = make_float4(p[0], p[1], p[2], p[3]);
       gb[u] = a.m2[(size_t)(m24(sb, total) + m24(tl, F) + gfi[u])];      // the cell's gate byte (the forward's scatter wrote it in this order)
-      gs[u] = a.ssum[gfi[u]];
+      if constexpr (COEF) gs[u] = a.coef[m24(B + b, F) + gfi[u]];          // layer 2's coefficient of (sample b, sensor f)
+      else gs[u] = a.ssum[gfi[u]];
     }
   };
   auto gather_consume = [&]() {
@@ -843,7 +863,11 @@ __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
     }
   };
   float sfv = 0.f;
-  if (tid >= NTHR - 64 && tid - (NTHR - 64) < F) sfv = a.ssum[tid - (NTHR - 64)];      // last wave: ssum -> LDS (the epilogue's coefficients)
+  if constexpr (COEF) {
+    if (tid >= NTHR - 64 && tid - (NTHR - 64) < F) sfv = a.coef[m24(b, F) + tid - (NTHR - 64)];   // last wave: layer 1's row -> LDS
+  } else {
+    if (tid >= NTHR - 64 && tid - (NTHR - 64) < F) sfv = a.ssum[tid - (NTHR - 64)];      // last wave: ssum -> LDS (the epilogue's coefficients)
+  }
   if (!(RD_ABL & 16)) gather_issue(tid);
   if (!RD_K1_ALATE && (!RD_K1_BLATE || !grpB)) load_panel(pw, wtiles(a, dm, 1, 1), nct, wave, lane);          // W2^T panel queues behind the gather
   // the gate masks Y1 > 0 of this wave's column tile: requested under the gather's latency
@@ -991,16 +1015,17 @@ __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
   }
 }
 
-template <int RT, int FC, int TC>
+template <int RT, int FC, int TC, bool COEF = false>
 int launch_fused(const FusedArgs& a, bool bwd, hipStream_t st) {
-  const size_t lds = (size_t)4 * RT * 16 * LDX * sizeof(__bf16) + (size_t)RT * 16 * sizeof(float) + (size_t)NWAVE * sizeof(int);   // planes, ssum, LinW (forward)
+  const size_t lds = (size_t)4 * RT * 16 * LDX * sizeof(__bf16) + (size_t)(COEF ? 2 : 1) * RT * 16 * sizeof(float) +
+                     (size_t)NWAVE * sizeof(int);   // planes, ssum (COEF: the two coefficient rows), LinW (forward)
   if (!bwd) {
-    RD_LDS_ATTR((k_msg_fwd_fused<RT, FC, TC>), lds);
-    hipLaunchKernelGGL((k_msg_fwd_fused<RT, FC, TC>), dim3(a.B), dim3(NTHR), lds, st, a);
+    RD_LDS_ATTR((k_msg_fwd_fused<RT, FC, TC, true, COEF>), lds);
+    hipLaunchKernelGGL((k_msg_fwd_fused<RT, FC, TC, true, COEF>), dim3(a.B), dim3(NTHR), lds, st, a);
     return check_launch("k_msg_fwd_fused");
   }
-  RD_LDS_ATTR((k_msg_bwd_fused<RT, FC, TC>), lds);
-  hipLaunchKernelGGL((k_msg_bwd_fused<RT, FC, TC>), dim3(a.B), dim3(NTHR), lds, st, a);
+  RD_LDS_ATTR((k_msg_bwd_fused<RT, FC, TC, COEF>), lds);
+  hipLaunchKernelGGL((k_msg_bwd_fused<RT, FC, TC, COEF>), dim3(a.B), dim3(NTHR), lds, st, a);
   return check_launch("k_msg_bwd_fused");
 }
 
@@ -1023,9 +1048,19 @@ int launch_fused_shape(const FusedArgs& a, const k1::Layout& L, bool bwd, hipStr
   const char* e = getenv("RD_K1_SPECIALIZE");
   const bool model_layout = a.ldz == 4 * L.F + 16 && (bwd || a.times == nullptr || a.d_pe == 16);
   if (!save) {
+    if (a.coef) return fail(RD_EUNSUPPORTED, "fused message passing: the save-free forward takes no coefficient table");
     if (bwd || !(L.F == 34 && L.T == 60 && model_layout && k1_specialize_on()))
       return fail(RD_EUNSUPPORTED, "fused message passing: no save-free instantiation for this shape");
     return launch_fused_infer(a, st);
+  }
+  if (a.coef) {                                        // coefficient dropout: the COEF instantiations, same shape dispatch
+    if (L.F == 34 && L.T == 60 && model_layout && !(e && atoi(e) == 0)) return launch_fused<3, 34, 60, true>(a, bwd, st);
+    switch (L.RT) {
+      case 1: return launch_fused<1, 0, 0, true>(a, bwd, st);
+      case 2: return launch_fused<2, 0, 0, true>(a, bwd, st);
+      case 3: return launch_fused<3, 0, 0, true>(a, bwd, st);
+      default: return fail(RD_EUNSUPPORTED, "fused message passing: F = %d > 48", L.F);
+    }
   }
   if (L.F == 34 && L.T == 60 && model_layout && !(e && atoi(e) == 0)) return launch_fused<3, 34, 60>(a, bwd, st);
   switch (L.RT) {
@@ -1073,8 +1108,9 @@ bool fused_msgpass_infer_ok(const rd_shape* s) {
 int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, const float* b1, const float* b2,
                       const float* ssum, const void* wt, float p_drop, uint64_t seed, void* tpX, void* tpY1,
                       void* m1, void* m2, void* mx, float* z, int ldz, hipStream_t st, const float* times,
-                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save) {
+                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save, const float* coef) {
   FusedArgs a{};
+  a.coef = coef;
   fill_layout(a, L);
   a.times = times; a.lengths = lengths; a.tscale = tscale; a.mask = mask; a.d_pe = d_pe;
   a.src = src; a.R_u = R_u; a.b1 = b1; a.b2 = b2; a.ssum = ssum; a.wt = (const __bf16*)wt;
@@ -1087,8 +1123,9 @@ int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, c
 
 int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, const void* wt, float p_drop,
                       const void* m1, const void* m2, const void* mx, const float* dz, int ldz, void* tpD1, void* tpD2,
-                      void* ones, float* rupart, hipStream_t st, const void* tpX, const void* tpY1) {
+                      void* ones, float* rupart, hipStream_t st, const void* tpX, const void* tpY1, const float* coef) {
   FusedArgs a{};
+  a.coef = coef;
   fill_layout(a, L);
   {   // the forward's row tiles, only touched here (RD_K1_WARM=0: not at all; A/B)
     static const bool warm = [] { const char* e = getenv("RD_K1_WARM"); return !(e && atoi(e) == 0); }();

@@ -20,7 +20,8 @@ through two hipGraphs instead of one C-ABI call per operator under autograd:
                `RD_MODULE_GRAD_VIEWS=0` restores the clone-and-return form (parameter hooks then fire as with the eager path).
 
 Same kernels, token plan and dropout scheme as `raindrop_amd.step.TrainStep` (masks are a function of the step's seed cell, which
-the forward graph bumps per replay); the loss stays the caller's.  Calls the captured step does not cover fall back to the eager
+the forward graph bumps per replay -- the coefficient dropout of `ob_propagation.dropout` / `ob_propagation_layer2.dropout` included:
+the forward graph then starts its sensor stage with the table launch); the loss stays the caller's.  Calls the captured step does not cover fall back to the eager
 operators, silently and per call: evaluation / no-grad calls, `use_beta` / `compute_distance` models, another batch size or
 device than the captured one is handled by capturing a second runner (the `RD_MODULE_GRAPH_MAX` = 4 most recently created are
 kept: each holds a step's activations), torch.distributed with more than one rank (use `TrainStep` + `dp.FlatGradAllReduce`
@@ -172,7 +173,9 @@ def forward(model, src, static, times, lengths):
         return None
     dev = src.device
     runners = model.__dict__.setdefault("_graph_runners", {})
-    key = (T, B, str(dev), float(model.dropout.p), int(_lib.load().rd_get_precision()))
+    from .models_rd import coef_dropout_of
+    # (the coefficient-dropout probabilities are read when a step is built: a changed attribute captures a runner of its own)
+    key = (T, B, str(dev), float(model.dropout.p), int(_lib.load().rd_get_precision())) + coef_dropout_of(model)
     r = runners.get(key)
     if r is False:                                                     # capture failed before for this key: do not retry every call
         return None

@@ -186,6 +186,19 @@ def edge_dropout_of(model):
     return float(model.ob_propagation.dropout)
 
 
+def coef_dropout_of(model):
+    """(p1, p2), the coefficient-dropout probabilities of the two operators on the DEFAULT branch (`use_beta=False`):
+    `ob_propagation.dropout` / `ob_propagation_layer2.dropout` in training mode (code/Ob_propagation.py:195-196; upstream users set
+    the attributes, the constructor has no keyword for them), (0, 0) in evaluation mode.  The edge weights of this branch come from
+    `global_structure`, which is no parameter: dropping coefficients adds no gradient term, and both layers are supported."""
+    if not model.training:
+        return 0.0, 0.0
+    p1, p2 = float(model.ob_propagation.dropout), float(model.ob_propagation_layer2.dropout)
+    if not (0.0 <= p1 < 1.0 and 0.0 <= p2 < 1.0):
+        raise _lib.RaindropHipError("ob_propagation.dropout / ob_propagation_layer2.dropout must be in [0, 1), got %r" % ((p1, p2),))
+    return p1, p2
+
+
 class Raindrop_v2(nn.Module):
     """code/models_rd.py:194-387.  Transformer-over-time on top of per-sample sensor-graph message
     passing; see the module docstring for the boundary contract."""
@@ -372,7 +385,9 @@ class Raindrop_v2(nn.Module):
                 src.float(), times.float(), lengths, self.pos_encoder.timescales(dev), g["ssum"], self.R_u,
                 self.ob_propagation.lin_value.weight, self.ob_propagation.lin_value.bias,
                 self.ob_propagation_layer2.lin_value.weight, self.ob_propagation_layer2.lin_value.bias, shp,
-                p_drop, seed)
+                p_drop, seed, coef_p=coef_dropout_of(self), edges=(g["edge_index"], g["edge_weights"]))
+            # coefficient dropout (training mode): one keep decision per (sample, layer, edge) under this forward's seed -- the
+            # aggregate scale ssum[f] becomes a per-(sample, layer, sensor) table (ops.coef_table); the returned structure is untouched.
             # every sample returns the same edge scores on this branch: cdist of equal columns, exactly 0
             distance = torch.zeros((), dtype=torch.float32, device=dev)
         # ---- temporal stage: nn.TransformerEncoder semantics on the HIP kernels (K2/K3) ----------

@@ -88,10 +88,26 @@ def timescales(max_len, d_pe=16):
 # sensor stage: observation embedding + 2 x Observation_progation + PE concat + padding mask
 # ------------------------------------------------------------------------------------------------
 
-def sensor_stage_fwd_raw(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed):
+def coef_table(edge_index, edge_weights, ssum, B, p1, p2, seed):
+    """rd_msgpass_coef_table: the per-(layer, sample, sensor) aggregate coefficients of the default branch under coefficient
+    dropout, coef [2,B,F] fp32 -- row l*B + b is row l*B + b of a 2B-row edge_softmax_list_batched(shared list, norm_row=1,
+    p_drop=p_l, seed) bit for bit; a layer with p_l = 0 gets `ssum`."""
+    ei = edge_index.contiguous()
+    w = edge_weights.contiguous()
+    _check(ei, dtype=torch.int64)
+    _check(w, ssum)
+    F = ssum.shape[0]
+    coef = torch.empty((2, int(B), F), dtype=torch.float32, device=ssum.device)
+    _lib.call("rd_msgpass_coef_table", int(B), F, ei.shape[1], _ptr(ei), ei.stride(0), _ptr(w), _ptr(ssum), float(p1), float(p2),
+              int(seed) & 0x7FFFFFFFFFFFFFFF, _ptr(coef), _stream())
+    return coef
+
+
+def sensor_stage_fwd_raw(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed, coef=None):
     """rd_sensor_stage_fwd: PE + padding mask + message passing into one [T,B,D] buffer.
+    coef [2,B,F] (coef_table): rd_sensor_stage_fwd_coef, the per-(layer, sample, sensor) scale in place of ssum[f].
     Returns (z, mask, saved)."""
-    _check(src, times, ts, ssum, R_u, W1, b1, W2, b2)
+    _check(src, times, ts, ssum, R_u, W1, b1, W2, b2, coef)
     _check(lengths, dtype=torch.int64)
     T, B, F, d = shp.T, shp.B, shp.F, shp.d_ob
     D = F * d + shp.d_pe
@@ -100,14 +116,15 @@ def sensor_stage_fwd_raw(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp
     mask = torch.empty((B, T), dtype=torch.bool, device=dev)
     sp = ctypes.byref(shp)
     saved = _workspace(_lib.load().rd_msgpass_saved_bytes(sp), dev)
-    _lib.call("rd_sensor_stage_fwd", sp, _ptr(src), _ptr(times), _ptr(lengths), _ptr(ts), _ptr(R_u), _ptr(W1),
-              _ptr(b1), _ptr(W2), _ptr(b2), _ptr(ssum), float(p_drop), int(seed), _ptr(z), _ptr(mask), _ptr(saved),
-              saved.numel(), _stream())
+    extra = () if coef is None else (_ptr(coef),)
+    _lib.call("rd_sensor_stage_fwd" if coef is None else "rd_sensor_stage_fwd_coef", sp, _ptr(src), _ptr(times), _ptr(lengths),
+              _ptr(ts), _ptr(R_u), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(ssum), *extra, float(p_drop), int(seed), _ptr(z),
+              _ptr(mask), _ptr(saved), saved.numel(), _stream())
     return z, mask, saved
 
 
-def sensor_stage_bwd_raw(src, R_u, W1, W2, ssum, saved, z, dz, shp, p_drop):
-    """rd_msgpass_bwd.  Returns (dR_u, dW1, db1, dW2, db2)."""
+def sensor_stage_bwd_raw(src, R_u, W1, W2, ssum, saved, z, dz, shp, p_drop, coef=None):
+    """rd_msgpass_bwd (coef: rd_msgpass_bwd_coef, the forward's table).  Returns (dR_u, dW1, db1, dW2, db2)."""
     K = shp.T * shp.d_ob
     D = shp.F * shp.d_ob + shp.d_pe
     dev = dz.device
@@ -118,8 +135,9 @@ def sensor_stage_bwd_raw(src, R_u, W1, W2, ssum, saved, z, dz, shp, p_drop):
     dRu = torch.empty_like(R_u)
     sp = ctypes.byref(shp)
     ws = _workspace(_lib.load().rd_msgpass_workspace_bytes(sp), dev)
-    _lib.call("rd_msgpass_bwd", sp, _ptr(src), _ptr(R_u), _ptr(W1), _ptr(W2), _ptr(ssum), float(p_drop),
-              _ptr(saved), saved.numel(), _ptr(z), _ptr(dz), D, _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2),
+    extra = () if coef is None else (_ptr(coef),)
+    _lib.call("rd_msgpass_bwd" if coef is None else "rd_msgpass_bwd_coef", sp, _ptr(src), _ptr(R_u), _ptr(W1), _ptr(W2), _ptr(ssum),
+              *extra, float(p_drop), _ptr(saved), saved.numel(), _ptr(z), _ptr(dz), D, _ptr(dW1), _ptr(db1), _ptr(dW2), _ptr(db2),
               _ptr(dRu), _ptr(ws), ws.numel(), _stream())
     return dRu, dW1, db1, dW2, db2
 
@@ -128,28 +146,40 @@ class _SensorStage(torch.autograd.Function):
     """z[T,B,D] = cat(message_passing(src), PE(times));  mask[B,T] = t >= lengths.
 
     Forward : rd_pe_mask + rd_msgpass_fwd write disjoint column ranges of one buffer.
-    Backward: rd_msgpass_bwd (dW1, db1, dW2, db2, dR_u); PE / mask carry no gradient."""
+    Backward: rd_msgpass_bwd (dW1, db1, dW2, db2, dR_u); PE / mask carry no gradient.
+    coef (coefficient dropout, coef_table): the `_coef` entry points in both directions; the table is kept for the backward."""
 
     @staticmethod
-    def forward(ctx, src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed):
-        z, mask, saved = sensor_stage_fwd_raw(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed)
+    def forward(ctx, src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed, coef=None):
+        z, mask, saved = sensor_stage_fwd_raw(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop, seed, coef)
         ctx.shp = shp
         ctx.p_drop = float(p_drop)
-        ctx.save_for_backward(src, R_u, W1, W2, ssum, saved, z)
+        ctx.save_for_backward(src, R_u, W1, W2, ssum, saved, z, coef)
         ctx.mark_non_differentiable(mask)
         return z, mask
 
     @staticmethod
     def backward(ctx, dz, _dmask):
-        src, R_u, W1, W2, ssum, saved, z = ctx.saved_tensors
+        src, R_u, W1, W2, ssum, saved, z, coef = ctx.saved_tensors
         dRu, dW1, db1, dW2, db2 = sensor_stage_bwd_raw(src, R_u, W1, W2, ssum, saved, z, dz.contiguous(), ctx.shp,
-                                                       ctx.p_drop)
-        return None, None, None, None, None, dRu, dW1, db1, dW2, db2, None, None, None
+                                                       ctx.p_drop, coef)
+        return None, None, None, None, None, dRu, dW1, db1, dW2, db2, None, None, None, None
 
 
-def sensor_stage(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop=0.0, seed=0):
+def sensor_stage(src, times, lengths, ts, ssum, R_u, W1, b1, W2, b2, shp, p_drop=0.0, seed=0, coef_p=(0.0, 0.0), edges=None):
+    """coef_p = (p1, p2): coefficient dropout of the two layers (code/Ob_propagation.py:195-196 on the default branch) -- one keep
+    decision per (sample, layer, edge) of `edges` = (edge_index [2,E], edge_weights [E]) under `seed`; (0, 0): no table, the plain
+    entry points."""
+    p1, p2 = float(coef_p[0]), float(coef_p[1])
+    coef = None
+    if p1 > 0.0 or p2 > 0.0:
+        if not (0.0 <= p1 < 1.0 and 0.0 <= p2 < 1.0):
+            raise _lib.RaindropHipError("sensor_stage: coefficient dropout probabilities must be in [0, 1), got %r" % ((p1, p2),))
+        if edges is None:
+            raise _lib.RaindropHipError("sensor_stage: coef_p needs the edge list the coefficients are dropped on (edges=)")
+        coef = coef_table(edges[0], edges[1], ssum, shp.B, p1, p2, seed)
     return _SensorStage.apply(src.contiguous(), times.contiguous(), lengths.contiguous(), ts, ssum,
-                              R_u.contiguous(), W1, b1, W2, b2, shp, p_drop, seed)
+                              R_u.contiguous(), W1, b1, W2, b2, shp, p_drop, seed, coef)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -136,9 +136,21 @@ def validate_batch(model, batch, labels=True):
 
 class SensorStage:
     """The sensor stage of the DEFAULT branch (rd_sensor_stage_fwd / rd_msgpass_bwd: code/models_rd.py:317's `use_beta = False`,
-    distance exactly 0), and the interface a step asks its sensor stage through."""
+    distance exactly 0), and the interface a step asks its sensor stage through.
+    Coefficient dropout: `coef_p` = (p1, p2), the model's `ob_propagation.dropout` / `ob_propagation_layer2.dropout` read when the step
+    is built (raindrop_amd.models_rd.coef_dropout_of: training-mode model; only a step with a backward -- an evaluation step never
+    drops).  With one of them non-zero the forward stage starts with the table launch (rd_msgpass_coef_table into `step.k1_coef`
+    [2,B,F], sample b = the caller's batch index with or without a token plan) and both directions run the `_coef` entry points;
+    with both zero the stage enqueues exactly what it always did.  The masks follow the step's seed and seed cell like the model's
+    own dropout: fresh per replay, the rank offset in the data-parallel form."""
     prepared_tiles = True         # rd_step_prepare's K1 weight tiles are this stage's
     distance = None
+    coef_p = (0.0, 0.0)
+
+    @property
+    def edge_drop(self):
+        """the step draws coefficient-dropout masks: its seed cell must advance per replay even with the model's dropout at 0"""
+        return self.coef_p[0] > 0.0 or self.coef_p[1] > 0.0
 
     def check(self, model):
         """A model built with the paper's branch switched on would silently train a different network here (and never see
@@ -155,7 +167,13 @@ class SensorStage:
                 int(step.lib.rd_msgpass_workspace_bytes(step.sp)) if step.has_backward else 0)
 
     def alloc(self, step):
-        pass
+        from .models_rd import coef_dropout_of
+        self.coef_p = coef_dropout_of(step.model) if step.has_backward else (0.0, 0.0)
+        if self.edge_drop:
+            g = step.graph_info
+            self.ei, self.ew = g["edge_index"].contiguous(), g["edge_weights"].contiguous()   # [2,E] int64 (rows E apart), [E]
+            ops._validate_edges(self.ei, step.model.d_inp, "TrainStep")
+            step.k1_coef = torch.zeros((2, step.B, step.model.d_inp), dtype=torch.float32, device=step.dev)
 
     def _weights(self, P):
         return [P["ob_propagation" + n] for n in (".lin_value.weight", ".lin_value.bias", "_layer2.lin_value.weight", "_layer2.lin_value.bias")]
@@ -167,15 +185,21 @@ class SensorStage:
             return s._call("rd_sensor_stage_fwd_infer", s.sp, _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(s.ts), _p(P["R_u"]),
                            _p(W1), _p(b1), _p(W2), _p(b2), _p(s.graph_info["ssum"]), _p(s.z), _p(s.mask), _p(s.k1_saved),
                            s.k1_saved.numel(), 1 if s.prep_k1 else 0, st)
-        s._call("rd_sensor_stage_fwd_prepared" if s.prep_k1 else "rd_sensor_stage_fwd", s.sp, _p(b["src"]), _p(b["times"]),
-                _p(b["lengths"]), _p(s.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2), _p(s.graph_info["ssum"]), s.p_drop,
-                s.seed, _p(s.z), _p(s.mask), _p(s.k1_saved), s.k1_saved.numel(), st)
+        coef = ()
+        if self.edge_drop:                                        # this replay's coefficient table, under the step's seed + seed cell
+            s._call("rd_msgpass_coef_table", s.B, s.model.d_inp, int(self.ei.shape[1]), _p(self.ei), self.ei.stride(0), _p(self.ew),
+                    _p(s.graph_info["ssum"]), self.coef_p[0], self.coef_p[1], s.seed, _p(s.k1_coef), st)
+            coef = (_p(s.k1_coef),)
+        s._call(("rd_sensor_stage_fwd_prepared" if s.prep_k1 else "rd_sensor_stage_fwd") + ("_coef" if coef else ""), s.sp,
+                _p(b["src"]), _p(b["times"]), _p(b["lengths"]), _p(s.ts), _p(P["R_u"]), _p(W1), _p(b1), _p(W2), _p(b2),
+                _p(s.graph_info["ssum"]), *coef, s.p_drop, s.seed, _p(s.z), _p(s.mask), _p(s.k1_saved), s.k1_saved.numel(), st)
 
     def backward(self, s, cur, st):
         b, P = s.batch, s.P
         W1, _, W2, _ = self._weights(P)
-        s._call("rd_msgpass_bwd", s.sp, _p(b["src"]), _p(P["R_u"]), _p(W1), _p(W2), _p(s.graph_info["ssum"]), s.p_drop,
-                _p(s.k1_saved), s.k1_saved.numel(), _p(s.z), _p(cur), s.D, *[_p(g) for g in self._weights(s.G)], _p(s.G["R_u"]),
+        coef = (_p(s.k1_coef),) if self.edge_drop else ()
+        s._call("rd_msgpass_bwd_coef" if coef else "rd_msgpass_bwd", s.sp, _p(b["src"]), _p(P["R_u"]), _p(W1), _p(W2),
+                _p(s.graph_info["ssum"]), *coef, s.p_drop, _p(s.k1_saved), s.k1_saved.numel(), _p(s.z), _p(cur), s.D, *[_p(g) for g in self._weights(s.G)], _p(s.G["R_u"]),
                 _p(s.k1_ws), s.k1_ws.numel(), st)
 
 
@@ -366,7 +390,7 @@ class Step:
         prep = self.prep_enc or self.prep_k1
         prep_args = (self.nl if self.prep_enc else 0, self._prep_w, self._prep_saved, self._prep_bytes,
                      _p(W1) if self.prep_k1 else None, _p(W2) if self.prep_k1 else None, _p(self.k1_saved), self.k1_saved.numel(), st)
-        drops = self.p_drop > 0.0 or getattr(self.sensor, "edge_drop", False)   # (the use_beta stage's coefficient dropout)
+        drops = self.p_drop > 0.0 or getattr(self.sensor, "edge_drop", False)   # (either sensor stage's coefficient dropout)
         cell = _p(self.seed_cell) if drops else None
         if self.plan is not None and prep and self.one_begin:
             return c("rd_step_begin", sp, _p(b["lengths"]), _p(self.plan), cell, 1, *prep_args)
