@@ -401,6 +401,28 @@ int rd_adam_step_dev(int64_t n, float* param, const float* grad, float* exp_avg,
 int rd_adam_state_advance(void* state, float beta1, float beta2, void* stream);
 int rd_set_adam_state(void* state, float beta1, float beta2);      /* NULL: unregister */
 
+/* Global-norm gradient clipping and the non-finite guard: torch.nn.utils.clip_grad_norm_ between backward and the update, as two
+ * launches a hipGraph can hold (raindrop_amd.optim.FlatAdam(max_grad_norm=...)).
+ * rd_grad_sumsq: partial[w] = sum of grad[i]^2 over the w-th of rd_grad_sumsq_grid() contiguous slices, squared and accumulated in
+ * double in a fixed order (no atomics: the same bits on every launch).  `partial`: rd_grad_sumsq_bytes() bytes, 16-byte aligned.
+ * rd_adam_step_clip / rd_adam_step_clip_dev: rd_adam_step / rd_adam_step_dev on the clipped gradient.  Every workgroup sums the
+ * partials in index order, norm = sqrt(sum), scale = norm > max_norm ? max_norm / (norm + 1e-6) : 1 (clip_grad_norm_'s coefficient,
+ * clamped at 1), then Adam with g * scale + weight_decay * p.  A sum that is not finite (an inf or NaN gradient) makes the launch
+ * store NOTHING: param, exp_avg, exp_avg_sq keep their bits.  At scale == 1 the update is rd_adam_step's / rd_adam_step_dev's, bit
+ * for bit.  `clip`: 64 bytes, 16-byte aligned, eight doubles {max_norm, last_norm, last_scale, skipped, clipped, 0, 0, 0}: slot 0 is
+ * read by the launch and written by the caller only (a new threshold is an 8-byte copy, not a new capture; +inf: guard without
+ * clipping); slots 1-4 are written by one thread of the launch -- the norm and the scale it applied (0 when it skipped) and two
+ * running counts of skipped / clipped steps.  The step state of the _dev form is advanced as for rd_adam_step_dev, skipped or not.
+ * RD_EINVAL before any launch: NULL or misaligned pointers, n <= 0, partial_bytes < rd_grad_sumsq_bytes(). */
+int32_t rd_grad_sumsq_grid(void);
+size_t rd_grad_sumsq_bytes(void);
+int rd_grad_sumsq(int64_t n, const float* grad, void* partial, size_t partial_bytes, void* stream);
+int rd_adam_step_clip(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int64_t step, const void* partial, size_t partial_bytes,
+                      void* clip, void* stream);
+int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
+                          float eps, const void* state, const void* partial, size_t partial_bytes, void* clip, void* stream);
+
 /* ---- generic dense pieces (used by the temporal encoder, the head and the large-K path) ---- */
 
 /* y[M,N] = act(x[M,K] W[N,K]^T + b)   (torch.nn.functional.linear; act: 0 none, 1 relu). */

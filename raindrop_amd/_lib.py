@@ -107,6 +107,13 @@ SIGNATURES = {
     "rd_adam_step_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P]),
     "rd_adam_state_advance": (c_int32, [_P, c_float, c_float, _P]),
     "rd_set_adam_state": (c_int32, [_P, c_float, c_float]),
+    # global-norm gradient clipping / non-finite guard (include/raindrop_hip.h; raindrop_amd.optim.FlatAdam(max_grad_norm=...))
+    "rd_grad_sumsq_grid": (c_int32, []),
+    "rd_grad_sumsq_bytes": (c_size_t, []),
+    "rd_grad_sumsq": (c_int32, [ctypes.c_int64, _P, _P, c_size_t, _P]),
+    "rd_adam_step_clip": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, ctypes.c_int64,
+                                    _P, c_size_t, _P, _P]),
+    "rd_adam_step_clip_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P]),
     "rd_linear_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_fwd_fp32": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_bwd_input": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P]),

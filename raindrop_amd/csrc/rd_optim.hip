@@ -84,6 +84,125 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const f
 }
 __global__ void k_adam_advance(double* state, float b1, float b2) { adam_state_advance(state, b1, b2); }
 
+// ---- global-norm gradient clipping and the non-finite guard (DESIGN.md "Gradient clipping") -------------------------------------
+// Two launches behind the last all-reduce wait, both capturable: k_sumsq_partial leaves kClipGrid partial sums of squares of the flat
+// gradient, k_adam_clip adds them up -- every workgroup the same kClipGrid doubles in index order, ~1 KB from L2: no float atomics,
+// no arrival ticket (rules 15, 37), the same bits on every workgroup, every launch and every rank -- and applies Adam to
+// g * min(1, max_norm / (norm + 1e-6)), or nothing at all when the sum is not finite.  New kernels, not a flag in k_adam / k_adam_dev:
+// with the feature off the step enqueues exactly what it did (rule 40).  (No own-code touch: the table has no site for them.)
+constexpr int kClipGrid = 128;
+
+// sum over the 64 lanes on the DPP path (rd_common.h wave_sum64_dpp) for a double: the two halves travel as two dwords
+__device__ __forceinline__ double wave_sum64_dpp_f64(double v) {
+#define RD_DPP_ADD64(ctrl, rmask)                                                                            \
+  {                                                                                                          \
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rmask, 0xf, false);               \
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rmask, 0xf, false);               \
+    v += __hiloint2double(hi, lo);                                                                           \
+  }
+  RD_DPP_ADD64(0x111, 0xf);   // row_shr:1
+  RD_DPP_ADD64(0x112, 0xf);   // row_shr:2
+  RD_DPP_ADD64(0x114, 0xf);   // row_shr:4
+  RD_DPP_ADD64(0x118, 0xf);   // row_shr:8
+  RD_DPP_ADD64(0x142, 0xa);   // row_bcast:15 -> rows 1, 3
+  RD_DPP_ADD64(0x143, 0xc);   // row_bcast:31 -> rows 2, 3
+#undef RD_DPP_ADD64
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 63), __builtin_amdgcn_readlane(__double2loint(v), 63));
+}
+
+// partial[w] = sum of g[i]^2 over workgroup w's contiguous run of float4 slots, squared and accumulated in double (the square of a
+// float is exact in a double).  Fixed order: thread t takes slots t, t + 256, ..; lanes by DPP, the four waves through LDS.
+// Every workgroup writes its partial (0 for an empty run: n smaller than the grid's reach).
+__global__ __launch_bounds__(256) void k_sumsq_partial(const float* __restrict__ g, long n, double* __restrict__ partial) {
+  __shared__ double wsum[4];
+  const long n4 = (n + 3) >> 2;                                  // float4 slots, the last one possibly short
+  const long per = (n4 + kClipGrid - 1) / kClipGrid;            // the grid IS kClipGrid (rd_grad_sumsq): a shift, not a 64-bit division
+  const long q0 = blockIdx.x * per, q1 = q0 + per < n4 ? q0 + per : n4;
+  double acc = 0.0;
+#pragma unroll 4
+  for (long q = q0 + threadIdx.x; q < q1; q += 256) {
+    const long i = q * 4;
+    if (i + 3 < n) {
+      const float4 x = *reinterpret_cast<const float4*>(g + i);
+      acc += (double)x.x * (double)x.x; acc += (double)x.y * (double)x.y;
+      acc += (double)x.z * (double)x.z; acc += (double)x.w * (double)x.w;
+    } else {
+      for (long j = i; j < n; ++j) acc += (double)g[j] * (double)g[j];
+    }
+  }
+  const double s = wave_sum64_dpp_f64(acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// a * b rounded on its own: never the multiply of a fused multiply-add (the compiler contracts a plain `a * b + c`, __fmul_rn included)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// The clip cell: slot 0 is read by every workgroup and written only by the host (an 8-byte copy, like lr); slots 1-4 are written by
+// thread 0 of workgroup 0 alone and read by no workgroup of any launch (the counters by that one thread, to add 1).
+struct ClipCell { double max_norm, last_norm, last_scale, skipped, clipped, pad0, pad1, pad2; };
+
+// k_adam_dev (DEV: step state in the device cell) / k_adam (host-computed corrections) on the clipped gradient.  The scale is its own
+// rounded multiply: at scale == 1 `gs` IS g and everything behind it is the expression of k_adam / k_adam_dev -- the same bits.
+// Weight decay is added AFTER the scale (torch clips the raw gradient; Adam adds wd * p inside its step).
+template <bool DEV>
+__global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, long n, float b1, float b2, float eps,
+                                                   const AdamState* __restrict__ state, float lr_h, float wd_h, float bc1_h,
+                                                   float bc2_sqrt_h, const double* __restrict__ partial, double* clip) {
+  double sum = 0.0;
+  for (int k = 0; k < kClipGrid; ++k) sum += partial[k];
+  const double max_norm = clip[0];
+  const bool finite = fabs(sum) <= 1.7976931348623157e308;       // false for inf and NaN
+  const double norm = sqrt(sum);
+  const double sc = norm > max_norm ? max_norm / (norm + 1e-6) : 1.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    clip[1] = norm;
+    clip[2] = finite ? sc : 0.0;
+    if (!finite) clip[3] += 1.0;
+    else if (sc < 1.0) clip[4] += 1.0;
+  }
+  if (!finite) return;                                           // uniform over the launch: p, m, v keep their bits
+  const float scale = (float)sc;
+  float lr, wd, bc1, bc2_sqrt;
+  if (DEV) {
+    lr = (float)state->lr; wd = (float)state->wd;
+    bc1 = (float)(1.0 - state->p1); bc2_sqrt = (float)sqrt(1.0 - state->p2);
+  } else {
+    lr = lr_h; wd = wd_h; bc1 = bc1_h; bc2_sqrt = bc2_sqrt_h;
+  }
+  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  const float step_size = lr / bc1;
+  if (i4 + 3 < n) {
+    float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
+    float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
+    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+      const float gs = mul_rounded(G[c4], scale);
+      const float gr = gs + wd * P[c4];
+      M[c4] = b1 * M[c4] + (1.f - b1) * gr;
+      V[c4] = b2 * V[c4] + (1.f - b2) * gr * gr;
+      P[c4] -= step_size * M[c4] / (sqrtf(V[c4]) / bc2_sqrt + eps);
+    }
+    *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
+    *reinterpret_cast<float4*>(v + i4) = vv;
+  } else {
+    for (long i = i4; i < n; ++i) {
+      const float gs = mul_rounded(g[i], scale);
+      const float gr = gs + wd * p[i];
+      m[i] = b1 * m[i] + (1.f - b1) * gr;
+      v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
+      p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
+    }
+  }
+}
+
 __global__ __launch_bounds__(64) void k_ifetch_probe(float* out, unsigned long long* t, float a, float b) {
   float x = (float)threadIdx.x;
   const unsigned long long c0 = clock64();
@@ -140,4 +259,54 @@ extern "C" int rd_adam_state_advance(void* state, float beta1, float beta2, void
   RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
   hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, (hipStream_t)stream, (double*)state, beta1, beta2);
   return check_launch("k_adam_advance");
+}
+
+// ---- gradient clipping / non-finite guard -----------------------------------------------------------------------------------------
+extern "C" int32_t rd_grad_sumsq_grid(void) { return kClipGrid; }
+extern "C" size_t rd_grad_sumsq_bytes(void) { return (size_t)kClipGrid * sizeof(double); }
+
+extern "C" int rd_grad_sumsq(int64_t n, const float* grad, void* partial, size_t partial_bytes, void* stream) {
+  RD_REQUIRE(n > 0, "bad n");
+  RD_REQUIRE(grad && partial, "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(partial)) & 15) == 0, "buffers must be 16-byte aligned");
+  RD_REQUIRE(partial_bytes >= rd_grad_sumsq_bytes(), "partial buffer too small (rd_grad_sumsq_bytes)");
+  hipLaunchKernelGGL(k_sumsq_partial, dim3(kClipGrid), dim3(256), 0, (hipStream_t)stream, grad, (long)n, (double*)partial);
+  return check_launch("k_sumsq_partial");
+}
+
+static int clip_args_ok(int64_t n, const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                        const void* partial, size_t partial_bytes, const void* clip) {
+  RD_REQUIRE(n > 0, "bad n");
+  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq && partial && clip, "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+               reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(clip)) & 15) == 0,
+             "buffers must be 16-byte aligned");
+  RD_REQUIRE(partial_bytes >= rd_grad_sumsq_bytes(), "partial buffer too small (rd_grad_sumsq_bytes)");
+  return RD_OK;
+}
+
+extern "C" int rd_adam_step_clip(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
+                                 size_t partial_bytes, void* clip, void* stream) {
+  RD_REQUIRE(step >= 1, "bad step");
+  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_adam_clip<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)nullptr, lr, weight_decay, (float)bc1,
+                     (float)sqrt(bc2), (const double*)partial, (double*)clip);
+  return check_launch("k_adam_clip");
+}
+
+extern "C" int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                     float beta2, float eps, const void* state, const void* partial, size_t partial_bytes,
+                                     void* clip, void* stream) {
+  RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
+  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_adam_clip<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, 0.f, 0.f, 0.f, 0.f,
+                     (const double*)partial, (double*)clip);
+  return check_launch("k_adam_clip_dev");
 }

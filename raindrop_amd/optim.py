@@ -6,16 +6,43 @@ gradients already live in two flat buffers, the whole update is ONE elementwise 
 (rd_adam_step) instead of a 35-tensor multi-tensor launch.  Same formula as torch (no amsgrad).
 """
 import ctypes
+import math
 
 import torch
 
 from . import _lib, ops
 
 
+def _check_max_grad_norm(x):
+    """a positive float, or math.inf (the non-finite guard alone)"""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not x > 0:          # NaN fails `x > 0`
+        raise ValueError("max_grad_norm must be None, a positive float or math.inf, got %r" % (x,))
+    return float(x)
+
+
 class FlatAdam:
-    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+    """Adam over the flat buffers; `step()` with host-computed bias corrections, `step_captured()` with the step state on the device.
+
+    max_grad_norm (default None: off -- the launches and the code path of an optimizer built without the keyword): global-norm
+    gradient clipping and a non-finite guard INSIDE the step, so that they also exist in a whole-step hipGraph
+    (`TrainStep.capture_full`).  A positive float clips like `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` in front of
+    `step()`: the raw gradient is multiplied by min(1, max_norm / (norm + 1e-6)), weight decay is added afterwards; `math.inf` keeps
+    only the guard.  On, a step is two launches instead of one (rd_grad_sumsq, rd_adam_step_clip[_dev]); at N > 1 they follow the
+    all-reduce, so the norm is that of the averaged gradient and the same bits on every rank.  The threshold lives in a device
+    cell: `set_max_grad_norm(x)` (or assigning `max_grad_norm` before `TrainStep.run_full`) is an 8-byte copy, not a new capture.
+    `grad_stats()` reads the last norm and scale and the counts of skipped and clipped steps.
+
+    A step whose gradient holds an inf or a NaN is SKIPPED: parameters, exp_avg and exp_avg_sq keep their bits.  It still COUNTS
+    as a step: `t` and the device step state {t, beta^t} advance (the state is advanced by the step's first launch, long before
+    the norm is known), so `self.t == device_steps()` always holds and the bias corrections of later steps are those of t + 1.
+    torch.amp's GradScaler does NOT count a skipped step; after k skips the corrections here are k steps ahead of a GradScaler
+    loop's (they tend to 1 either way)."""
+
+    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
         if flat_param.grad is None:
             raise ValueError("flat_param.grad must be the flat gradient buffer")
+        self.max_grad_norm = None if max_grad_norm is None else _check_max_grad_norm(max_grad_norm)
+        self.clip_cell = self.clip_partial = None
         self.param = flat_param
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat_param.data)
@@ -23,19 +50,66 @@ class FlatAdam:
         self.t = 0
         self.step_cell = None                # device step state of the captured form (step_captured)
         self._cell_stale = False
+        if self.max_grad_norm is not None:
+            self._make_clip_buffers()
 
     def hyper(self):
-        """the values a captured launch holds as CONSTANTS (TrainStep.run_full captures again when they change): betas and eps.
-        lr and weight_decay live in the device step cell (cell_hyper): changing them is a small copy, not a new capture."""
-        return (float(self.betas[0]), float(self.betas[1]), float(self.eps))
+        """the values a captured launch holds as CONSTANTS (TrainStep.run_full captures again when they change): betas and eps, and
+        whether the clipping launches are there at all.  lr and weight_decay live in the device step cell (cell_hyper), the
+        clipping threshold in the clip cell: changing them is a small copy, not a new capture."""
+        h = (float(self.betas[0]), float(self.betas[1]), float(self.eps))
+        return h if self.max_grad_norm is None else h + ("clip",)
 
     def cell_hyper(self):
         return (float(self.lr), float(self.weight_decay))
+
+    # ---- gradient clipping / non-finite guard (max_grad_norm) ----
+    def _make_clip_buffers(self):
+        """the clip cell {max_norm, last_norm, last_scale, skipped, clipped, 0, 0, 0} (include/raindrop_hip.h rd_adam_step_clip) and
+        the partial sums of rd_grad_sumsq; made outside any capture (the constructor, load_state_dict)"""
+        dev = self.param.device
+        self.clip_partial = torch.zeros((int(_lib.load().rd_grad_sumsq_bytes()) // 8,), dtype=torch.float64, device=dev)
+        self.clip_cell = torch.tensor([self.max_grad_norm] + [0.0] * 7, dtype=torch.float64).to(dev)
+        self._cell_max_norm = self.max_grad_norm
+
+    def _clip_args(self):
+        self.sync_clip_cell()
+        return (ops._ptr(self.clip_partial), self.clip_partial.numel() * 8, ops._ptr(self.clip_cell))
+
+    def set_max_grad_norm(self, x):
+        """A new threshold (positive float or math.inf) for the steps enqueued from here on, captured ones included: one 8-byte
+        copy into the clip cell, stream-ordered with the launches around it."""
+        if self.max_grad_norm is None:
+            raise ValueError("clipping is off: construct FlatAdam with max_grad_norm (the step's launches differ)")
+        self.max_grad_norm = _check_max_grad_norm(x)
+        self.sync_clip_cell()
+
+    def sync_clip_cell(self):
+        """push a changed `max_grad_norm` into the clip cell (TrainStep.run_full calls it next to sync_cell_hyper)"""
+        if self.clip_cell is not None and self.max_grad_norm is not None and self._cell_max_norm != self.max_grad_norm:
+            self.clip_cell[0:1] = torch.tensor([_check_max_grad_norm(self.max_grad_norm)], dtype=torch.float64,
+                                               device=self.clip_cell.device)
+            self._cell_max_norm = self.max_grad_norm
+
+    def grad_stats(self):
+        """dict(norm, scale, skipped, clipped) of the steps so far -- the last step's gradient norm and the factor applied to it (0.0:
+        the step was skipped), and how many steps were skipped / clipped: ONE device-to-host copy (it waits for the stream)."""
+        if self.clip_cell is None:
+            raise ValueError("clipping is off: construct FlatAdam with max_grad_norm")
+        c = self.clip_cell.cpu().tolist()
+        return dict(norm=c[1], scale=c[2], skipped=int(c[3]), clipped=int(c[4]))
 
     def step(self):
         self.t += 1
         self._cell_stale = True              # a captured step that follows re-syncs the device step state (TrainStep.run_full)
         p, g = self.param.data, self.param.grad
+        if self.max_grad_norm is not None:
+            partial, nbytes, cell = self._clip_args()
+            _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
+            _lib.call("rd_adam_step_clip", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
+                      float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
+                      self.t, partial, nbytes, cell, ops._stream())
+            return
         _lib.call("rd_adam_step", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
                   float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
                   self.t, ops._stream())
@@ -50,6 +124,13 @@ class FlatAdam:
         p, g = self.param.data, self.param.grad
         if advance:
             _lib.call("rd_adam_state_advance", ops._ptr(self.step_cell), float(self.betas[0]), float(self.betas[1]), ops._stream())
+        if self.max_grad_norm is not None:   # the norm's partial sums, then the clipping instantiation of the update
+            partial, nbytes, cell = self._clip_args()
+            _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
+            _lib.call("rd_adam_step_clip_dev", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
+                      float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell), partial, nbytes, cell,
+                      ops._stream())
+            return
         _lib.call("rd_adam_step_dev", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
                   float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell), ops._stream())
 
@@ -94,8 +175,10 @@ class FlatAdam:
         self.param.grad.zero_()
 
     def state_dict(self):
+        stats = self.grad_stats() if self.clip_cell is not None else dict(skipped=0, clipped=0)
         return dict(t=self.t, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr, betas=self.betas,
-                    eps=self.eps, weight_decay=self.weight_decay)
+                    eps=self.eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
+                    grad_skipped=stats["skipped"], grad_clipped=stats["clipped"])
 
     def load_state_dict(self, sd):
         """In place (the moment buffers keep their addresses: a captured step stays valid); the device step state follows at the
@@ -105,3 +188,12 @@ class FlatAdam:
         self.t = int(sd["t"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
         self._cell_stale = True
+        if "max_grad_norm" in sd:            # (a dictionary from before the keyword leaves the setting and the counts as they are)
+            mgn = sd["max_grad_norm"]
+            self.max_grad_norm = None if mgn is None else _check_max_grad_norm(mgn)
+            if self.max_grad_norm is not None:
+                if self.clip_cell is None:
+                    self._make_clip_buffers()
+                self.sync_clip_cell()
+                self.clip_cell[3:5] = torch.tensor([float(sd.get("grad_skipped", 0)), float(sd.get("grad_clipped", 0))],
+                                                   dtype=torch.float64, device=self.clip_cell.device)

@@ -754,6 +754,7 @@ class TrainStep(Step):
         the caller falls back to run_allreduce() + opt.step()."""
         flat = self.flat
         opt.sync_step_cell()
+        opt.sync_clip_cell()                                               # FlatAdam(max_grad_norm=...): the threshold's cell (no-op when off)
         # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
         # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
         begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
@@ -803,6 +804,7 @@ class TrainStep(Step):
             self.seed_cell.copy_(cell)
         self._full_opt.sync_cell_hyper()                                   # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259;
                                                                            # warm-up / cosine schedules): an 8-byte copy, no new capture
+        self._full_opt.sync_clip_cell()                                    # the clipping threshold likewise (FlatAdam.max_grad_norm)
         if getattr(self._full_opt, "_cell_stale", False):                  # host-side steps were taken since: device state follows self.t
             self._full_opt.sync_step_cell()
             self._full_opt._cell_stale = False
