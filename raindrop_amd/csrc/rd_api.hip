@@ -3,6 +3,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "rd_common.h"
 #include "rd_rng.h"
 #include "rd_trailing.h"
@@ -12,6 +14,19 @@ namespace rd {
 char* err_buf() {
   static thread_local char buf[512] = {0};
   return buf;
+}
+
+// ---- launch log (include/raindrop_hip_debug.h): the distinct names check_launch was called with while it is on.  Host memory only;
+// the names are the string literals of the call sites, kept by pointer and compared by content. ----
+int g_launch_log_on = 0;
+static std::mutex g_launch_log_mu;
+static const char* g_launch_log_names[512];
+static int g_launch_log_n = 0;
+void launch_log_record(const char* what) {
+  std::lock_guard<std::mutex> lock(g_launch_log_mu);
+  for (int i = 0; i < g_launch_log_n; ++i)
+    if (g_launch_log_names[i] == what || strcmp(g_launch_log_names[i], what) == 0) return;
+  if (g_launch_log_n < (int)(sizeof(g_launch_log_names) / sizeof(g_launch_log_names[0]))) g_launch_log_names[g_launch_log_n++] = what;
 }
 
 // Registered per HOST THREAD and read when a call is ENQUEUED (the pointer becomes a kernel argument): a captured hipGraph
@@ -96,6 +111,27 @@ int fail(int code, const char* fmt, ...) {
 }  // namespace rd
 
 using namespace rd;
+
+extern "C" void rd_debug_launch_log(int on) {            // not part of the ABI
+  std::lock_guard<std::mutex> lock(g_launch_log_mu);
+  g_launch_log_n = 0;
+  g_launch_log_on = on ? 1 : 0;
+}
+extern "C" size_t rd_debug_launch_log_read(char* out, size_t cap) {      // not part of the ABI
+  std::lock_guard<std::mutex> lock(g_launch_log_mu);
+  size_t need = 0, pos = 0;
+  for (int i = 0; i < g_launch_log_n; ++i) {
+    const size_t len = strlen(g_launch_log_names[i]);
+    need += len + (i ? 1 : 0);
+    if (out && pos + len + (i ? 1 : 0) < cap) {
+      if (i) out[pos++] = '\n';
+      memcpy(out + pos, g_launch_log_names[i], len);
+      pos += len;
+    }
+  }
+  if (out && cap) out[pos] = 0;
+  return need;
+}
 
 extern "C" int rd_set_precision(int32_t mode) {
   RD_REQUIRE(mode == RD_PREC_FP32 || mode == RD_PREC_BF16X3 || mode == RD_PREC_BF16, "unknown precision mode %d", mode);

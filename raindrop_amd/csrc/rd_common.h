@@ -13,7 +13,12 @@ namespace rd {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 
+// host-side launch log (include/raindrop_hip_debug.h rd_debug_launch_log): off by default -- one load and one branch here
+extern int g_launch_log_on;
+void launch_log_record(const char* what);
+
 inline int check_launch(const char* what) {
+  if (g_launch_log_on) launch_log_record(what);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail((int)e, "%s: %s", what, hipGetErrorString(e));
   return RD_OK;

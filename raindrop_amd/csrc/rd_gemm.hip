@@ -653,7 +653,21 @@ int launch_bf16x3_n(const GemmArgs& g, hipStream_t st) {
   if (lds > 48 * 1024)
     RD_LDS_ATTR((k_gemm_bf16x3<A_KC, B_KC, MI, NI, NPRE>), lds);
   hipLaunchKernelGGL((k_gemm_bf16x3<A_KC, B_KC, MI, NI, NPRE>), grid, dim3(256), lds, st, g);
-  return check_launch("k_gemm_bf16x3");
+  // One name per workgroup tile, form of the reduction loop and workgroup-to-tile map: the launch log tells RD_WGRAD_TILE,
+  // RD_GEMM_NPRE, RD_GEMM_XCD and RD_SPLITK_XCD apart by it.  The plain name is the default map of its kind (single pass: XCD
+  // round-robin; split-K: one reduction slice per XCD), "_rowmajor" / "_zgrid" the map with the switch off.
+  const int map = g.nsplit > 1 ? (g.slice_xcd ? 0 : 1) : (g.xcd_swizzle ? 0 : 2);
+  if (NPRE > 0)
+    return check_launch(map == 0 ? "k_gemm_bf16x3_64x64_npre" : map == 1 ? "k_gemm_bf16x3_64x64_npre_zgrid" : "k_gemm_bf16x3_64x64_npre_rowmajor");
+  if (MI == 2 && NI == 2)
+    return check_launch(map == 0 ? "k_gemm_bf16x3_64x64" : map == 1 ? "k_gemm_bf16x3_64x64_zgrid" : "k_gemm_bf16x3_64x64_rowmajor");
+  if (MI == 4 && NI == 2)
+    return check_launch(map == 0 ? "k_gemm_bf16x3_128x64" : map == 1 ? "k_gemm_bf16x3_128x64_zgrid" : "k_gemm_bf16x3_128x64_rowmajor");
+  if (MI == 4 && NI == 4)
+    return check_launch(map == 0 ? "k_gemm_bf16x3_128x128" : map == 1 ? "k_gemm_bf16x3_128x128_zgrid" : "k_gemm_bf16x3_128x128_rowmajor");
+  if (MI == 2 && NI == 4)
+    return check_launch(map == 0 ? "k_gemm_bf16x3_64x128" : map == 1 ? "k_gemm_bf16x3_64x128_zgrid" : "k_gemm_bf16x3_64x128_rowmajor");
+  return check_launch(map == 0 ? "k_gemm_bf16x3_64x160" : map == 1 ? "k_gemm_bf16x3_64x160_zgrid" : "k_gemm_bf16x3_64x160_rowmajor");
 }
 
 template <bool A_KC, bool B_KC, int MI, int NI>
@@ -1108,7 +1122,7 @@ static int launch_panel_wide(const GemmArgs& g, hipStream_t st) {
   const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
   RD_LDS_ATTR((k_gemm_panel_wide<NJ>), lds);
   hipLaunchKernelGGL((k_gemm_panel_wide<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch("k_gemm_panel_wide");
+  return check_launch(g.xcd_swizzle ? "k_gemm_panel_wide" : "k_gemm_panel_wide_rowmajor");
 }
 static int launch_panel_pc(const GemmArgs& g, hipStream_t st) {
   constexpr int NJ = 2, TM = 128, TN = 64 * NJ;
@@ -1116,7 +1130,7 @@ static int launch_panel_pc(const GemmArgs& g, hipStream_t st) {
   const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
   RD_LDS_ATTR((k_gemm_panel_pc<NJ>), lds);
   hipLaunchKernelGGL((k_gemm_panel_pc<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch("k_gemm_panel_pc");
+  return check_launch(g.xcd_swizzle ? "k_gemm_panel_pc" : "k_gemm_panel_pc_rowmajor");
 }
 static int launch_panel(const GemmArgs& g, hipStream_t st) {
   const PanelForm form = panel_form(g);
@@ -1127,7 +1141,7 @@ static int launch_panel(const GemmArgs& g, hipStream_t st) {
   const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
   RD_LDS_ATTR((k_gemm_panel<NJ>), lds);
   hipLaunchKernelGGL((k_gemm_panel<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch("k_gemm_panel");
+  return check_launch(g.xcd_swizzle ? "k_gemm_panel" : "k_gemm_panel_rowmajor");
 }
 
 // padded work / tile efficiency: bigger tiles re-read less and amortise the barrier, but waste

@@ -472,7 +472,7 @@ int launch_rowgemm_kc(const RowGemmArgs& a, hipStream_t st) {
                      (LNB ? (size_t)WV * 2 * KC * 32 * sizeof(float) : 0);
   RD_LDS_ATTR((k_rowgemm<KC, ROWS, NJ, LN, LNB, WV>), lds);
   hipLaunchKernelGGL((k_rowgemm<KC, ROWS, NJ, LN, LNB, WV>), dim3(cdiv(a.M, ROWS)), dim3(64 * WV), lds, st, a);
-  return check_launch("k_rowgemm");
+  return check_launch(LN ? "k_rowgemm_ln" : LNB ? "k_rowgemm_lnb" : "k_rowgemm");      // epilogue / prologue form: what RD_LN_FUSE / RD_LNB_FUSE select
 }
 
 }  // namespace

@@ -2138,7 +2138,8 @@ int launch_add_ln_fwd(const float* x, const float* r, const float* g, const floa
   else hipLaunchKernelGGL(k_add_ln_fwd, dim3(cdiv(M, 4)), dim3(256), 0, st, x, r, g, bta, s_out, y, stats, M, D, p_drop,
                           seed, site, seed_cell());
 #undef RD_LNF
-  return check_launch("k_add_ln_fwd");
+  return check_launch(nv == 1 ? "k_add_ln_fwd_r1" : nv == 2 ? "k_add_ln_fwd_r2" : nv == 3 ? "k_add_ln_fwd_r3" : nv == 4 ? "k_add_ln_fwd_r4"
+                                                                                                                   : "k_add_ln_fwd");
 }
 
 // backward: ds = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat));  dr = ds o dropout mask;
@@ -2343,7 +2344,7 @@ int launch_ln_bwd(const float* dy, const float* s, const float* stats, const flo
   else hipLaunchKernelGGL(k_ln_bwd, dim3(lnb), dim3(256), lds, st, dy, s, stats, g, ds_out, dr_out, part, M, D,
                           p_drop, seed, site, seed_cell());
 #undef RD_LN
-  return check_launch("k_ln_bwd");
+  return check_launch(nv == 1 ? "k_ln_bwd_r1" : nv == 2 ? "k_ln_bwd_r2" : nv == 3 ? "k_ln_bwd_r3" : nv == 4 ? "k_ln_bwd_r4" : "k_ln_bwd");
 }
 
 // code/models_rd.py:366-367,379: agg[b,c] = sum_t r[t,b,c] * (1 - mask[b,t]) / (lengths[b] + 1)
