@@ -444,6 +444,15 @@ int rd_linear_bwd_input_gated(int32_t M, int32_t N, int32_t K, const float* dy, 
  * loss[0] = mean_b(logsumexp(logits[b]) - logits[b, y[b]]); dlogits = (softmax - onehot) / B. */
 int rd_softmax_xent(int32_t B, int32_t C, const float* logits, const int64_t* y, float* loss,
                     float* dlogits, void* stream);
+/* torch.nn.CrossEntropyLoss(weight = w, label_smoothing = eps) (mean) forward + backward in one launch, any C.
+ * crit = [eps, w_0 .. w_{C-1}] (C + 1 floats on the device, read when the kernel runs); p = softmax(logits[b]), W = sum_b w[y[b]]:
+ *   loss[0]      = (1 - eps) sum_b w[y_b] (-log p[b,y_b]) / W + (eps / C) sum_b sum_c w_c (-log p[b,c]) / W
+ *   dlogits[b,c] = (1 - eps) (w[y_b] / W) (p[b,c] - [c == y_b]) + (eps / C) (1 / W) (p[b,c] sum_k w_k - w_c)
+ * W is formed from per-class label counts, sum over c ascending of n_c w_c: the same bits in every launch (and in every workgroup
+ * of rd_head_train_crit).  With eps = 0 and every w_c = 1 loss and dlogits are rd_softmax_xent's bit for bit.  W == 0 gives NaN (as
+ * torch); a label outside [0, C) gives a NaN loss and reads nothing out of bounds.  B < 2^24. */
+int rd_softmax_xent_crit(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
+                         float* dlogits, void* stream);
 /* Tuning knob of the encoder's row-block products (process-global, read when a product is enqueued): bit mask of the kernel
  * variants that run on 32-row instead of 64-row workgroups (1: K <= 160, 2: K <= 288, 4: LayerNorm epilogue, 8: LayerNorm-
  * backward prologue); -1 restores the default (environment RD_RG_ROWS32, else 15).  Results do not depend on it beyond
@@ -470,6 +479,17 @@ int rd_head_train(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, in
                   const int64_t* y, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0,
                   float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
                   void* stream);
+/* rd_head_train with rd_softmax_xent_crit's loss (class weights and label smoothing; crit = [eps, w_0 .. w_{C-1}] on the device,
+ * read when the kernels run: a captured step changes its criterion by a copy into that buffer) in place of the plain mean cross
+ * entropy.  Same two launches, support test and workspace as rd_head_train (criterion instantiations of its first kernel; every
+ * workgroup forms W itself from the labels, in the fixed order above: no atomics, the same bits in every launch).  With eps = 0
+ * and every w_c = 1: logits, dr and the six parameter gradients are rd_head_train's bit for bit.  B < 2^24. */
+int rd_head_train_crit(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
+                       const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w,
+                       const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                       const int64_t* y, const float* crit, float* loss, float* logits, float* g_emb_w, float* g_emb_b,
+                       float* g_w0, float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
+                       void* stream);
 /* The same head around a loss the CALLER evaluates -- the reference's loop: outputs = model(..); loss = criterion(outputs, y);
  * loss.backward() (code/Raindrop.py:317-323).  rd_head_forward stops at the logits; rd_head_backward recomputes the head's
  * forward phases (a masked mean and two small products) and continues from the caller's d loss / d logits [B,C].  Same kernel,

@@ -288,7 +288,78 @@ __global__ __launch_bounds__(256) void k_softmax_xent(const float* __restrict__ 
   }
   if (threadIdx.x == 0) *loss = red[0] * invB;
 }
+
+// torch's CrossEntropyLoss(weight = w, label_smoothing = eps), mean reduction, forward + backward; crit = [eps, w_0 .. w_{C-1}]:
+//   loss    = (1 - eps) sum_b w[y_b] nll_b / W + (eps / C) sum_b sum_c w_c (-log p[b,c]) / W,        W = sum_b w[y_b]
+//   dl[b,c] = (1 - eps) (w[y_b] / W) (p[b,c] - [c == y_b]) + (eps / C) (1 / W) (p[b,c] sum_k w_k - w_c)
+// The arithmetic of the fused head's CRIT instantiations (rd_head.hip): W = sum over c ascending of n_c w_c from per-class label
+// counts (integers: LDS atomics have no order to fix), w[y_b] (1 / W) the last factor of the plain term, the per-sample term scaled
+// by B / W and the sum by 1 / B -- at eps = 0, w = 1 every factor is the plain kernel's, so dlogits and loss are its bits.
+// A label outside [0, C) is counted nowhere, reads no logit and makes the loss NaN.  Any C: classes in chunks of 256.
+__global__ __launch_bounds__(256) void k_softmax_xent_crit(const float* __restrict__ logits, const int64_t* __restrict__ y,
+                                                           const float* __restrict__ crit, float* __restrict__ loss,
+                                                           float* __restrict__ dlogits, int B, int C) {
+  __shared__ float red[256];
+  __shared__ int cnt[256];
+  __shared__ float wsum[2];
+  const int tid = threadIdx.x;
+  const float* w = crit + 1;
+  float Wn = 0.f, sw = 0.f;                                // thread 0's
+  for (int c0 = 0; c0 < C; c0 += 256) {
+    cnt[tid] = 0;
+    __syncthreads();
+    for (int b = tid; b < B; b += 256) {
+      const long yb = (long)y[b];
+      if (yb >= c0 && yb < min(c0 + 256, C)) atomicAdd(&cnt[(int)(yb - c0)], 1);
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int c = c0; c < min(c0 + 256, C); ++c) { Wn += (float)cnt[c - c0] * w[c]; sw += w[c]; }
+    __syncthreads();
+  }
+  if (tid == 0) { wsum[0] = Wn; wsum[1] = sw; }
+  __syncthreads();
+  Wn = wsum[0]; sw = wsum[1];
+  const float eps = crit[0], invB = 1.0f / (float)B, invW = 1.0f / Wn, scale = (float)B / Wn;
+  const float ome = 1.0f - eps, ec = eps / (float)C, es = ec * invW;
+  float acc = 0.f;
+  for (int b = tid; b < B; b += 256) {
+    const float* row = logits + (long)b * C;
+    float m = row[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(row[c] - m);
+    const float lse = m + logf(se);
+    const long yb = (long)y[b];
+    const bool yok = yb >= 0 && yb < C;
+    const int t = yok ? (int)yb : 0;
+    float sm = 0.f;
+    for (int c = 0; c < C; ++c) sm += w[c] * (lse - row[c]);
+    const float wy = w[t], fy = wy * invW;
+    const float term = ome * (wy * (lse - row[t])) + ec * sm;
+    acc += yok ? term * scale : __builtin_nanf("");
+    for (int c = 0; c < C; ++c) {
+      const float p = expf(row[c] - lse);
+      dlogits[(long)b * C + c] = (ome * (p - (c == t ? 1.f : 0.f))) * fy + es * (p * sw - w[c]);
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) *loss = red[0] * invB;
+}
 }  // namespace
+
+extern "C" int rd_softmax_xent_crit(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
+                                    float* dlogits, void* stream) {
+  RD_REQUIRE(B > 0 && C > 0 && B < (1 << 24), "bad dims B=%d C=%d", B, C);
+  RD_REQUIRE(logits && y && crit && loss && dlogits, "NULL tensor");
+  hipLaunchKernelGGL(k_softmax_xent_crit, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, y, crit, loss, dlogits, B, C);
+  return check_launch("k_softmax_xent_crit");
+}
 
 extern "C" int rd_softmax_xent(int32_t B, int32_t C, const float* logits, const int64_t* y, float* loss,
                                float* dlogits, void* stream) {

@@ -43,6 +43,7 @@ struct HeadArgs {
   const int32_t* plan;             // token plan (rd_plan.h) or null: r / dr hold the live rows only, sample b at rows off[rank[b]] + t
   unsigned long long* stamps;      // debug (tools/head_timing.py): clock64 per phase, thread 0 of workgroup 0
   int touch_bytes;                 // > 0: bytes of this kernel's own code requested into L2 at its start (rd_common.h touch_own_code)
+  const float* crit;               // CRIT instantiations (rd_head_train_crit): [eps, w_0 .. w_{C-1}], the criterion's smoothing and class weights
 };
 static unsigned long long* g_head_stamps = nullptr;
 #define HSTAMP(i)                                                                           \
@@ -77,7 +78,12 @@ __device__ __forceinline__ float wsum64(float v) { return wave_sum64_dpp(v); }
 // NRJ / NKI: W0 rows per wave and 64-column slots per lane that are actually FETCHED (16 NRJ >= dh, 64 NKI >= dh).  The generic
 // <16, 4> form requests 256 x 256 clamped elements whatever dh is -- at P19 (dh = 186) 262 KB of address-unit traffic for a 138-KB
 // matrix, and that request phase was the first 5.7 k of the kernel's 30 k cycles (tools/head_timing.py); <12, 3> requests 192 x 192.
-template <int RB, int NRJ, int NKI>
+// CRIT: torch's CrossEntropyLoss(weight = w, label_smoothing = eps), mean reduction, in place of the plain mean cross entropy
+// (rd_head_train_crit; mode 0 only).  An instantiation, not a branch in front of the loss block (DESIGN rule 40): the CRIT = false
+// kernels are the kernels as they were.  A workgroup owns one sample but the mean's denominator W = sum_b w[y_b] belongs to the
+// batch: EVERY workgroup counts the labels per class (wave ballots -- integers, no order to fix) and forms
+// W = sum over c ascending of n_c w_c, so all workgroups and any two launches get the same bits with no atomics and no ticket.
+template <int RB, int NRJ, int NKI, bool CRIT>
 __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
   __shared__ __attribute__((aligned(16))) float feat[RB][HR_LD], hid[RB][HR_LD], dhid[RB][HR_LD], dfeat[RB][HR_LD];
   __shared__ __attribute__((aligned(16))) float red[HR_WAVES * RB * HR_LD];     // mean-phase and wave partials
@@ -87,6 +93,8 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
   // round trips during which the workgroup's other waves sat at the next barrier (SQ counters: 80 % of the wave cycles waiting)
   __shared__ float w2s[16 * HR_LD], embb[HR_LD], b2s[16], embws[HR_EMBW], stats[RB][HR_DS];
   __shared__ long long ys[RB];
+  __shared__ int cntw[CRIT ? HR_WAVES : 1][16];      // CRIT: labels per (wave, class) of the whole batch
+  __shared__ float crs[CRIT ? 17 : 1], nws[CRIT ? 16 : 1];   // CRIT: [eps, w_0 ..]; n_c w_c
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int b0 = blockIdx.x * RB;
   const int T = a.T, B = a.B, D = a.D, dh = a.dh, C = a.C, D4 = D >> 2;
@@ -102,6 +110,8 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
   const int nw2 = C * dh;
   const float pb0 = a.b0[min(tid, dh - 1)], pw2 = a.w2[min(tid, nw2 - 1)], pb2 = a.b2[min(tid, C - 1)];
   const long long py = a.mode == 0 ? a.y[min(b0 + min(tid, RB - 1), B - 1)] : 0;   // uniform
+  long long pyl = 0; float pcr = 0.f;
+  if constexpr (CRIT) { pyl = a.y[min(tid, B - 1)]; pcr = a.crit[min(tid, C)]; }   // the batch's labels (first 1024), the criterion
   float pew = 0.f, peb = 0.f, pst = 0.f;
   if (emb_lds) {                                     // uniform
     const int ne = a.Fe * a.ds, ns = RB * a.ds, ts = min(tid, ns - 1), rs = ts / a.ds;
@@ -173,6 +183,25 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
     }
     for (int i = tid + HR_THR; i < nw2; i += HR_THR) w2s[i] = a.w2[i];                // C * dh > 1024 only
     if (tid < RB) invl[tid] = (b0 + tid < B) ? 1.0f / (float)(plen + 1) : 0.f;
+    if constexpr (CRIT) {
+      if (tid <= C) crs[tid] = pcr;
+      // lane c of every wave counts the wave's labels equal to c (labels outside [0, C) are counted nowhere)
+      // The first 1024 labels (in flight since the top) are NOT an iteration of the loop behind them: a loop with a load inside
+      // waits for everything outstanding -- all of W0 -- before its first use, whatever its trip count (as for the rows below).
+      int cn = 0;
+      for (int c = 0; c < C; ++c) {
+        const int n = __popcll(__ballot(tid < B && pyl == c));
+        if (lane == c) cn += n;
+      }
+      for (int bb = HR_THR; bb < B; bb += HR_THR) {        // uniform; B > 1024 only
+        const long long yv = a.y[min(bb + tid, B - 1)];
+        for (int c = 0; c < C; ++c) {
+          const int n = __popcll(__ballot(bb + tid < B && yv == c));
+          if (lane == c) cn += n;
+        }
+      }
+      if (lane < 16) cntw[wave][lane] = cn;
+    }
   }
   // ---- the rows: first pass (in flight since the top), further passes for T > 4 ntg steps ----
   {
@@ -193,6 +222,14 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
   HSTAMP(2);
   lds_barrier();                                           // LDS only: W0 stays in flight (no thread reads global memory another wrote)
   HSTAMP(3);
+  if constexpr (CRIT) {                                    // the last wave (idle in the mean's second half): n_c w_c per class
+    if (tid >= HR_THR - 64 && lane < C) {
+      int n = 0;
+#pragma unroll
+      for (int q = 0; q < HR_WAVES; ++q) n += cntw[q][lane];
+      nws[lane] = (float)n * crs[1 + lane];
+    }
+  }
   if (tid < P) {
     const int r = tid / D4, c4 = tid - r * D4;
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -299,6 +336,26 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
     const long yb = (long)ys[r];
     const bool yok = yb >= 0 && yb < C;
     const int t = yok ? (int)yb : 0;
+    if constexpr (CRIT) {
+      // loss = (1 - eps) sum_b w[y_b] nll_b / W + (eps / C) sum_b sum_c w_c (-log p[b,c]) / W,  W = sum_b w[y_b] = sum_c n_c w_c.
+      // w[y_b] (1 / W) is the LAST factor of the plain term: at eps = 0, w = 1 it is 1.0f / B and the smoothing term an exact zero,
+      // i.e. dlogits are the plain kernel's bits.  The per-sample term leaves scaled by B / W (exactly 1 there): the trailing
+      // launch's sum / B (head_wgrad_body, unchanged) is then the weighted mean.
+      const float eps = crs[0];
+      float Wn = 0.f, sw = 0.f, sm = 0.f;
+      for (int c = 0; c < C; ++c) { Wn += nws[c]; sw += crs[1 + c]; sm += crs[1 + c] * (lse - lg[r][c]); }
+      const float invW = 1.0f / Wn, wy = crs[1 + t], fy = wy * invW;
+      const float ome = 1.0f - eps, ec = eps / (float)C, es = ec * invW;
+      const float term = ome * (wy * (lse - lg[r][t])) + ec * sm;
+      a.lossr[b] = yok ? term * ((float)B / Wn) : __builtin_nanf("");
+      for (int c = 0; c < C; ++c) {
+        const float p = expf(lg[r][c] - lse);
+        const float d = (ome * (p - (c == t ? 1.f : 0.f))) * fy + es * (p * sw - crs[1 + c]);
+        dl[r][c] = d;
+        a.dlog[(long)b * C + c] = d;
+        a.logits[(long)b * C + c] = lg[r][c];
+      }
+    } else {
     a.lossr[b] = yok ? lse - lg[r][t] : __builtin_nanf("");
     const float invB = 1.0f / (float)B;
     for (int c = 0; c < C; ++c) {
@@ -306,6 +363,7 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
       dl[r][c] = d;
       a.dlog[(long)b * C + c] = d;
       a.logits[(long)b * C + c] = lg[r][c];
+    }
     }
   } else if (tid < RB) {
     for (int c = 0; c < C; ++c) dl[tid][c] = 0.f;
@@ -413,8 +471,8 @@ extern "C" int rd_head_train_supported(int32_t D, int32_t Fe, int32_t C) {
 
 static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
                        const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w, const float* emb_b,
-                       const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* dlog_in,
-                       float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
+                       const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* crit,
+                       const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                        float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream);
 
 extern "C" int rd_head_train(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
@@ -424,8 +482,22 @@ extern "C" int rd_head_train(const rd_shape* s, int32_t D, int32_t d_static, int
                              float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
                              void* stream) {
   RD_REQUIRE(y && loss && logits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
-  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, nullptr, loss, logits, g_emb_w,
-                     g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
+  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, nullptr, nullptr, loss, logits,
+                     g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
+}
+
+// rd_head_train with torch's CrossEntropyLoss(weight = w, label_smoothing = eps), mean reduction, as the loss: crit = [eps, w_0 ..
+// w_{C-1}] on the device, read when the kernel RUNS (a captured step changes its criterion by a copy into that buffer).
+extern "C" int rd_head_train_crit(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
+                                  const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w,
+                                  const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                                  const int64_t* y, const float* crit, float* loss, float* logits, float* g_emb_w, float* g_emb_b,
+                                  float* g_w0, float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+  RD_REQUIRE(y && crit && loss && logits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
+  RD_REQUIRE(s && s->B < (1 << 24), "head_train_crit: B must be below 2^24 (per-class label counts are carried as floats)");
+  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, crit, nullptr, loss, logits,
+                     g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
 }
 
 // The same head as two calls around a loss the CALLER evaluates (the reference's training loop: `criterion(outputs, y)` in
@@ -437,7 +509,7 @@ extern "C" int rd_head_forward(const rd_shape* s, int32_t D, int32_t d_static, i
                                const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
                                float* logits, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(logits, "NULL tensor");
-  return head_launch(1, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, nullptr, logits,
+  return head_launch(1, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, nullptr, nullptr, logits,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 extern "C" int rd_head_backward(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
@@ -446,14 +518,14 @@ extern "C" int rd_head_backward(const rd_shape* s, int32_t D, int32_t d_static, 
                                 const float* dlogits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                                 float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(dlogits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
-  return head_launch(2, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, dlogits, nullptr, nullptr,
+  return head_launch(2, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, dlogits, nullptr, nullptr,
                      g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
 }
 
 static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
                        const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w, const float* emb_b,
-                       const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* dlog_in,
-                       float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
+                       const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* crit,
+                       const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                        float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(s && s->T > 0 && s->B > 0, "bad shape");
   RD_REQUIRE(rd_head_train_supported(D, Fe, C), "head_train: unsupported sizes D=%d Fe=%d C=%d", D, Fe, C);
@@ -465,7 +537,7 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
   hipStream_t st = (hipStream_t)stream;
   HeadArgs a{};
   a.r = r; a.mask = mask; a.lengths = lengths; a.stat = stat; a.emb_w = emb_w; a.emb_b = emb_b; a.w0 = w0; a.b0 = b0; a.w2 = w2;
-  a.b2 = b2; a.y = y; a.logits = logits; a.dr = dr; a.mode = mode; a.dlog_in = dlog_in;
+  a.b2 = b2; a.y = y; a.crit = crit; a.logits = logits; a.dr = dr; a.mode = mode; a.dlog_in = dlog_in;
   float* ws = (float*)workspace;
   a.feat = ws; a.hid = a.feat + (size_t)B * dh; a.dhid = a.hid + (size_t)B * dh; a.demb = a.dhid + (size_t)B * dh;
   a.dlog = a.demb + (size_t)B * dh; a.lossr = a.dlog + (size_t)B * C;
@@ -478,8 +550,11 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
   // (rounds 2 and 4) and is no longer built (its hid phase spilled at 128 registers).
   // W0 fetched as 192 x 192 where that covers it (P19: dh = 186), else 256 x 256 (RD_HEAD_NARROW=0: always the latter)
   static const int narrow = [] { const char* e = getenv("RD_HEAD_NARROW"); return e ? atoi(e) : 1; }();
-  if (narrow && dh <= 192) { a.touch_bytes = touch ? RD_TL_HEAD_P19 : 0; hipLaunchKernelGGL((k_head_rows<1, 12, 3>), dim3(B), dim3(HR_THR), 0, st, a); }
-  else { a.touch_bytes = touch ? RD_TL_HEAD : 0; hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI>), dim3(B), dim3(HR_THR), 0, st, a); }
+  if (crit) {                                                          // the criterion instantiations: touch lengths of their own
+    if (narrow && dh <= 192) { a.touch_bytes = touch ? RD_TL_HEAD_P19_C : 0; hipLaunchKernelGGL((k_head_rows<1, 12, 3, true>), dim3(B), dim3(HR_THR), 0, st, a); }
+    else { a.touch_bytes = touch ? RD_TL_HEAD_C : 0; hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, true>), dim3(B), dim3(HR_THR), 0, st, a); }
+  } else if (narrow && dh <= 192) { a.touch_bytes = touch ? RD_TL_HEAD_P19 : 0; hipLaunchKernelGGL((k_head_rows<1, 12, 3, false>), dim3(B), dim3(HR_THR), 0, st, a); }
+  else { a.touch_bytes = touch ? RD_TL_HEAD : 0; hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, false>), dim3(B), dim3(HR_THR), 0, st, a); }
   int rc = check_launch("k_head_rows");
   if (rc || mode == 1) return rc;
   HwArgs h{};

@@ -285,7 +285,7 @@ def evaluate_captured(model, ds, chunk=2048, group=None, save_free=True):
 
 
 @torch.no_grad()
-def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True):
+def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True, class_weight=None, label_smoothing=0.0):
     """The validation / test block of the reference's loop (`code/Raindrop.py:345-370,385-401`) without leaving the device until
     the end: `evaluate_captured` -> `transform` of the logits with torch ("sigmoid": validation, :349; "softmax": test, :388-389;
     None: the logits) -> `metrics.rank_metrics`, `metrics.confusion` and `rd_softmax_xent` on the TRANSFORMED scores (the
@@ -293,22 +293,31 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     Ranking equals the reference's only under the same transform: it is the transform that produces the ties.
     Returns Python floats `auroc`, `auprc` (binary: column 1, what roc_auc_score(y, probs[:, 1]) gives; more classes: the
     macro mean of the one-vs-rest values; save_free: as in `evaluate_captured`), `loss`, `accuracy`, `precision`, `recall`, `f1` (macro, over all n_classes classes) and
-    numpy arrays `auroc_per_class`, `auprc_per_class`, `confusion` [C, C] (rows = true class).  `ds.y` is required."""
+    numpy arrays `auroc_per_class`, `auprc_per_class`, `confusion` [C, C] (rows = true class).  `ds.y` is required.
+    class_weight / label_smoothing (raindrop_amd.step.criterion_values): `loss` is CrossEntropyLoss(weight=class_weight,
+    label_smoothing=label_smoothing) of the same scores (`rd_softmax_xent_crit`), the training steps' criterion; no other field
+    changes."""
     from . import metrics
+    from .step import criterion_values
     if ds.y is None:
         raise _lib.RaindropHipError("validate needs the dataset's labels (DeviceDataset(..., y=...))")
     if transform not in ("sigmoid", "softmax", None):
         raise ValueError("transform must be 'sigmoid', 'softmax' or None")
     logits = evaluate_captured(model, ds, chunk, group, save_free=save_free)
     N, C = logits.shape
+    crit = criterion_values(class_weight, label_smoothing, C)
     scores = torch.sigmoid(logits) if transform == "sigmoid" else torch.softmax(logits, dim=1) if transform == "softmax" else logits
     scores = scores.contiguous()
     r = metrics.rank_metrics(scores, ds.y)
     cm = metrics.confusion(scores, ds.y)
     loss = torch.empty(1, dtype=torch.float32, device=ds.dev)
     dscores = torch.empty_like(scores)
-    _lib.call("rd_softmax_xent", int(N), int(C), _p(scores), _p(ds.y), _p(loss), _p(dscores),
-              ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    if crit is not None:
+        critd = torch.tensor(crit, dtype=torch.float32, device=ds.dev)
+        _lib.call("rd_softmax_xent_crit", int(N), int(C), _p(scores), _p(ds.y), _p(critd), _p(loss), _p(dscores), st)
+    else:
+        _lib.call("rd_softmax_xent", int(N), int(C), _p(scores), _p(ds.y), _p(loss), _p(dscores), st)
     packed = torch.cat([r["mean"], loss.double(), r["auroc_per_class"], r["auprc_per_class"], cm.reshape(-1).double()]).cpu().numpy()
     auroc_pc, auprc_pc = packed[3:3 + C].copy(), packed[3 + C:3 + 2 * C].copy()
     cmh = np.rint(packed[3 + 2 * C:]).astype(np.int64).reshape(C, C)             # counts < 2^53: exact in float64

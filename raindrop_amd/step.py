@@ -9,7 +9,8 @@ Python in the replay path, every buffer allocated once:
     x_{l+1}          <- rd_encoder_layer_fwd(x_l)               (K2/K3, per layer)
     feat = [agg|emb] <- rd_masked_mean_fwd, rd_linear_fwd       (K5; both write into one buffer)
     logits           <- rd_linear_fwd x2
-    loss, dlogits    <- rd_softmax_xent                         (CrossEntropyLoss fwd+bwd, one launch)
+    loss, dlogits    <- rd_softmax_xent                         (CrossEntropyLoss fwd+bwd, one launch; rd_softmax_xent_crit
+                                                                with class_weight= / label_smoothing=)
     ... the same chain backwards, each gradient written straight into its slice of the flat
     gradient buffer (raindrop_amd.dp.FlatGradAllReduce): no accumulate kernels, no packing copy.
 
@@ -132,6 +133,28 @@ def validate_batch(model, batch, labels=True):
         lo, hi = int(batch["y"].min()), int(batch["y"].max())
         if lo < 0 or hi >= model.n_classes:
             raise _lib.RaindropHipError("TrainStep: labels must lie in [0, %d), got [%d, %d]" % (model.n_classes, lo, hi))
+
+
+def criterion_values(class_weight, label_smoothing, n_classes):
+    """The device criterion buffer's contents `[eps, w_0 .. w_{C-1}]` (include/raindrop_hip.h rd_softmax_xent_crit) for
+    `torch.nn.CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)`, or None for that criterion's defaults
+    (`class_weight=None` and `label_smoothing=0`: the plain mean cross entropy, which needs no buffer).  `class_weight`: a sequence
+    or 1-d tensor of `n_classes` finite values >= 0 (as fp32); `label_smoothing` in [0, 1).  Anything else: ValueError."""
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:                                       # NaN fails both comparisons
+        raise ValueError("label_smoothing must lie in [0, 1), got %r" % (label_smoothing,))
+    if class_weight is None:
+        if eps == 0.0:
+            return None
+        return [eps] + [1.0] * int(n_classes)
+    w = torch.as_tensor(class_weight.detach().cpu() if isinstance(class_weight, torch.Tensor) else list(class_weight),
+                        dtype=torch.float64)
+    if w.dim() != 1 or w.numel() != int(n_classes):
+        raise ValueError("class_weight must hold n_classes = %d values, got shape %s" % (n_classes, tuple(w.shape)))
+    w32 = w.to(torch.float32)
+    if not bool(torch.isfinite(w32).all()) or bool((w32 < 0).any()):
+        raise ValueError("class_weight must be finite and >= 0, got %s" % (w.tolist(),))
+    return [eps] + [float(v) for v in w32.tolist()]
 
 
 class SensorStage:
@@ -268,11 +291,21 @@ class Step:
     }
 
     def __init__(self, model, batch, sensor, flat=None, has_backward=True, labels=True, p_drop=None, seed=1234, token_plan=None,
-                 save_free=True):
+                 save_free=True, class_weight=None, label_smoothing=0.0):
         """sensor: the sensor-stage object of the model's branch.  has_backward=False: a forward-only step -- no gradient tables,
         no dx / dfeat / dhid / dlogits / loss / weight-gradient workspace, no backward workspaces, seed cell or trailing riders,
         dropout off whatever model.training says, the eager surface's head operator by operator, and (save_free, the default) the
-        inference forward of every stage on buffers of the inference sizes.  save_free has no meaning with a backward."""
+        inference forward of every stage on buffers of the inference sizes.  save_free has no meaning with a backward.
+        class_weight / label_smoothing: the step's loss is torch.nn.CrossEntropyLoss(weight=class_weight,
+        label_smoothing=label_smoothing) (mean reduction; `criterion_values` has the accepted values, ValueError otherwise) --
+        the step then owns a device buffer `crit` = [eps, w_0 ..] and its head runs the `_crit` entry points (rd_head_train_crit /
+        rd_softmax_xent_crit), which read that buffer when they RUN: `set_criterion` changes both between replays.  The mean's
+        denominator is the sum of w[y_b] over THIS step's batch: under data parallelism every rank normalises by its own shard
+        and the gradient all-reduce averages the ranks, which is what DistributedDataParallel with torch's criterion computes.
+        Both at their defaults: the plain mean cross entropy, no buffer, the launches the step always enqueued."""
+        self._crit_vals = criterion_values(class_weight, label_smoothing, model.n_classes)
+        if self._crit_vals is not None and not (has_backward and labels):
+            raise ValueError("class_weight / label_smoothing belong to a step that evaluates the loss itself (a training step with labels)")
         self.model, self.flat, self.batch, self.sensor, self.has_backward = model, flat, batch, sensor, bool(has_backward)
         self.infer = bool(save_free) and not self.has_backward
         self.dev = batch["src"].device
@@ -369,6 +402,11 @@ class Step:
         # Forward-only: the eager surface's head in both layouts (raindrop_amd/evalstep.py has the reason)
         self.head_fused = bwd and bool(lib.rd_head_train_supported(D, self.Fe, m.n_classes))
         self.head_ws = a.u8(lib.rd_head_train_workspace_bytes(B, dh, m.n_classes)) if self.head_fused else None
+        # the criterion [eps, w_0 .. w_{C-1}] of a step with class weights / label smoothing (None: the plain mean cross entropy)
+        self.crit = None
+        if getattr(self, "_crit_vals", None) is not None:
+            self.crit = a.zeros((m.n_classes + 1,))
+            self.crit.copy_(torch.tensor(self._crit_vals, dtype=torch.float32))
         tables = lambda T_: [_lib.RdEncoderPtrs(*[T_["transformer_encoder.layers.%d.%s" % (i, n)].data_ptr() for n in ops.ENC_PARAM_NAMES])
                              for i in range(self.nl)]
         self.enc_w, self.enc_g = tables(self.P), tables(self.G) if bwd else []
@@ -446,7 +484,24 @@ class Step:
         if not self.head_fused:
             return self._head_by_operator()
         common, tail = self._fused_head_args()
+        if self.crit is not None:                                          # class weights / label smoothing: the criterion instantiation
+            return self._call("rd_head_train_crit", *common, _p(self.batch["y"]), _p(self.crit), _p(self.loss), _p(self.logits), *tail)
         self._call("rd_head_train", *common, _p(self.batch["y"]), _p(self.loss), _p(self.logits), *tail)
+
+    def set_criterion(self, class_weight=None, label_smoothing=0.0):
+        """Change the step's loss to CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing) between steps: a copy of
+        C + 1 floats into the device buffer the head kernels read when they run, like `lr` -- never a new capture.  None / 0 mean
+        what they mean to the constructor (all weights 1 / no smoothing).  Only a step BUILT with a criterion has that buffer and
+        the kernels that read it; any other refuses (build a new step)."""
+        if self.crit is None:
+            raise _lib.RaindropHipError("set_criterion: this step was built for the plain mean cross entropy (class_weight=None, "
+                                        "label_smoothing=0) and its captured head reads no criterion buffer; build the step with "
+                                        "class_weight=... or label_smoothing=... to change them between steps")
+        vals = criterion_values(class_weight, label_smoothing, self.model.n_classes)
+        if vals is None:
+            vals = [0.0] + [1.0] * self.model.n_classes
+        self._crit_vals = vals
+        self.crit.copy_(torch.tensor(vals, dtype=torch.float32))
 
     def _head_fwd(self):
         """The head around a loss the caller evaluates (or none): up to self.logits."""
@@ -470,7 +525,10 @@ class Step:
         c = self._call
         self._head_forward_by_operator()
         # ---------------- loss: mean cross entropy (code/Raindrop.py:255,322) and its gradient ----------
-        c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
+        if self.crit is not None:
+            c("rd_softmax_xent_crit", B, C, _p(self.logits), _p(b["y"]), _p(self.crit), _p(self.loss), _p(self.dlogits), st)
+        else:
+            c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
         # ---------------- backward ----------------
         ws, wsn = _p(self.wg_ws), self.wg_ws.numel()
         c("rd_linear_bwd_weight", B, C, dh, _p(self.dlogits), C, _p(self.hid), dh, _p(G["mlp_static.2.weight"]),
@@ -539,10 +597,15 @@ class TrainStep(Step):
     TUNE_WAVES = (12, 15)
 
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 module_mode=False, sensor=None):
+                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
         live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
         of device tensors that are REUSED every step (copy new data into them).
+        class_weight, label_smoothing: the loss is torch.nn.CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
+        instead of the plain mean cross entropy, in every form of the step (eager run(), the captured graph, capture_full, the
+        two-graph data-parallel form); `set_criterion` changes both between replays without a new capture.  Each rank normalises by
+        the weights of its OWN shard's labels and the gradient all-reduce averages the ranks -- DistributedDataParallel's result
+        with torch's criterion, not the single-process result on the global batch (`Step.__init__`).
         token_plan: store and process only the live (sample, step) rows (include/raindrop_hip.h "token plan": the padding mask of
         code/models_rd.py:298-299 applied as a layout; same logits, loss and gradients).  None = environment RD_TOKEN_PLAN
         (default on) where the shape supports it.
@@ -560,7 +623,7 @@ class TrainStep(Step):
         self.split = bool(split) and len(model.transformer_encoder.layers) >= 2
         self.autotune, self.tuned_rows32, self.tuned_waves16 = bool(autotune), None, None
         super().__init__(model, batch, sensor or SensorStage(), flat=flat, labels=not self.module_mode, p_drop=p_drop, seed=seed,
-                         token_plan=token_plan)
+                         token_plan=token_plan, class_weight=class_weight, label_smoothing=label_smoothing)
         if self.split:
             self._check_split_order()
         self.graph = self.graph_b = self.graph_full = self._full_opt = self._full_hyper = None
@@ -837,9 +900,13 @@ class AutogradStep:
     rd_structure_distance_bwd -> rd_graph_beta_bwd_alpha).  Any other model would add lambda * 0 and is refused.  0: CE alone,
     the same capture as without the argument."""
 
-    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234, distance_weight=0.0):
+    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234, distance_weight=0.0, class_weight=None, label_smoothing=0.0):
+        """class_weight / label_smoothing (`criterion_values`): the captured loss is torch.nn.functional.cross_entropy(logits, y,
+        weight=class_weight, label_smoothing=label_smoothing) (`_criterion`)."""
+        crit = criterion_values(class_weight, label_smoothing, model.n_classes)
         self.model, self.batch = model, batch
         self.dev = batch["src"].device
+        self._crit = None if crit is None else (crit[0], torch.tensor(crit[1:], dtype=torch.float32, device=self.dev))
         self.distance_weight = float(distance_weight)
         if self.distance_weight != 0.0 and not (getattr(model, "use_beta", False) and getattr(model, "compute_distance", False)):
             raise _lib.RaindropHipError("AutogradStep(distance_weight=%g): the structure distance is the constant 0 unless the model "
@@ -857,10 +924,28 @@ class AutogradStep:
         model.graph_step = False                                  # the operator surface is what gets captured
         self._capture()
 
+    def _criterion(self, logits, y):
+        """The step's cross entropy.  Without smoothing it is torch's own call (with `weight` when given).  With smoothing AND
+        weights torch's fused call cannot be captured: its weighted mean gathers the weights through `masked_select`, whose
+        output size is read back on the host ("operation not permitted when stream is capturing").  The same value -- mean
+        reduction, no ignore_index -- written out in operations of static shape:
+            (1 - eps) sum_b w[y_b] (-logp[b,y_b]) / W + (eps / C) sum_b sum_c w_c (-logp[b,c]) / W,   W = sum_b w[y_b]."""
+        if self._crit is None:
+            return torch.nn.functional.cross_entropy(logits, y)
+        eps, w = self._crit
+        if eps == 0.0:
+            return torch.nn.functional.cross_entropy(logits, y, weight=w)
+        logp = torch.log_softmax(logits, 1)
+        wy = w[y]
+        W = wy.sum()
+        nll = -(wy * logp.gather(1, y.unsqueeze(1)).squeeze(1)).sum() / W
+        smooth = -(logp * w).sum() / W
+        return (1.0 - eps) * nll + (eps / logits.shape[1]) * smooth
+
     def _one(self):
         b = self.batch
         logits, distance, _ = self.model(b["src"], b["static"], b["times"], b["lengths"])
-        loss = torch.nn.functional.cross_entropy(logits, b["y"])
+        loss = self._criterion(logits, b["y"])
         if self.distance_weight != 0.0:
             loss = loss + self.distance_weight * distance
         loss.backward()
