@@ -423,6 +423,35 @@ int rd_adam_step_clip(int64_t n, float* param, const float* grad, float* exp_avg
 int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
                           float eps, const void* state, const void* partial, size_t partial_bytes, void* clip, void* stream);
 
+/* Exponential moving average of the weights inside the update's own launch (raindrop_amd.optim.FlatAdam(ema_decay=...)): the four
+ * updates above with two more arguments, `ema` (n floats, 16-byte aligned) and `ema_cell` (64 bytes, 16-byte aligned).  After the
+ * Adam update of element i, in fp32, in the thread that wrote p_new:  ema[i] += c_t * (p_new[i] - ema[i]),  c_t = 1 - d_t rounded to
+ * float once, d_t formed in double by every workgroup: d_t = d, or with warm-up min(d, (1 + k) / (10 + k)), k = the number of EMA
+ * updates so far (0-based; not the number of steps).  param, exp_avg, exp_avg_sq get the bits of the twin without `ema`.
+ * `ema_cell`: eight doubles {d, warm-up, k0, k1, 0, 0, 0, 0}.  Slot 0: the decay d, written by the caller and read by the launch (a new
+ * decay is an 8-byte copy, not a new capture).  Slot 1: the warm-up flag, 0 or 1, the caller's likewise.  Slots 2 and 3 hold k and
+ * belong to the launch: with s the step number (`step` of the host forms; t of `state`, which an earlier launch advanced, for the
+ * _dev forms) every workgroup reads k from slot 2 + (s & 1) and one thread writes k + 1 to slot 2 + ((s + 1) & 1) -- no workgroup
+ * reads a word another workgroup of the same launch writes, no atomics, two replays from the same state give the same bits.  The
+ * caller initialises BOTH slots to the count (0), and again whenever it makes the step number jump (steps must follow each other by
+ * one for the parity to select the slot last written).  A step the clip forms skip (non-finite gradient norm) stores nothing to
+ * `ema` and writes k, not k + 1: param, exp_avg, exp_avg_sq and ema keep their bits and the skipped step is no update.
+ * RD_EINVAL before any launch: NULL or misaligned pointers, n <= 0, and what the twin refuses. */
+int rd_adam_step_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, int64_t step, float* ema, void* ema_cell, void* stream);
+int rd_adam_step_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
+                         float eps, const void* state, float* ema, void* ema_cell, void* stream);
+int rd_adam_step_clip_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int64_t step, const void* partial, size_t partial_bytes,
+                          void* clip, float* ema, void* ema_cell, void* stream);
+int rd_adam_step_clip_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                              float beta2, float eps, const void* state, const void* partial, size_t partial_bytes, void* clip,
+                              float* ema, void* ema_cell, void* stream);
+/* a <-> b over n floats in place (16-byte accesses, a scalar tail; capturable): FlatAdam.swap_ema exchanges the flat parameters and
+ * their average, so that whatever holds the parameters' addresses evaluates the average.  a, b: 16-byte aligned, not overlapping.
+ * RD_EINVAL: NULL or misaligned pointers, n <= 0. */
+int rd_swap_f32(int64_t n, float* a, float* b, void* stream);
+
 /* ---- generic dense pieces (used by the temporal encoder, the head and the large-K path) ---- */
 
 /* y[M,N] = act(x[M,K] W[N,K]^T + b)   (torch.nn.functional.linear; act: 0 none, 1 relu). */

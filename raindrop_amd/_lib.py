@@ -114,6 +114,14 @@ SIGNATURES = {
     "rd_adam_step_clip": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, ctypes.c_int64,
                                     _P, c_size_t, _P, _P]),
     "rd_adam_step_clip_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P]),
+    # weight averaging inside the update's launch (raindrop_amd.optim.FlatAdam(ema_decay=...)): the twins take `ema`, `ema_cell` in front of the stream
+    "rd_adam_step_ema": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float,
+                                   ctypes.c_int64, _P, _P, _P]),
+    "rd_adam_step_ema_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P, _P]),
+    "rd_adam_step_clip_ema": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, ctypes.c_int64,
+                                        _P, c_size_t, _P, _P, _P, _P]),
+    "rd_adam_step_clip_ema_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P, _P, _P]),
+    "rd_swap_f32": (c_int32, [ctypes.c_int64, _P, _P, _P]),
     "rd_linear_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_fwd_fp32": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_bwd_input": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P]),

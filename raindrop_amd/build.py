@@ -56,7 +56,7 @@ TOUCH_SITES = [
     ("K1_INF_P19", r"k_msg_fwd_fusedILi3ELi34ELi60ELb0ELb0E", "step"), ("ATTN_INF", r"k_attn_fwd_fusedILi\d+ELi\d+ELb0ELb0E", "step"),
     ("ATTN_INF_B", r"k_attn_fwd_fusedILi\d+ELi\d+ELb1ELb0E", "step"),
     ("EF_INF_P19", r"k_enc_post_inferILi152ELi272ELb0E", "step"), ("EF_INF_P19_B", r"k_enc_post_inferILi152ELi272ELb1E", "step"),
-    ("DW", r"4k_dwE", "step"), ("DW_REDUCE", r"k_dw_reduce", "step"), ("ADAM", r"6k_adamE", "step"), ("ADAM_DEV", r"10k_adam_devE", "step"),
+    ("DW", r"4k_dwE", "step"), ("DW_REDUCE", r"k_dw_reduce", "step"), ("ADAM", r"6k_adamILb0EE", "step"), ("ADAM_DEV", r"10k_adam_devILb0EE", "step"),   # (EMA = false: the weight-averaging twins touch nothing)
     ("WSPLIT", r"k_wsplit", "step"), ("TWG", r"5k_twgILb0E", "step"), ("TWG_ONE", r"5k_twgILb1E", "step"),
     ("HEAD_P19", r"k_head_rowsILi1ELi12ELi3ELb0E", "step"), ("HEAD", r"k_head_rowsILi1ELi16ELi4ELb0E", "step"),
     # the criterion twins (template flag CRIT: class weights / label smoothing): lengths of their own, the plain ones keep theirs

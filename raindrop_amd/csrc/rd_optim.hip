@@ -6,32 +6,72 @@
 namespace rd {
 namespace {
 
+// (the device step state: the comment in front of k_adam_dev)
+struct AdamState { double t, p1, p2, lr, pad0, wd, pad1, pad2; };
+// ---- exponential moving average of the weights (DESIGN.md "Weight averaging") ------------------------------------------------------
+// ema[i] += c_t (p_new[i] - ema[i]) in the thread that holds p_new in a register: one more flat buffer read and written by the update's
+// own launch, no launch of its own.  A template flag of the four update kernels (rule 40): the EMA = false instantiations are the
+// kernels as they were, instruction for instruction -- three unused trailing arguments move the kernarg offset of the hidden
+// block-size word, one immediate (profiles/ema_isa_diff.txt).  (No own-code touch in the EMA = true ones: the table has no site.)
+// The EMA cell, eight doubles {d, warm-up, k[0], k[1], 0, 0, 0, 0}: slots 0 and 1 are read by every workgroup and written by the host
+// only (a new decay is an 8-byte copy, not a new capture).  k, the number of EMA updates so far, lives in TWO slots selected by the
+// parity of the step number s (host forms: the `step` argument; _dev forms: t of the step state, which an EARLIER launch advanced):
+// every workgroup reads k from slot s & 1, thread 0 of workgroup 0 writes k + 1 -- or k, when the non-finite guard skips the step --
+// to slot (s + 1) & 1, where the next step reads it.  No workgroup reads a word another workgroup of the same launch writes (the
+// rule of k_adam_dev's step state), whether the update happens is decided in THIS launch, and there is no atomic.
+struct EmaCell { double decay, warmup, k[2], pad0, pad1, pad2, pad3; };
+
+// c_t = 1 - d_t as a float, d_t = d or min(d, (1 + k) / (10 + k)) formed in double: the same bits in every workgroup
+__device__ __forceinline__ float ema_coef(const EmaCell* cell, long step, double& k) {
+  const double d = cell->decay;
+  k = cell->k[step & 1];
+  const double w = (1.0 + k) / (10.0 + k);
+  const double dt = (cell->warmup != 0.0 && w < d) ? w : d;
+  return (float)(1.0 - dt);
+}
+__device__ __forceinline__ void ema_count(EmaCell* cell, long step, double k_next) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) cell->k[(step + 1) & 1] = k_next;
+}
+
+template <bool EMA>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, long n, float lr,
-                                              float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  RD_TOUCH_CODE_FIRST(RD_TL_ADAM, blockIdx.x, 64);             // own code -> L2 by the first workgroups (rd_common.h; 3 012-byte kernel)
+                                              float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt,
+                                              float* __restrict__ ema, EmaCell* cell, long step) {
+  float ce = 0.f;
+  if (EMA) {
+    double k;
+    ce = ema_coef(cell, step, k);
+    ema_count(cell, step, k + 1.0);
+  }
+  if (!EMA) RD_TOUCH_CODE_FIRST(RD_TL_ADAM, blockIdx.x, 64);            // own code -> L2 by the first workgroups (rd_common.h; 3 012-byte kernel)
   const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
   if (i4 >= n) return;
   const float step_size = lr / bc1;
   if (i4 + 3 < n) {
     float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
     float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+    float4 ee;
+    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
+    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const float gr = G[c] + wd * P[c];
       M[c] = b1 * M[c] + (1.f - b1) * gr;
       V[c] = b2 * V[c] + (1.f - b2) * gr * gr;
       P[c] -= step_size * M[c] / (sqrtf(V[c]) / bc2_sqrt + eps);
+      if (EMA) E[c] += ce * (P[c] - E[c]);
     }
     *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
     *reinterpret_cast<float4*>(v + i4) = vv;
+    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
   } else {
     for (long i = i4; i < n; ++i) {
       const float gr = g[i] + wd * p[i];
       m[i] = b1 * m[i] + (1.f - b1) * gr;
       v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
       p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
+      if (EMA) ema[i] += ce * (p[i] - ema[i]);
     }
   }
 }
@@ -50,11 +90,18 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 // return of a device-scope atomic on ONE line, the last one for a fence and a second atomic on top).
 // lr and weight_decay live in the cell too: a learning-rate schedule is an 8-byte copy, not a new capture.
 // (beta^t by repeated multiplication differs from pow() by ~t 2^-53 relative: far below the float the correction is rounded to.)
-struct AdamState { double t, p1, p2, lr, pad0, wd, pad1, pad2; };
+template <bool EMA>
 __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                   float* __restrict__ v, long n, float b1, float b2, float eps,
-                                                  const AdamState* __restrict__ state) {
-  RD_TOUCH_CODE_FIRST(RD_TL_ADAM_DEV, blockIdx.x, 64);
+                                                  const AdamState* __restrict__ state, float* __restrict__ ema, EmaCell* cell) {
+  float ce = 0.f;
+  if (EMA) {                                                     // the step number: t of the step being applied
+    const long step = (long)state->t;
+    double k;
+    ce = ema_coef(cell, step, k);
+    ema_count(cell, step, k + 1.0);
+  }
+  if (!EMA) RD_TOUCH_CODE_FIRST(RD_TL_ADAM_DEV, blockIdx.x, 64);
   const float lr = (float)state->lr, wd = (float)state->wd;
   const float bc1 = (float)(1.0 - state->p1), bc2_sqrt = (float)sqrt(1.0 - state->p2);
   const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
@@ -63,22 +110,27 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const f
   if (i4 + 3 < n) {
     float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
     float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+    float4 ee;
+    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
+    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
 #pragma unroll
     for (int c4 = 0; c4 < 4; ++c4) {
       const float gr = G[c4] + wd * P[c4];
       M[c4] = b1 * M[c4] + (1.f - b1) * gr;
       V[c4] = b2 * V[c4] + (1.f - b2) * gr * gr;
       P[c4] -= step_size * M[c4] / (sqrtf(V[c4]) / bc2_sqrt + eps);
+      if (EMA) E[c4] += ce * (P[c4] - E[c4]);
     }
     *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
     *reinterpret_cast<float4*>(v + i4) = vv;
+    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
   } else {
     for (long i = i4; i < n; ++i) {
       const float gr = g[i] + wd * p[i];
       m[i] = b1 * m[i] + (1.f - b1) * gr;
       v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
       p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
+      if (EMA) ema[i] += ce * (p[i] - ema[i]);
     }
   }
 }
@@ -149,11 +201,12 @@ struct ClipCell { double max_norm, last_norm, last_scale, skipped, clipped, pad0
 // k_adam_dev (DEV: step state in the device cell) / k_adam (host-computed corrections) on the clipped gradient.  The scale is its own
 // rounded multiply: at scale == 1 `gs` IS g and everything behind it is the expression of k_adam / k_adam_dev -- the same bits.
 // Weight decay is added AFTER the scale (torch clips the raw gradient; Adam adds wd * p inside its step).
-template <bool DEV>
+template <bool DEV, bool EMA>
 __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n, float b1, float b2, float eps,
                                                    const AdamState* __restrict__ state, float lr_h, float wd_h, float bc1_h,
-                                                   float bc2_sqrt_h, const double* __restrict__ partial, double* clip) {
+                                                   float bc2_sqrt_h, const double* __restrict__ partial, double* clip,
+                                                   float* __restrict__ ema, EmaCell* cell, long step_h) {
   double sum = 0.0;
   for (int k = 0; k < kClipGrid; ++k) sum += partial[k];
   const double max_norm = clip[0];
@@ -166,7 +219,14 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
     if (!finite) clip[3] += 1.0;
     else if (sc < 1.0) clip[4] += 1.0;
   }
-  if (!finite) return;                                           // uniform over the launch: p, m, v keep their bits
+  float ce = 0.f;
+  if (EMA) {                                                     // a skipped step is no update of the average: k moves on unchanged
+    const long step = DEV ? (long)state->t : step_h;
+    double k;
+    ce = ema_coef(cell, step, k);
+    ema_count(cell, step, finite ? k + 1.0 : k);
+  }
+  if (!finite) return;                                           // uniform over the launch: p, m, v (and ema) keep their bits
   const float scale = (float)sc;
   float lr, wd, bc1, bc2_sqrt;
   if (DEV) {
@@ -181,7 +241,9 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
   if (i4 + 3 < n) {
     float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
     float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+    float4 ee;
+    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
+    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
 #pragma unroll
     for (int c4 = 0; c4 < 4; ++c4) {
       const float gs = mul_rounded(G[c4], scale);
@@ -189,9 +251,11 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
       M[c4] = b1 * M[c4] + (1.f - b1) * gr;
       V[c4] = b2 * V[c4] + (1.f - b2) * gr * gr;
       P[c4] -= step_size * M[c4] / (sqrtf(V[c4]) / bc2_sqrt + eps);
+      if (EMA) E[c4] += ce * (P[c4] - E[c4]);
     }
     *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
     *reinterpret_cast<float4*>(v + i4) = vv;
+    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
   } else {
     for (long i = i4; i < n; ++i) {
       const float gs = mul_rounded(g[i], scale);
@@ -199,7 +263,21 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
       m[i] = b1 * m[i] + (1.f - b1) * gr;
       v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
       p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
+      if (EMA) ema[i] += ce * (p[i] - ema[i]);
     }
+  }
+}
+
+// a <-> b over n floats, 16 bytes per thread and a scalar tail behind the last whole float4 (FlatAdam.swap_ema: the flat parameters and
+// their average change places IN PLACE, so every holder of a parameter address -- EvalStep, feed.validate -- reads the other one)
+__global__ __launch_bounds__(256) void k_swap_f32(float* __restrict__ a, float* __restrict__ b, long n) {
+  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  if (i4 + 3 < n) {
+    const float4 x = *reinterpret_cast<float4*>(a + i4), y = *reinterpret_cast<float4*>(b + i4);
+    *reinterpret_cast<float4*>(a + i4) = y; *reinterpret_cast<float4*>(b + i4) = x;
+  } else {
+    for (long i = i4; i < n; ++i) { const float x = a[i]; a[i] = b[i]; b[i] = x; }
   }
 }
 
@@ -235,8 +313,9 @@ extern "C" int rd_adam_step(int64_t n, float* param, const float* grad, float* e
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2));
+  hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
+                     (float*)nullptr, (EmaCell*)nullptr, 0L);
   return check_launch("k_adam");
 }
 
@@ -250,8 +329,8 @@ extern "C" int rd_adam_step_dev(int64_t n, float* param, const float* grad, floa
   RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
                reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(state)) & 15) == 0, "buffers must be 16-byte aligned");
   const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam_dev, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state);
+  hipLaunchKernelGGL(k_adam_dev<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, (float*)nullptr, (EmaCell*)nullptr);
   return check_launch("k_adam_dev");
 }
 
@@ -293,9 +372,9 @@ extern "C" int rd_adam_step_clip(int64_t n, float* param, const float* grad, flo
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam_clip<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+  hipLaunchKernelGGL((k_adam_clip<false, false>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
                      exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)nullptr, lr, weight_decay, (float)bc1,
-                     (float)sqrt(bc2), (const double*)partial, (double*)clip);
+                     (float)sqrt(bc2), (const double*)partial, (double*)clip, (float*)nullptr, (EmaCell*)nullptr, 0L);
   return check_launch("k_adam_clip");
 }
 
@@ -305,8 +384,83 @@ extern "C" int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad,
   RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
   if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
   const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam_clip<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+  hipLaunchKernelGGL((k_adam_clip<true, false>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
                      exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, 0.f, 0.f, 0.f, 0.f,
-                     (const double*)partial, (double*)clip);
+                     (const double*)partial, (double*)clip, (float*)nullptr, (EmaCell*)nullptr, 0L);
   return check_launch("k_adam_clip_dev");
+}
+
+// ---- exponential moving average of the weights: the EMA twins of the four updates, and the in-place exchange -------------------------
+static int ema_args_ok(int64_t n, const float* ema, const void* ema_cell) {
+  RD_REQUIRE(n > 0, "bad n");
+  RD_REQUIRE(ema && ema_cell, "NULL ema / ema_cell");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(ema_cell)) & 15) == 0, "ema / ema_cell must be 16-byte aligned");
+  return RD_OK;
+}
+
+extern "C" int rd_adam_step_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int64_t step, float* ema, void* ema_cell, void* stream) {
+  RD_REQUIRE(n > 0 && step >= 1, "bad n / step");
+  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
+               reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
+             "buffers must be 16-byte aligned");
+  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), ema, (EmaCell*)ema_cell,
+                     (long)step);
+  return check_launch("k_adam_ema");
+}
+
+extern "C" int rd_adam_step_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                    float beta2, float eps, const void* state, float* ema, void* ema_cell, void* stream) {
+  RD_REQUIRE(n > 0 && state != nullptr, "bad n / NULL optimizer state");
+  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
+               reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(state)) & 15) == 0, "buffers must be 16-byte aligned");
+  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_adam_dev<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                     exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, ema, (EmaCell*)ema_cell);
+  return check_launch("k_adam_dev_ema");
+}
+
+extern "C" int rd_adam_step_clip_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
+                                     size_t partial_bytes, void* clip, float* ema, void* ema_cell, void* stream) {
+  RD_REQUIRE(step >= 1, "bad step");
+  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
+  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL((k_adam_clip<false, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)nullptr, lr, weight_decay, (float)bc1,
+                     (float)sqrt(bc2), (const double*)partial, (double*)clip, ema, (EmaCell*)ema_cell, (long)step);
+  return check_launch("k_adam_clip_ema");
+}
+
+extern "C" int rd_adam_step_clip_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                         float beta2, float eps, const void* state, const void* partial, size_t partial_bytes,
+                                         void* clip, float* ema, void* ema_cell, void* stream) {
+  RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
+  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
+  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL((k_adam_clip<true, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
+                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, 0.f, 0.f, 0.f, 0.f,
+                     (const double*)partial, (double*)clip, ema, (EmaCell*)ema_cell, 0L);
+  return check_launch("k_adam_clip_ema_dev");
+}
+
+extern "C" int rd_swap_f32(int64_t n, float* a, float* b, void* stream) {
+  RD_REQUIRE(n > 0, "bad n");
+  RD_REQUIRE(a && b, "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0, "buffers must be 16-byte aligned");
+  const long threads = (n + 3) / 4;
+  hipLaunchKernelGGL(k_swap_f32, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, (long)n);
+  return check_launch("k_swap_f32");
 }

@@ -326,3 +326,12 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     return {"auroc": float(auroc_pc[1] if binary else packed[0]), "auprc": float(auprc_pc[1] if binary else packed[1]),
             "loss": float(packed[2]), "accuracy": acc, "precision": prec, "recall": rec, "f1": f1,
             "auroc_per_class": auroc_pc, "auprc_per_class": auprc_pc, "confusion": cmh}
+
+
+def validate_ema(model, ds, opt, **kw):
+    """`validate(model, ds, **kw)` on the AVERAGED weights of `opt` (raindrop_amd.optim.FlatAdam(ema_decay=...)): the flat
+    parameters and their average change places for the duration (`opt.ema_weights()`: two in-place exchanges, rd_swap_f32), and the
+    cached captured forwards, which read the parameters by address, are replayed as they are -- no new capture, no copy of the
+    model.  The training weights are back, bit for bit, when it returns."""
+    with opt.ema_weights():
+        return validate(model, ds, **kw)

@@ -5,6 +5,7 @@ with this model unchanged.  `FlatAdam` is the fast path: because the live parame
 gradients already live in two flat buffers, the whole update is ONE elementwise HIP kernel
 (rd_adam_step) instead of a 35-tensor multi-tensor launch.  Same formula as torch (no amsgrad).
 """
+import contextlib
 import ctypes
 import math
 
@@ -18,6 +19,13 @@ def _check_max_grad_norm(x):
     if isinstance(x, bool) or not isinstance(x, (int, float)) or not x > 0:          # NaN fails `x > 0`
         raise ValueError("max_grad_norm must be None, a positive float or math.inf, got %r" % (x,))
     return float(x)
+
+
+def _check_ema_decay(x):
+    """a float in [0, 1)"""
+    if isinstance(x, bool) or not isinstance(x, float) or not 0.0 <= x < 1.0:          # NaN fails the comparison
+        raise ValueError("ema_decay must be None or a float in [0, 1), got %r" % (x,))
+    return x
 
 
 class FlatAdam:
@@ -36,13 +44,32 @@ class FlatAdam:
     as a step: `t` and the device step state {t, beta^t} advance (the state is advanced by the step's first launch, long before
     the norm is known), so `self.t == device_steps()` always holds and the bias corrections of later steps are those of t + 1.
     torch.amp's GradScaler does NOT count a skipped step; after k skips the corrections here are k steps ahead of a GradScaler
-    loop's (they tend to 1 either way)."""
+    loop's (they tend to 1 either way).
 
-    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+    ema_decay (default None: off -- the launches, the code path, `hyper()` and the `state_dict()` keys of an optimizer built without
+    the keyword): an exponential moving average of the flat parameters, `self.ema`, kept INSIDE the update's launch (the EMA twins
+    rd_adam_step[_clip]_ema[_dev]: the thread that wrote p_new does ema += (1 - d_t)(p_new - ema) in fp32), so it exists in
+    `step()`, `step_captured()` and a whole-step hipGraph alike, with no launch added; it combines with `max_grad_norm`.  `ema`
+    starts as a copy of the parameters (torch.optim.swa_utils.AveragedModel's first call).  d_t = ema_decay, or with
+    `ema_warmup=True` min(ema_decay, (1 + k) / (10 + k)) with k the number of EMA updates so far, counted on the device
+    (`ema_updates()`): a step the non-finite guard skips leaves `ema` untouched and is not counted.  The decay lives in a device
+    cell: `set_ema_decay(d)` (or assigning `ema_decay` before `TrainStep.run_full`) is an 8-byte copy, not a new capture; switching
+    averaging on or off, or the warm-up, is a new capture / another optimizer.
+    `swap_ema()` exchanges parameters and average IN PLACE (rd_swap_f32): whatever holds the parameters' addresses -- a captured
+    `EvalStep`, `feed.validate`, the eager forward -- then evaluates the average; `ema_weights()` is the context manager around two
+    swaps.  While swapped, `step()` / `step_captured()` (and the whole-step replays) raise instead of training the average.
+    The average covers the flat parameters, which is everything: the model has no buffers (no batch-norm statistics)."""
+
+    def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
+                 ema_warmup=False):
         if flat_param.grad is None:
             raise ValueError("flat_param.grad must be the flat gradient buffer")
         self.max_grad_norm = None if max_grad_norm is None else _check_max_grad_norm(max_grad_norm)
         self.clip_cell = self.clip_partial = None
+        self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = self.ema_cell = None
+        self.ema_swapped = False
         self.param = flat_param
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.exp_avg = torch.zeros_like(flat_param.data)
@@ -52,13 +79,17 @@ class FlatAdam:
         self._cell_stale = False
         if self.max_grad_norm is not None:
             self._make_clip_buffers()
+        if self.ema_decay is not None:
+            self._make_ema_buffers()
 
     def hyper(self):
         """the values a captured launch holds as CONSTANTS (TrainStep.run_full captures again when they change): betas and eps, and
         whether the clipping launches are there at all.  lr and weight_decay live in the device step cell (cell_hyper), the
         clipping threshold in the clip cell: changing them is a small copy, not a new capture."""
         h = (float(self.betas[0]), float(self.betas[1]), float(self.eps))
-        return h if self.max_grad_norm is None else h + ("clip",)
+        if self.max_grad_norm is not None:
+            h = h + ("clip",)
+        return h if self.ema_decay is None else h + ("ema",)             # the EMA twin of the update is another launch
 
     def cell_hyper(self):
         return (float(self.lr), float(self.weight_decay))
@@ -99,10 +130,93 @@ class FlatAdam:
         c = self.clip_cell.cpu().tolist()
         return dict(norm=c[1], scale=c[2], skipped=int(c[3]), clipped=int(c[4]))
 
+    # ---- exponential moving average of the weights (ema_decay) ----
+    def _make_ema_buffers(self, updates=0):
+        """`ema` = a copy of the flat parameters, and the EMA cell {d, warm-up, k, k, 0, 0, 0, 0} (include/raindrop_hip.h
+        rd_adam_step_ema); made outside any capture (the constructor, load_state_dict)"""
+        self.ema = self.param.data.detach().clone()
+        self.ema_cell = torch.tensor([self.ema_decay, float(self.ema_warmup), float(updates), float(updates)] + [0.0] * 4,
+                                     dtype=torch.float64).to(self.param.device)
+        self._cell_ema_decay = self.ema_decay
+        self._ema_t = self.t
+
+    def _ema_on(self):
+        if self.ema_decay is None or self.ema is None:
+            raise ValueError("weight averaging is off: construct FlatAdam with ema_decay (the step's launches differ)")
+
+    def _ema_args(self):
+        self.sync_ema_cell()
+        return (ops._ptr(self.ema), ops._ptr(self.ema_cell))
+
+    def _check_not_swapped(self, what):
+        if self.ema_swapped:
+            raise _lib.RaindropHipError("FlatAdam.%s: the parameters are exchanged with their average (swap_ema / ema_weights): a step "
+                                        "now would train the averaged weights -- swap back first" % what)
+
+    def set_ema_decay(self, d):
+        """A new decay (float in [0, 1)) for the steps enqueued from here on, captured ones included: one 8-byte copy into the EMA
+        cell, stream-ordered with the launches around it."""
+        self._ema_on()
+        self.ema_decay = _check_ema_decay(d)
+        self.sync_ema_cell()
+
+    def sync_ema_cell(self):
+        """push a changed `ema_decay` into the EMA cell (TrainStep.run_full calls it next to sync_clip_cell), and keep the count
+        readable when `t` was set from outside (load_state_dict, a restored snapshot): the launches keep the count in the slot the
+        NEXT step number's parity selects, so after a jump of `t` the current count is copied into both slots, on the device."""
+        if self.ema_cell is None or self.ema_decay is None:
+            return
+        if self._cell_ema_decay != self.ema_decay:
+            self.ema_cell[0:1] = torch.tensor([_check_ema_decay(self.ema_decay)], dtype=torch.float64, device=self.ema_cell.device)
+            self._cell_ema_decay = self.ema_decay
+        if self._ema_t != self.t:
+            cur = 2 + ((self._ema_t + 1) & 1)
+            self.ema_cell[2:4] = self.ema_cell[cur:cur + 1].clone()
+            self._ema_t = self.t
+
+    def ema_updates(self):
+        """updates of the average so far according to the device (skipped steps are not counted): one device-to-host copy"""
+        self._ema_on()
+        return int(self.ema_cell.cpu().tolist()[2 + ((self._ema_t + 1) & 1)])
+
+    def swap_ema(self):
+        """Exchange the flat parameters and their average in place (rd_swap_f32; stream-ordered, capturable): every holder of a
+        parameter address sees the other set.  Steps raise until the next swap."""
+        self._ema_on()
+        _lib.call("rd_swap_f32", self.param.numel(), ops._ptr(self.param.data), ops._ptr(self.ema), ops._stream())
+        self.ema_swapped = not self.ema_swapped
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with opt.ema_weights(): ...` -- the model (and every captured step that reads its parameters) holds the averaged weights
+        inside the block and the training weights, bit for bit, after it."""
+        if self.ema_swapped:
+            raise _lib.RaindropHipError("FlatAdam.ema_weights: already swapped")
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            self.swap_ema()
+
     def step(self):
+        self._check_not_swapped("step")
+        p, g = self.param.data, self.param.grad
+        if self.ema_decay is not None:
+            ema = self._ema_args()           # (in front of `t += 1`: it sees a `t` that was set from outside)
+            self.t += 1
+            self._cell_stale = True
+            self._ema_t = self.t
+            head = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq), float(self.lr),
+                    float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
+            if self.max_grad_norm is not None:
+                partial, nbytes, cell = self._clip_args()
+                _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
+                _lib.call("rd_adam_step_clip_ema", *head, partial, nbytes, cell, *ema, ops._stream())
+            else:
+                _lib.call("rd_adam_step_ema", *head, *ema, ops._stream())
+            return
         self.t += 1
         self._cell_stale = True              # a captured step that follows re-syncs the device step state (TrainStep.run_full)
-        p, g = self.param.data, self.param.grad
         if self.max_grad_norm is not None:
             partial, nbytes, cell = self._clip_args()
             _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
@@ -120,10 +234,22 @@ class FlatAdam:
         caller's step already did (raindrop_amd.step.TrainStep.capture_full registers the cell -- `register_cell` -- and its first
         launch advances it: no extra launch).  Every replay is one step -- the owner of the graph keeps `self.t` in step
         (`note_replay`) and pushes a changed lr / weight decay with `sync_cell_hyper` (no new capture)."""
+        self._check_not_swapped("step_captured")
         self.sync_step_cell(create_only=True)
         p, g = self.param.data, self.param.grad
         if advance:
             _lib.call("rd_adam_state_advance", ops._ptr(self.step_cell), float(self.betas[0]), float(self.betas[1]), ops._stream())
+        if self.ema_decay is not None:       # the EMA twins: the step number (the count's slot) is the device state's t
+            ema = self._ema_args()
+            head = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq), float(self.betas[0]),
+                    float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell))
+            if self.max_grad_norm is not None:
+                partial, nbytes, cell = self._clip_args()
+                _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
+                _lib.call("rd_adam_step_clip_ema_dev", *head, partial, nbytes, cell, *ema, ops._stream())
+            else:
+                _lib.call("rd_adam_step_ema_dev", *head, *ema, ops._stream())
+            return
         if self.max_grad_norm is not None:   # the norm's partial sums, then the clipping instantiation of the update
             partial, nbytes, cell = self._clip_args()
             _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
@@ -170,19 +296,28 @@ class FlatAdam:
 
     def note_replay(self):
         self.t += 1
+        if self.ema_decay is not None and self._ema_t == self.t - 1:         # the replay moved the count to the next slot
+            self._ema_t = self.t
 
     def zero_grad(self, set_to_none=False):
         self.param.grad.zero_()
 
     def state_dict(self):
         stats = self.grad_stats() if self.clip_cell is not None else dict(skipped=0, clipped=0)
-        return dict(t=self.t, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr, betas=self.betas,
-                    eps=self.eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
-                    grad_skipped=stats["skipped"], grad_clipped=stats["clipped"])
+        sd = dict(t=self.t, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, lr=self.lr, betas=self.betas,
+                  eps=self.eps, weight_decay=self.weight_decay, max_grad_norm=self.max_grad_norm,
+                  grad_skipped=stats["skipped"], grad_clipped=stats["clipped"])
+        if self.ema_decay is not None:       # (off: the keys of an optimizer without the keyword)
+            if self.ema_swapped:
+                raise _lib.RaindropHipError("FlatAdam.state_dict: the parameters are exchanged with their average: swap back first")
+            sd.update(ema=self.ema, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=self.ema_updates())
+        return sd
 
     def load_state_dict(self, sd):
-        """In place (the moment buffers keep their addresses: a captured step stays valid); the device step state follows at the
-        next captured step."""
+        """In place (the moment buffers and `ema` keep their addresses: a captured step stays valid); the device step state follows
+        at the next captured step.  A dictionary without the `ema` keys leaves the average and its settings as they are."""
+        if self.ema_swapped:
+            raise _lib.RaindropHipError("FlatAdam.load_state_dict: the parameters are exchanged with their average: swap back first")
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.t = int(sd["t"])
@@ -197,3 +332,12 @@ class FlatAdam:
                 self.sync_clip_cell()
                 self.clip_cell[3:5] = torch.tensor([float(sd.get("grad_skipped", 0)), float(sd.get("grad_clipped", 0))],
                                                    dtype=torch.float64, device=self.clip_cell.device)
+        if sd.get("ema_decay") is not None:
+            self.ema_decay, self.ema_warmup = _check_ema_decay(sd["ema_decay"]), bool(sd.get("ema_warmup", False))
+            k = float(sd.get("ema_updates", 0))
+            if self.ema is None:             # off -> on: new buffers, and hyper() makes a captured step capture again
+                self._make_ema_buffers(int(k))
+            else:                            # in place: both count slots, so that any step number finds it
+                self.ema_cell.copy_(torch.tensor([self.ema_decay, float(self.ema_warmup), k, k] + [0.0] * 4, dtype=torch.float64))
+                self._cell_ema_decay, self._ema_t = self.ema_decay, self.t
+            self.ema.copy_(sd["ema"])

@@ -627,6 +627,7 @@ class TrainStep(Step):
         if self.split:
             self._check_split_order()
         self.graph = self.graph_b = self.graph_full = self._full_opt = self._full_hyper = None
+        self.captures = 0                                                  # whole-step graphs captured so far (capture_full)
         if use_graph:
             self._capture()
 
@@ -818,6 +819,7 @@ class TrainStep(Step):
         flat = self.flat
         opt.sync_step_cell()
         opt.sync_clip_cell()                                               # FlatAdam(max_grad_norm=...): the threshold's cell (no-op when off)
+        opt.sync_ema_cell()                                                # FlatAdam(ema_decay=...): the decay's cell likewise
         # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
         # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
         begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
@@ -853,6 +855,7 @@ class TrainStep(Step):
         opt.sync_step_cell()                                               # the warm-up did not step the optimizer; neither did the capture
         self._full_opt = opt
         self._full_hyper = opt.hyper()                                     # betas, eps are launch arguments: baked into the graph (lr, weight decay: device cell)
+        self.captures += 1
         return self.graph_full
 
     def run_full(self):
@@ -861,6 +864,9 @@ class TrainStep(Step):
             raise _lib.RaindropHipError("TrainStep.run_full: call capture_full(opt) first")
         if self._param_ptrs() != self._ptrs:
             raise _lib.RaindropHipError("TrainStep: a parameter or gradient buffer moved since construction: build a new TrainStep")
+        if getattr(self._full_opt, "ema_swapped", False):                  # FlatAdam.swap_ema / ema_weights(): the parameters ARE the average now
+            raise _lib.RaindropHipError("TrainStep.run_full: the optimizer's parameters are exchanged with their average "
+                                        "(FlatAdam.swap_ema): a replay would train the averaged weights -- swap back first")
         if self._full_opt.hyper() != self._full_hyper:                     # betas / eps changed: launch constants of the captured
             cell = self.seed_cell.clone()                                  # Adam -- capture again
             self.capture_full(self._full_opt)                              # (the warm-up passes advance the dropout stream: put it back)
@@ -868,6 +874,7 @@ class TrainStep(Step):
         self._full_opt.sync_cell_hyper()                                   # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259;
                                                                            # warm-up / cosine schedules): an 8-byte copy, no new capture
         self._full_opt.sync_clip_cell()                                    # the clipping threshold likewise (FlatAdam.max_grad_norm)
+        self._full_opt.sync_ema_cell()                                     # and the averaging decay (FlatAdam.ema_decay)
         if getattr(self._full_opt, "_cell_stale", False):                  # host-side steps were taken since: device state follows self.t
             self._full_opt.sync_step_cell()
             self._full_opt._cell_stale = False
