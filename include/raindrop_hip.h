@@ -553,6 +553,27 @@ int rd_batch_gather(int32_t T, int32_t B, int32_t W, int32_t d_static, int64_t N
                     float* src, float* times, float* static_out, int64_t* y_out, int64_t* lengths,
                     int32_t* bad_index_count, void* stream);
 
+/* The batch of a captured step from a device-resident EPOCH PLAN (raindrop_amd.feed.EpochFeed): rd_batch_gather with
+ * idx = plan[cursor], where plan is int64 [capacity, B] and cell = int64[2] {cursor, n_batches} are read ON THE DEVICE when
+ * the kernel runs (the cursor through the scalar cache: it is uniform) -- a replay of the same hipGraph gathers the next
+ * batch, and a new epoch is a copy into plan and cell, never a new capture.  Writes src, times, static_out, y_out and lengths
+ * exactly as rd_batch_gather(idx = plan[cursor]) does, bit for bit; y_all / y_out are required.  Nothing outside the plan is
+ * ever read: n_batches is cut to capacity, and a cursor outside [0, n_batches) reads the last valid row (row 0 of an empty
+ * plan) and adds ONE to *bad_index_count; sample indices outside [0,N) are clamped and counted as in rd_batch_gather.  The
+ * cell is not written (rd_feed_record advances it).  Asynchronous, capturable; B == 0 is a no-op. */
+int rd_feed_gather(int32_t T, int32_t B, int32_t W, int32_t d_static, int64_t N, int64_t capacity, const float* P_all,
+                   const float* time_all, const float* static_all, const int64_t* y_all, const int64_t* plan,
+                   const int64_t* cell, float* src, float* times, float* static_out, int64_t* y_out, int64_t* lengths,
+                   int32_t* bad_index_count, void* stream);
+/* The LAST launch of a fed step (one workgroup), k = cursor: loss_hist[k] = *loss; correct_hist[k] = the number of samples b
+ * with argmax_c logits[b, c] == y[b] (logits [B,C] row-major; ties go to the lowest class, a NaN is the maximum: torch.argmax;
+ * int32, integer partial sums in a fixed order, no atomics); then cursor = k + 1.  loss_hist / correct_hist hold `capacity`
+ * entries.  With the cursor outside [0, min(n_batches, capacity)) nothing is written and the cell stays as it is.  The cursor
+ * is read by the step's first launch (rd_feed_gather) and advanced by this one: stream order inside one graph is the whole
+ * protocol.  Asynchronous, capturable; B == 0 is a no-op. */
+int rd_feed_record(int32_t B, int32_t C, int64_t capacity, int64_t* cell, const float* loss, const float* logits,
+                   const int64_t* y, float* loss_hist, int32_t* correct_hist, void* stream);
+
 /* ---- paper-faithful graph operator: the use_beta branch of Observation_progation.message,
  * code/Ob_propagation.py:161-185,190-191,195,200,207-208,227, batched over B sample graphs that share an edge list.
  *   V [B,N,K] = relu(lin_value(x)),  H [B,N,T*32] = increase_dim(x)   (both per NODE: rd_linear_fwd)

@@ -137,6 +137,9 @@ SIGNATURES = {
     "rd_head_forward": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 11 + [_P, c_size_t, _P]),
     "rd_head_backward": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 18 + [_P, c_size_t, _P]),
     "rd_batch_gather": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64] + [_P] * 12),
+    # the batch of a captured step from a device-resident epoch plan (raindrop_amd.feed.EpochFeed)
+    "rd_feed_gather": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64, ctypes.c_int64] + [_P] * 13),
+    "rd_feed_record": (c_int32, [c_int32, c_int32, ctypes.c_int64] + [_P] * 7),
     "rd_graph_beta_kept": (c_int32, [c_int32]),
     "rd_graph_beta_workspace_bytes": (c_size_t, [c_int32] * 5),
     "rd_graph_beta_fwd": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64]

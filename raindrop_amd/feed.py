@@ -85,6 +85,118 @@ class DeviceDataset:
         return n
 
 
+class EpochFeed:
+    """The batches of one epoch as a device-resident plan that a captured step reads by itself (`TrainStep(..., feed=)`): the
+    step's FIRST launch (rd_feed_gather) copies batch `cursor` of the plan out of `ds` into the step's batch buffers, its LAST
+    (rd_feed_record) stores the loss and the number of correctly classified samples of that batch and moves the cursor on.  Plan
+    and cursor are read on the device when the kernels run, so an epoch is `n_batches` replays of one graph, one small upload
+    (`load_epoch`) and one small read-back (`history`); a new epoch, with another number of batches, needs no new capture.
+
+        fd = EpochFeed(ds, batch_size=128, capacity=planner.n_batches)
+        step = TrainStep(model, flat, batch, feed=fd); step.capture_full(opt)     # batch: the step's own buffers, any valid contents
+        fd.load_epoch(planner.next_epoch())
+        while fd.remaining(): step.run_full()
+        loss, correct = fd.history()
+
+    Owns one int64 buffer {cursor, n_batches | plan [capacity, batch_size]}, the history [2, capacity] (fp32 losses, int32 counts) and the
+    bad-index counter.  `ds` must carry labels.  Under data parallelism every rank has its own feed and loads its own plan rows."""
+
+    def __init__(self, ds, batch_size, capacity):
+        if torch.device(ds.dev).type != "cuda":
+            raise _lib.RaindropHipError("EpochFeed needs a ROCm device (there is no CPU fallback)")
+        if ds.y is None:
+            raise _lib.RaindropHipError("EpochFeed needs the dataset's labels (DeviceDataset(..., y=...))")
+        self.ds, self.dev, self.B, self.capacity = ds, ds.dev, int(batch_size), int(capacity)
+        if self.B <= 0 or self.capacity <= 0:
+            raise ValueError("batch_size and capacity must be positive, got %r and %r" % (batch_size, capacity))
+        self._state = torch.zeros(2 + self.capacity * self.B, dtype=torch.int64, device=self.dev)
+        self.cell, self.plan = self._state[:2], self._state[2:].view(self.capacity, self.B)
+        self._hist = torch.zeros((2, self.capacity), dtype=torch.int32, device=self.dev)
+        self.loss_hist, self.correct_hist = self._hist[0].view(torch.float32), self._hist[1]
+        self._bad = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self._n = self._left = 0
+
+    def load_epoch(self, batches):
+        """`batches`: index vectors of `batch_size` samples each (EpochPlanner.next_epoch()), at most `capacity` of them, checked
+        against [0, N) on the host (IndexError).  One host-to-device copy of {0, n | rows}, and the history slots 0 .. n-1 zeroed,
+        in the order of the current stream: whatever was enqueued before still sees the previous epoch."""
+        rows = [np.asarray(b.cpu() if torch.is_tensor(b) else b).reshape(-1) for b in batches]
+        n = len(rows)
+        if n > self.capacity:
+            raise ValueError("%d batches do not fit a plan of capacity %d" % (n, self.capacity))
+        if any(r.size != self.B for r in rows):
+            raise ValueError("every batch must hold batch_size = %d indices, got %s" % (self.B, sorted({int(r.size) for r in rows})))
+        host = np.zeros(2 + n * self.B, dtype=np.int64)
+        host[1] = n
+        if n:
+            idx = host[2:].reshape(n, self.B)
+            idx[:] = np.stack(rows)
+            lo, hi = int(idx.min()), int(idx.max())
+            if lo < 0 or hi >= self.ds.N:
+                raise IndexError("batch index out of range [0,%d): min %d max %d" % (self.ds.N, lo, hi))
+        self._state[:host.size].copy_(torch.from_numpy(host))
+        if n:
+            self._hist[:, :n].zero_()
+        self._n = self._left = n
+
+    def remaining(self):
+        """batches of the loaded epoch no step has taken yet: the host's mirror of the device cursor, no synchronisation"""
+        return self._left
+
+    def _take(self, who):
+        """a step is about to be enqueued: refuse behind the last batch, else count it"""
+        if self._left == 0:
+            raise _lib.RaindropHipError("%s: the epoch plan is used up (%d of %d batches taken): EpochFeed.load_epoch first"
+                                        % (who, self._n, self._n))
+        self._left -= 1
+
+    def history(self):
+        """(loss [n_done] float32, correct [n_done] int32) of the batches taken so far in this epoch, as numpy arrays: ONE
+        device-to-host copy (it waits for the stream)."""
+        h = self._hist[:, :self._n - self._left].cpu().numpy()
+        return h[0].view(np.float32).copy(), h[1].copy()
+
+    def bad_indices(self):
+        """Out-of-range sample indices and cursors the gathers clamped since the last call of this method (`load_epoch` checks the
+        indices on the host: anything here came from a plan or cell written some other way); reading it synchronises."""
+        n = int(self._bad.item())
+        self._bad.zero_()
+        return n
+
+    # ---- what a step enqueues (raindrop_amd.step.TrainStep) -------------------------------------------------------------------
+    def check_step(self, model, batch):
+        """the feed writes into `batch`: same device, same shapes, labels there"""
+        ds, src = self.ds, batch["src"]
+        if batch.get("y") is None:
+            raise ValueError("a fed step needs batch['y']: the feed gathers the labels")
+        want = (ds.T, self.B, ds.W)
+        if tuple(src.shape) != want or src.device != self.cell.device:
+            raise ValueError("the feed gathers src %s on %s, the step's batch holds %s on %s" % (want, self.cell.device, tuple(src.shape), src.device))
+        st = batch.get("static")
+        if st is not None and (ds.Pstatic is None or tuple(st.shape) != (self.B, ds.ds)):
+            raise ValueError("the step's batch has static features %s, the feed's dataset %s" % (
+                tuple(st.shape), None if ds.Pstatic is None else (self.B, ds.ds)))
+
+    def enqueue_gather(self, batch, call=_lib.call):
+        ds, st = self.ds, batch.get("static")
+        call("rd_feed_gather", ds.T, self.B, ds.W, ds.ds if st is not None else 0, ds.N, self.capacity, _p(ds.P), _p(ds.Ptime),
+             _p(ds.Pstatic) if st is not None else None, _p(ds.y), _p(self.plan), _p(self.cell), _p(batch["src"]), _p(batch["times"]),
+             _p(st), _p(batch["y"]), _p(batch["lengths"]), _p(self._bad), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def enqueue_record(self, loss, logits, y, call=_lib.call):
+        call("rd_feed_record", int(logits.shape[0]), int(logits.shape[1]), self.capacity, _p(self.cell), _p(loss), _p(logits), _p(y),
+             _p(self.loss_hist), _p(self.correct_hist), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def snapshot(self):
+        """cursor, history and counter as they are now (device clones, stream-ordered): a capture's warm-up passes run the step
+        for real, `restore` puts back what they moved"""
+        return self.cell.clone(), self._hist.clone(), self._bad.clone()
+
+    def restore(self, snap):
+        for dst, src in zip((self.cell, self._hist, self._bad), snap):
+            dst.copy_(src)
+
+
 class EpochPlanner:
     """The reference's batch plan over a whole RUN (`code/Raindrop.py:261-307`): `idx_0` and the 3x-expanded `idx_1` are
     created once per run and shuffled IN PLACE at the start of every epoch, so epoch k's permutation is applied on top of

@@ -597,10 +597,18 @@ class TrainStep(Step):
     TUNE_WAVES = (12, 15)
 
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0):
+                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0, feed=None):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
         live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
         of device tensors that are REUSED every step (copy new data into them).
+        feed: a raindrop_amd.feed.EpochFeed -- the step fetches its own batch: in every form (eager run(), the captured graph, the
+        two-graph form, capture_full) the FIRST thing enqueued, in front of the `begin` stage, is rd_feed_gather, which copies batch
+        `cursor` of the feed's epoch plan into `batch`, and the LAST (behind the optimizer in capture_full, at the end of the second
+        graph in the two-graph form) is rd_feed_record, which stores this batch's loss and number of correct predictions in the
+        feed's history and advances the cursor.  run() / run_full() refuse once `feed.remaining()` is 0.  The warm-up passes of a
+        capture run the step for real: the feed's cursor, history and counter are put back afterwards, `batch` holds whatever they
+        gathered.  The measurement captures (capture_segments / capture_marked) do not feed.  None: the launches the step always
+        enqueued.
         class_weight, label_smoothing: the loss is torch.nn.CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
         instead of the plain mean cross entropy, in every form of the step (eager run(), the captured graph, capture_full, the
         two-graph data-parallel form); `set_criterion` changes both between replays without a new capture.  Each rank normalises by
@@ -613,6 +621,8 @@ class TrainStep(Step):
         # module_mode (raindrop_amd.graph_module): the loss is the CALLER's -- the step is cut into parts 'mf' (forward up to the
         # logits) and 'mb' (backward from self.dlogits, which the caller fills), batch carries no labels
         self.module_mode = bool(module_mode)
+        if feed is not None and self.module_mode:
+            raise ValueError("TrainStep(module_mode=True) takes its batch and its loss from the caller: it can not run on a feed")
         # split: capture the step as TWO graphs -- (A) forward + loss + the backward of the head and the last encoder layer, (B) the
         # rest of the backward pass -- so that a data-parallel caller can start the all-reduce of the gradients A has finished
         # (run(between=...)) beside B.  None = on when torch.distributed runs more than one rank (RD_DP_OVERLAP=0 turns it off).
@@ -626,10 +636,34 @@ class TrainStep(Step):
                          token_plan=token_plan, class_weight=class_weight, label_smoothing=label_smoothing)
         if self.split:
             self._check_split_order()
+        self.feed = feed
+        if feed is not None:
+            feed.check_step(model, batch)
         self.graph = self.graph_b = self.graph_full = self._full_opt = self._full_hyper = None
         self.captures = 0                                                  # whole-step graphs captured so far (capture_full)
         if use_graph:
-            self._capture()
+            with self._feed_kept():
+                self._capture()
+
+    # ---- the feed's two launches around the step (nothing without a feed) ---------------------------------------------------------
+    def _feed_gather(self):
+        if self.feed is not None:
+            self.feed.enqueue_gather(self.batch, self._call)
+
+    def _feed_record(self):
+        if self.feed is not None:
+            self.feed.enqueue_record(self.loss, self.logits, self.batch["y"], self._call)
+
+    @contextlib.contextmanager
+    def _feed_kept(self):
+        """around a capture: its warm-up passes (and the autotune's timed replays) gather, record and advance the cursor like any
+        step -- the feed is as it was afterwards"""
+        snap = self.feed.snapshot() if self.feed is not None else None
+        try:
+            yield
+        finally:
+            if snap is not None:
+                self.feed.restore(snap)
 
     def _capture(self):
         """Capture the step as one hipGraph (two in the split form).  With `autotune`, the step is captured once per setting of the
@@ -696,11 +730,24 @@ class TrainStep(Step):
 
 
     def _capture_one(self):
+        def whole():
+            self._feed_gather()
+            self._body()
+            self._feed_record()
+
+        def first():
+            self._feed_gather()
+            self._body("a")
+
+        def second():
+            self._body("b")
+            self._feed_record()
+
         def cap():
             if self.split:
-                self.graph, self.graph_b = capture_graphs([lambda: self._body("a"), lambda: self._body("b")], warm=self._body)
+                self.graph, self.graph_b = capture_graphs([first, second], warm=whole)
             else:
-                (self.graph,), self.graph_b = capture_graphs([self._body]), None
+                (self.graph,), self.graph_b = capture_graphs([whole]), None
         self._with_cell(cap)
 
     def capture_segments(self, parts=("begin", "k1f", "mid", "k1b")):
@@ -769,6 +816,8 @@ class TrainStep(Step):
         if self._param_ptrs() != self._ptrs:
             raise _lib.RaindropHipError("TrainStep: a parameter or gradient buffer moved since construction (model.to(), "
                                         "flatten_parameters() or a re-assignment): build a new TrainStep")
+        if self.feed is not None:
+            self.feed._take("TrainStep.run")
         if self.graph is not None:
             self.graph.replay()
             if self.graph_b is not None:
@@ -778,6 +827,7 @@ class TrainStep(Step):
         else:
             def eager():
                 with torch.no_grad():
+                    self._feed_gather()
                     if self.split:
                         self._body("a")
                         if between is not None:
@@ -785,6 +835,7 @@ class TrainStep(Step):
                         self._body("b")
                     else:
                         self._body()
+                    self._feed_record()
             self._with_cell(eager)
         for p, v in zip(self.flat.params, self.flat.views):
             p.grad = v
@@ -825,10 +876,13 @@ class TrainStep(Step):
         begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
 
         def warm():                                                        # outside the capture: RCCL's lazy inits, too
+            self._feed_gather()
             self._body()
             flat.allreduce()
+            self._feed_record()
 
         def whole():
+            self._feed_gather()
             if begin_adv:
                 opt.register_cell(True)
             if self.split:
@@ -845,13 +899,15 @@ class TrainStep(Step):
                 opt.register_cell(False)
                 flat.allreduce()
             opt.step_captured(advance=not begin_adv)
+            self._feed_record()
 
         def cap():
             try:
                 self.graph_full, = capture_graphs([whole], warm=warm)
             finally:
                 opt.register_cell(False)
-        self._with_cell(cap)
+        with self._feed_kept():
+            self._with_cell(cap)
         opt.sync_step_cell()                                               # the warm-up did not step the optimizer; neither did the capture
         self._full_opt = opt
         self._full_hyper = opt.hyper()                                     # betas, eps are launch arguments: baked into the graph (lr, weight decay: device cell)
@@ -867,6 +923,8 @@ class TrainStep(Step):
         if getattr(self._full_opt, "ema_swapped", False):                  # FlatAdam.swap_ema / ema_weights(): the parameters ARE the average now
             raise _lib.RaindropHipError("TrainStep.run_full: the optimizer's parameters are exchanged with their average "
                                         "(FlatAdam.swap_ema): a replay would train the averaged weights -- swap back first")
+        if self.feed is not None:
+            self.feed._take("TrainStep.run_full")
         if self._full_opt.hyper() != self._full_hyper:                     # betas / eps changed: launch constants of the captured
             cell = self.seed_cell.clone()                                  # Adam -- capture again
             self.capture_full(self._full_opt)                              # (the warm-up passes advance the dropout stream: put it back)

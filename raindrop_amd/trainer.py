@@ -1,0 +1,159 @@
+"""The reference script's training loop (`code/Raindrop.py:256-381`) as one call on the captured path.
+
+`fit` puts together what the library has: `feed.EpochPlanner` (the script's batch plan, same numpy calls), `feed.EpochFeed` (the
+plan on the device), `TrainStep` / `BetaTrainStep` with the feed attached, `FlatAdam` inside `capture_full`, `feed.validate` and a
+plateau scheduler.  An epoch is one upload of the plan, `n_batches` replays of ONE hipGraph and one read-back of the per-batch
+losses and hit counts; validation is the captured evaluation pass.  `ReduceOnPlateau` restates torch's scheduler on the host,
+because `FlatAdam` has no `param_groups` for torch's to act on.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib, dp, feed as feed_mod
+from .optim import FlatAdam
+
+VAL_FIELDS = ("auroc", "auprc", "loss", "accuracy", "precision", "recall", "f1")
+
+
+class ReduceOnPlateau:
+    """`torch.optim.lr_scheduler.ReduceLROnPlateau` for an optimizer that keeps its rate in `opt.lr` (FlatAdam): the same rule, the
+    same float arithmetic, so the same rates.  The defaults are the script's (`code/Raindrop.py:257-259`).  `step(metric)` once per
+    epoch; `opt` may be given later (`fit` binds its optimizer to a scheduler passed in without one)."""
+
+    def __init__(self, opt=None, mode="max", factor=0.1, patience=1, threshold=1e-4, threshold_mode="rel", cooldown=0, min_lr=1e-8,
+                 eps=1e-8):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        if mode not in ("min", "max"):
+            raise ValueError("mode " + str(mode) + " is unknown!")
+        if threshold_mode not in ("rel", "abs"):
+            raise ValueError("threshold mode " + str(threshold_mode) + " is unknown!")
+        self.opt, self.mode, self.factor, self.patience = opt, mode, factor, patience
+        self.threshold, self.threshold_mode, self.cooldown, self.min_lr, self.eps = threshold, threshold_mode, cooldown, min_lr, eps
+        self.best = math.inf if mode == "min" else -math.inf
+        self.cooldown_counter = self.num_bad_epochs = self.last_epoch = 0
+
+    def is_better(self, a, best):
+        if self.mode == "min":
+            return a < best * (1.0 - self.threshold) if self.threshold_mode == "rel" else a < best - self.threshold
+        return a > best * (self.threshold + 1.0) if self.threshold_mode == "rel" else a > best + self.threshold
+
+    def step(self, metric):
+        current = float(metric)
+        self.last_epoch += 1
+        if self.is_better(current, self.best):
+            self.best, self.num_bad_epochs = current, 0
+        else:
+            self.num_bad_epochs += 1
+        if self.cooldown_counter > 0:
+            self.cooldown_counter -= 1
+            self.num_bad_epochs = 0                              # bad epochs in the cooldown do not count
+        if self.num_bad_epochs > self.patience:
+            old = float(self.opt.lr)
+            new = max(old * self.factor, self.min_lr)
+            if old - new > self.eps:
+                self.opt.lr = new
+            self.cooldown_counter, self.num_bad_epochs = self.cooldown, 0
+        return float(self.opt.lr)
+
+
+def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy):
+    """what can be refused without a device"""
+    if strategy not in (1, 2, 3):
+        raise ValueError("strategy must be 1, 2 or 3, got %r" % (strategy,))
+    if int(batch_size) != batch_size or batch_size <= 0:
+        raise ValueError("batch_size must be a positive integer, got %r" % (batch_size,))
+    if strategy in (1, 2) and batch_size % 2:
+        raise ValueError("strategy %d draws batch_size / 2 samples of each class: batch_size must be even, got %d" % (strategy, batch_size))
+    if int(epochs) != epochs or epochs < 0:
+        raise ValueError("epochs must be a non-negative integer, got %r" % (epochs,))
+    for name, ds in (("train_ds", train_ds), ("val_ds", val_ds)):
+        if getattr(ds, "y", None) is None:
+            raise _lib.RaindropHipError("fit: %s carries no labels (DeviceDataset(..., y=...))" % name)
+
+
+def _live_names(model):
+    from . import synth
+    cfg = dict(static=bool(model.static), nlayers=len(model.transformer_encoder.layers))
+    return synth.live_parameter_names_beta(cfg) if getattr(model, "use_beta", False) else synth.live_parameter_names(cfg)
+
+
+def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
+        class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True):
+    """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
+    after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
+
+    * batches: `feed.EpochPlanner(train labels, batch_size, strategy)` -- the script's numpy calls in the script's order, so
+      `np.random.seed` before the call (or `seed=`, which also seeds the step's dropout stream) reproduces its batches;
+    * the step: `TrainStep` (`BetaTrainStep` for a `use_beta` model, with `distance_weight`) on one `feed.EpochFeed`, `FlatAdam(lr,
+      weight_decay, max_grad_norm, ema_decay)` inside `capture_full`; `class_weight` / `label_smoothing` set the criterion of the
+      step and of the validation loss.  The model is put into training mode to build the step (that is when dropout is read) and
+      gets its previous mode back at the end; evaluation runs with dropout off whatever the mode;
+    * per epoch: `load_epoch`, `n_batches` x `run_full`, `feed.history()`; then `feed.validate(model, val_ds, transform=...)` (on the
+      averaged weights, `validate_ema`, when `ema_decay` is set), the scheduler's step on `auprc` (:368) and, when `auroc` beats the
+      best so far (:369-374), a device copy of the flat parameters (of their average when `ema_decay` is set: what was validated);
+    * at the end the best copy goes back into the parameters (:381), so `feed.validate(model, val_ds)` gives `best_auroc` again.
+
+    scheduler: True = `ReduceOnPlateau` with the script's settings, False / None = a constant rate, or a `ReduceOnPlateau` of your own.
+    Returns a dict of per-epoch lists -- `train_loss` (the float32 mean of the epoch's per-batch losses), `train_accuracy`, `lr` (the
+    rate after the epoch's scheduler step), `val_auroc`, `val_auprc`, `val_loss`, `val_accuracy`, `val_precision`, `val_recall`,
+    `val_f1` -- plus `best_epoch` (None when no epoch's auroc exceeded 0) and `best_auroc`.
+
+    One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
+    its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
+    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy)
+    from .step import TrainStep
+    from .step_beta import BetaTrainStep
+    if seed is not None:
+        np.random.seed(seed)
+    B = int(batch_size)
+    beta = bool(getattr(model, "use_beta", False))
+    if distance_weight and not beta:
+        raise ValueError("distance_weight belongs to a use_beta model")
+    was_training = model.training
+    model.train()
+    named = dict(model.named_parameters())
+    flat = dp.FlatGradAllReduce([(n, named[n]) for n in _live_names(model)], n_buckets=2)
+    opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+    planner = feed_mod.EpochPlanner(train_ds.y.cpu().numpy(), batch_size=B, strategy=strategy, n_total=train_ds.N)
+    fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1))
+    P, Pstatic, Ptime, y, lengths = train_ds.batch(np.arange(B) % train_ds.N)          # valid contents for the step's checks
+    batch = dict(src=P, static=Pstatic if model.static else None, times=Ptime, y=y, lengths=lengths)
+    kw = dict(autotune=autotune, class_weight=class_weight, label_smoothing=label_smoothing, feed=fd)
+    if seed is not None:
+        kw["seed"] = int(seed)
+    step = BetaTrainStep(model, flat, batch, distance_weight=distance_weight, **kw) if beta else TrainStep(model, flat, batch, **kw)
+    sched = ReduceOnPlateau() if scheduler is True else (scheduler or None)
+    if sched is not None and sched.opt is None:
+        sched.opt = opt
+    out = {k: [] for k in ("train_loss", "train_accuracy", "lr") + tuple("val_" + f for f in VAL_FIELDS)}
+    best, best_auroc, best_epoch = None, 0.0, None
+    vkw = dict(transform=transform, class_weight=class_weight, label_smoothing=label_smoothing)
+    try:
+        step.capture_full(opt)
+        for epoch in range(int(epochs)):
+            fd.load_epoch(planner.next_epoch())
+            while fd.remaining():
+                step.run_full()
+            loss, correct = fd.history()
+            out["train_loss"].append(float(loss.mean()) if loss.size else float("nan"))
+            out["train_accuracy"].append(float(correct.sum()) / max(correct.size * B, 1))
+            v = feed_mod.validate_ema(model, val_ds, opt, **vkw) if ema_decay is not None else feed_mod.validate(model, val_ds, **vkw)
+            for f in VAL_FIELDS:
+                out["val_" + f].append(v[f])
+            if sched is not None:
+                sched.step(v["auprc"])
+            out["lr"].append(float(opt.lr))
+            if v["auroc"] > best_auroc:
+                best_auroc, best_epoch = v["auroc"], epoch
+                src = opt.ema if ema_decay is not None else opt.param.data
+                best = src.clone() if best is None else best.copy_(src)
+        if best is not None:
+            opt.param.data.copy_(best)
+    finally:
+        step.close()
+        model.train(was_training)
+    out["best_epoch"], out["best_auroc"] = best_epoch, best_auroc
+    return out
