@@ -382,38 +382,48 @@ int rd_masked_mean_bwd(const rd_shape* s, int32_t D, const float* dout, int32_t 
 
 /* ---- caller step (a19): the optimizer of code/Raindrop.py:256 ------------------------------- */
 
-/* torch.optim.Adam (no amsgrad; weight_decay added to the gradient) over one flat buffer of n
- * floats: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).
- * `step` is t (1-based).  All four buffers 16-byte aligned. */
+/* torch.optim.Adam (no amsgrad; weight_decay added to the gradient) over one flat buffer of n floats, as ONE launch, in eight forms:
+ *     rd_adam_step [_clip] [_ema] [_dev]
+ *   m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps),   g = grad + weight_decay * p.
+ * Shared arguments: `n`; `param`, `grad`, `exp_avg`, `exp_avg_sq` (n floats each, 16-byte aligned); `beta1`, `beta2`, `eps` (launch
+ * constants); `stream`.  The forms differ in where the step's scalars come from and in two optional riders:
+ *   host forms (no _dev): `lr`, `weight_decay` and `step` = t (1-based) are arguments; the bias corrections are formed on the host.
+ *   _dev: they are read from `state`, so the launch is one a hipGraph can replay.
+ *   _clip: the gradient is scaled to a global norm first, and a non-finite gradient skips the step (`partial`, `partial_bytes`, `clip`).
+ *   _ema: an exponential moving average of the parameters is kept by the same launch (`ema`, `ema_cell`).
+ * The three cells are 64 bytes, 16-byte aligned, eight doubles each; a launch never reads a word another workgroup of the same
+ * launch writes, and a value the caller may change between replays (lr, the threshold, the decay) is an 8-byte copy, not a new capture.
+ *   `state` {t, beta1^t, beta2^t, lr, 0, weight_decay, 0, 0} OF THE STEP BEING APPLIED; the update only reads it.  It is advanced once
+ *     per step by an EARLIER launch: rd_adam_state_advance (one thread: t += 1, beta^t *= beta), or -- no extra launch -- by the
+ *     step's first launch: rd_set_adam_state registers the cell on this host thread and rd_step_begin (enqueued while it is
+ *     registered) advances it next to the dropout seed bump.  Initialise {steps taken so far, beta1^t, beta2^t, lr, 0, wd, 0, 0}.
+ *     (A learning-rate schedule, code/Raindrop.py:257-259, writes slot 3.)
+ *   `clip` {max_norm, last_norm, last_scale, skipped, clipped, 0, 0, 0}: slot 0 is read by the launch and written by the caller only
+ *     (+inf: guard without clipping); slots 1-4 are written by one thread of the launch -- the norm and the scale it applied (0 when
+ *     it skipped) and two running counts of skipped / clipped steps.
+ *   `ema_cell` {d, warm-up, k0, k1, 0, 0, 0, 0}: slot 0 the decay d, slot 1 the warm-up flag (0 or 1), both the caller's.  Slots 2 and
+ *     3 hold k, the number of EMA updates so far, and belong to the launch: with s the step number (`step` of the host forms; t of
+ *     `state` for the _dev forms) every workgroup reads k from slot 2 + (s & 1) and one thread writes k + 1 to slot 2 + ((s + 1) & 1)
+ *     -- no atomics, two replays from the same state give the same bits.  The caller initialises BOTH slots to the count (0), and
+ *     again whenever it makes the step number jump (steps must follow each other by one for the parity to select the slot last written).
+ * RD_EINVAL before any launch: a NULL or misaligned pointer, step < 1, n <= 0, partial_bytes < rd_grad_sumsq_bytes().  One exception:
+ * plain rd_adam_step accepts n == 0 and returns RD_OK without a launch; the seven other forms refuse it.
+ * raindrop_amd.optim.FlatAdam.step / step_captured; raindrop_amd.step.TrainStep.capture_full. */
 int rd_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
                  float beta1, float beta2, float eps, float weight_decay, int64_t step, void* stream);
-/* The same update with the optimizer's step state on the DEVICE -- ONE launch a hipGraph can replay.  `state`: 64 bytes, 16-byte
- * aligned, eight doubles {t, beta1^t, beta2^t, lr, 0, weight_decay, 0, 0} OF THE STEP BEING APPLIED; the launch only reads it (no
- * workgroup of a launch ever sees a state another workgroup of the same launch wrote).  The state is advanced once per step by an
- * EARLIER launch: rd_adam_state_advance (one thread: t += 1, beta^t *= beta), or -- no extra launch -- by the step's first launch:
- * rd_set_adam_state registers the cell on this host thread and rd_step_begin (enqueued while it is registered) advances it next
- * to the dropout seed bump.  lr / weight_decay are read from the cell so that a learning-rate schedule (code/Raindrop.py:257-259)
- * is an 8-byte copy into it, not a new capture; beta1, beta2, eps are launch constants.
- * Initialise {steps taken so far, beta1^t, beta2^t, lr, 0, weight_decay, 0, 0}.
- * raindrop_amd.optim.FlatAdam.step_captured / raindrop_amd.step.TrainStep.capture_full. */
 int rd_adam_step_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
                      float eps, const void* state, void* stream);
 int rd_adam_state_advance(void* state, float beta1, float beta2, void* stream);
 int rd_set_adam_state(void* state, float beta1, float beta2);      /* NULL: unregister */
 
-/* Global-norm gradient clipping and the non-finite guard: torch.nn.utils.clip_grad_norm_ between backward and the update, as two
- * launches a hipGraph can hold (raindrop_amd.optim.FlatAdam(max_grad_norm=...)).
+/* _clip: global-norm gradient clipping and the non-finite guard, torch.nn.utils.clip_grad_norm_ between backward and the update, as
+ * two launches a hipGraph can hold (raindrop_amd.optim.FlatAdam(max_grad_norm=...)).
  * rd_grad_sumsq: partial[w] = sum of grad[i]^2 over the w-th of rd_grad_sumsq_grid() contiguous slices, squared and accumulated in
  * double in a fixed order (no atomics: the same bits on every launch).  `partial`: rd_grad_sumsq_bytes() bytes, 16-byte aligned.
- * rd_adam_step_clip / rd_adam_step_clip_dev: rd_adam_step / rd_adam_step_dev on the clipped gradient.  Every workgroup sums the
- * partials in index order, norm = sqrt(sum), scale = norm > max_norm ? max_norm / (norm + 1e-6) : 1 (clip_grad_norm_'s coefficient,
- * clamped at 1), then Adam with g * scale + weight_decay * p.  A sum that is not finite (an inf or NaN gradient) makes the launch
- * store NOTHING: param, exp_avg, exp_avg_sq keep their bits.  At scale == 1 the update is rd_adam_step's / rd_adam_step_dev's, bit
- * for bit.  `clip`: 64 bytes, 16-byte aligned, eight doubles {max_norm, last_norm, last_scale, skipped, clipped, 0, 0, 0}: slot 0 is
- * read by the launch and written by the caller only (a new threshold is an 8-byte copy, not a new capture; +inf: guard without
- * clipping); slots 1-4 are written by one thread of the launch -- the norm and the scale it applied (0 when it skipped) and two
- * running counts of skipped / clipped steps.  The step state of the _dev form is advanced as for rd_adam_step_dev, skipped or not.
- * RD_EINVAL before any launch: NULL or misaligned pointers, n <= 0, partial_bytes < rd_grad_sumsq_bytes(). */
+ * The update then: every workgroup sums the partials in index order, norm = sqrt(sum), scale = norm > max_norm ? max_norm /
+ * (norm + 1e-6) : 1 (clip_grad_norm_'s coefficient, clamped at 1), then Adam with g = grad * scale + weight_decay * p.  A sum that is
+ * not finite (an inf or NaN gradient) makes the launch store NOTHING: param, exp_avg, exp_avg_sq keep their bits.  At scale == 1 the
+ * update is that of the form without _clip, bit for bit.  The step state of the _dev form is advanced as always, skipped or not. */
 int32_t rd_grad_sumsq_grid(void);
 size_t rd_grad_sumsq_bytes(void);
 int rd_grad_sumsq(int64_t n, const float* grad, void* partial, size_t partial_bytes, void* stream);
@@ -423,20 +433,12 @@ int rd_adam_step_clip(int64_t n, float* param, const float* grad, float* exp_avg
 int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
                           float eps, const void* state, const void* partial, size_t partial_bytes, void* clip, void* stream);
 
-/* Exponential moving average of the weights inside the update's own launch (raindrop_amd.optim.FlatAdam(ema_decay=...)): the four
- * updates above with two more arguments, `ema` (n floats, 16-byte aligned) and `ema_cell` (64 bytes, 16-byte aligned).  After the
- * Adam update of element i, in fp32, in the thread that wrote p_new:  ema[i] += c_t * (p_new[i] - ema[i]),  c_t = 1 - d_t rounded to
- * float once, d_t formed in double by every workgroup: d_t = d, or with warm-up min(d, (1 + k) / (10 + k)), k = the number of EMA
- * updates so far (0-based; not the number of steps).  param, exp_avg, exp_avg_sq get the bits of the twin without `ema`.
- * `ema_cell`: eight doubles {d, warm-up, k0, k1, 0, 0, 0, 0}.  Slot 0: the decay d, written by the caller and read by the launch (a new
- * decay is an 8-byte copy, not a new capture).  Slot 1: the warm-up flag, 0 or 1, the caller's likewise.  Slots 2 and 3 hold k and
- * belong to the launch: with s the step number (`step` of the host forms; t of `state`, which an earlier launch advanced, for the
- * _dev forms) every workgroup reads k from slot 2 + (s & 1) and one thread writes k + 1 to slot 2 + ((s + 1) & 1) -- no workgroup
- * reads a word another workgroup of the same launch writes, no atomics, two replays from the same state give the same bits.  The
- * caller initialises BOTH slots to the count (0), and again whenever it makes the step number jump (steps must follow each other by
- * one for the parity to select the slot last written).  A step the clip forms skip (non-finite gradient norm) stores nothing to
- * `ema` and writes k, not k + 1: param, exp_avg, exp_avg_sq and ema keep their bits and the skipped step is no update.
- * RD_EINVAL before any launch: NULL or misaligned pointers, n <= 0, and what the twin refuses. */
+/* _ema: the exponential moving average of the weights inside the update's own launch (raindrop_amd.optim.FlatAdam(ema_decay=...)):
+ * the four forms above with `ema` (n floats, 16-byte aligned) and `ema_cell` in front of the stream.  After the Adam update of
+ * element i, in fp32, in the thread that wrote p_new:  ema[i] += c_t * (p_new[i] - ema[i]),  c_t = 1 - d_t rounded to float once, d_t
+ * formed in double by every workgroup: d_t = d, or with warm-up min(d, (1 + k) / (10 + k)) (k: 0-based; not the number of steps).
+ * param, exp_avg, exp_avg_sq get the bits of the form without _ema.  A step the clip forms skip stores nothing to `ema` and writes
+ * k, not k + 1: the skipped step is no update of the average. */
 int rd_adam_step_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                      float beta2, float eps, float weight_decay, int64_t step, float* ema, void* ema_cell, void* stream);
 int rd_adam_step_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,

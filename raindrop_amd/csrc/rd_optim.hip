@@ -1,6 +1,10 @@
 // rd_optim.hip -- Adam update over one flat parameter buffer (the optimizer of code/Raindrop.py:256,
 // torch.optim.Adam(lr=1e-4) with default betas / eps, no amsgrad).  With the live parameters and
 // their gradients held in flat buffers (raindrop_amd/dp.py) the whole update is one elementwise pass.
+// One body, three kernel shells, eight instantiations: the update is written ONCE (adam_element / adam_thread, templates on
+// <CLIP, EMA>); k_adam<EMA>, k_adam_dev<EMA> and k_adam_clip<DEV, EMA> only fetch their scalars and call it; the eight extern "C"
+// entry points fill one AdamCall and share one launcher (adam_launch<DEV, CLIP, EMA>).  A flag that is off does not exist in the
+// instruction stream (rule 40): profiles/adam_refactor_isa.txt holds the eight instantiations against the six hand-kept copies.
 #include "rd_common.h"
 
 namespace rd {
@@ -33,6 +37,58 @@ __device__ __forceinline__ void ema_count(EmaCell* cell, long step, double k_nex
   if (blockIdx.x == 0 && threadIdx.x == 0) cell->k[(step + 1) & 1] = k_next;
 }
 
+// a * b rounded on its own: never the multiply of a fused multiply-add (the compiler contracts a plain `a * b + c`, __fmul_rn included)
+__device__ __forceinline__ float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// ---- the update, once ----------------------------------------------------------------------------------------------------------------
+// Adam on one element.  CLIP: the gradient is scaled first, by its own rounded multiply -- at scale == 1 `g * scale` IS g and everything
+// behind it is the expression without the flag: the same bits.  Weight decay is added AFTER the scale (torch clips the raw gradient;
+// Adam adds wd * p inside its step).  EMA: the average follows the new parameter in the same thread.  Without a flag its operand is
+// not in the expression at all (not `* 1.0f`: that is another instruction stream).
+struct AdamCoef { float b1, b2, eps, wd, bc2_sqrt, step_size, scale, ce; };
+
+// (Buffers and index, not references: element i of the flat buffers in the tail, of the thread's four registers in the float4 path;
+// each access is then formed where the expression uses it, which keeps the tail's loads and stores in the order they always had.)
+template <bool CLIP, bool EMA, typename I>
+__device__ __forceinline__ void adam_element(float* p, const float* g, float* m, float* v, float* e, I i, const AdamCoef& c) {
+  const float gr = (CLIP ? mul_rounded(g[i], c.scale) : g[i]) + c.wd * p[i];
+  m[i] = c.b1 * m[i] + (1.f - c.b1) * gr;
+  v[i] = c.b2 * v[i] + (1.f - c.b2) * gr * gr;
+  p[i] -= c.step_size * m[i] / (sqrtf(v[i]) / c.bc2_sqrt + c.eps);
+  if (EMA) e[i] += c.ce * (p[i] - e[i]);
+}
+
+// One thread's four elements: 16-byte loads and stores, or -- the last thread of the buffer -- a scalar tail.  (The buffers are the
+// kernels' __restrict__ arguments; the qualifier is not repeated here.)
+template <bool CLIP, bool EMA>
+__device__ __forceinline__ void adam_thread(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1,
+                                            float b2, float eps, float wd, float bc1, float bc2_sqrt, float scale, float ce) {
+  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
+  if (i4 >= n) return;
+  const AdamCoef c = {b1, b2, eps, wd, bc2_sqrt, lr / bc1, scale, ce};
+  if (i4 + 3 < n) {
+    // p is loaded LAST.  Which of two products a sum fuses into its FMA follows the order of the sum's operands, and the optimiser
+    // orders them by where their loads stand (it sees this function unrolled before it sees the kernel): with p first,
+    // `b1 * m + (1 - b1) * gr` came out as fma(1 - b1, gr, b1 * m) instead of fma(b1, m, (1 - b1) * gr) -- other bits than the kernels
+    // have always given.  profiles/adam_refactor_isa.txt records the streams, tests/test_adam_bits_gpu.py pins the bits.
+    float4 gg = *reinterpret_cast<const float4*>(g + i4), mm = *reinterpret_cast<float4*>(m + i4);
+    float4 vv = *reinterpret_cast<float4*>(v + i4), pp = *reinterpret_cast<float4*>(p + i4);
+    float4 ee;
+    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) adam_element<CLIP, EMA>(&pp.x, &gg.x, &mm.x, &vv.x, &ee.x, k, c);
+    *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
+    *reinterpret_cast<float4*>(v + i4) = vv;
+    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
+  } else {
+    for (long i = i4; i < n; ++i) adam_element<CLIP, EMA>(p, g, m, v, ema, i, c);
+  }
+}
+
+// ---- the three shells: where lr / wd / bc1 / bc2_sqrt, the scale and the EMA coefficient come from ----------------------------------
 template <bool EMA>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, long n, float lr,
@@ -45,40 +101,9 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     ema_count(cell, step, k + 1.0);
   }
   if (!EMA) RD_TOUCH_CODE_FIRST(RD_TL_ADAM, blockIdx.x, 64);            // own code -> L2 by the first workgroups (rd_common.h; 3 012-byte kernel)
-  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  const float step_size = lr / bc1;
-  if (i4 + 3 < n) {
-    float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
-    float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float4 ee;
-    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float gr = G[c] + wd * P[c];
-      M[c] = b1 * M[c] + (1.f - b1) * gr;
-      V[c] = b2 * V[c] + (1.f - b2) * gr * gr;
-      P[c] -= step_size * M[c] / (sqrtf(V[c]) / bc2_sqrt + eps);
-      if (EMA) E[c] += ce * (P[c] - E[c]);
-    }
-    *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
-    *reinterpret_cast<float4*>(v + i4) = vv;
-    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
-  } else {
-    for (long i = i4; i < n; ++i) {
-      const float gr = g[i] + wd * p[i];
-      m[i] = b1 * m[i] + (1.f - b1) * gr;
-      v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-      p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
-      if (EMA) ema[i] += ce * (p[i] - ema[i]);
-    }
-  }
+  adam_thread<false, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f, ce);
 }
 
-// What kind of box is this?  (DESIGN.md "Box variance")  32 KB of straight-line code -- 4096 dependent 8-byte v_fma_f32, nothing the
-// compiler can fold --, one wave, clock64 around it: cold (its code in no cache) about 80 ticks per 64-byte line where the hardware
-// fetches instructions ahead, 400-450 where it does not; warm 45-55 / 75-95.  tools/probe_clocks.hip is the standalone form.
 // The same update with the optimizer's step state on the DEVICE: a captured launch cannot carry the host's bias corrections (they
 // change every step).  The state is eight doubles {t, beta1^t, beta2^t, lr, -, weight_decay, -, -} holding the values OF THE STEP
 // BEING APPLIED; this kernel only READS it.  The state is advanced -- t += 1, beta^t *= beta -- by an earlier launch of the same
@@ -104,35 +129,7 @@ __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const f
   if (!EMA) RD_TOUCH_CODE_FIRST(RD_TL_ADAM_DEV, blockIdx.x, 64);
   const float lr = (float)state->lr, wd = (float)state->wd;
   const float bc1 = (float)(1.0 - state->p1), bc2_sqrt = (float)sqrt(1.0 - state->p2);
-  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  const float step_size = lr / bc1;
-  if (i4 + 3 < n) {
-    float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
-    float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float4 ee;
-    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      const float gr = G[c4] + wd * P[c4];
-      M[c4] = b1 * M[c4] + (1.f - b1) * gr;
-      V[c4] = b2 * V[c4] + (1.f - b2) * gr * gr;
-      P[c4] -= step_size * M[c4] / (sqrtf(V[c4]) / bc2_sqrt + eps);
-      if (EMA) E[c4] += ce * (P[c4] - E[c4]);
-    }
-    *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
-    *reinterpret_cast<float4*>(v + i4) = vv;
-    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
-  } else {
-    for (long i = i4; i < n; ++i) {
-      const float gr = g[i] + wd * p[i];
-      m[i] = b1 * m[i] + (1.f - b1) * gr;
-      v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-      p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
-      if (EMA) ema[i] += ce * (p[i] - ema[i]);
-    }
-  }
+  adam_thread<false, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, 1.f, ce);
 }
 __global__ void k_adam_advance(double* state, float b1, float b2) { adam_state_advance(state, b1, b2); }
 
@@ -188,19 +185,12 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(const float* __restrict__
   if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
 }
 
-// a * b rounded on its own: never the multiply of a fused multiply-add (the compiler contracts a plain `a * b + c`, __fmul_rn included)
-__device__ __forceinline__ float mul_rounded(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-
 // The clip cell: slot 0 is read by every workgroup and written only by the host (an 8-byte copy, like lr); slots 1-4 are written by
 // thread 0 of workgroup 0 alone and read by no workgroup of any launch (the counters by that one thread, to add 1).
 struct ClipCell { double max_norm, last_norm, last_scale, skipped, clipped, pad0, pad1, pad2; };
 
-// k_adam_dev (DEV: step state in the device cell) / k_adam (host-computed corrections) on the clipped gradient.  The scale is its own
-// rounded multiply: at scale == 1 `gs` IS g and everything behind it is the expression of k_adam / k_adam_dev -- the same bits.
-// Weight decay is added AFTER the scale (torch clips the raw gradient; Adam adds wd * p inside its step).
+// k_adam_dev (DEV: step state in the device cell) / k_adam (host-computed corrections) on the clipped gradient: the prologue forms the
+// scale and decides whether the step happens at all, the update is adam_thread<CLIP = true>.
 template <bool DEV, bool EMA>
 __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n, float b1, float b2, float eps,
@@ -235,37 +225,7 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
   } else {
     lr = lr_h; wd = wd_h; bc1 = bc1_h; bc2_sqrt = bc2_sqrt_h;
   }
-  const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
-  if (i4 >= n) return;
-  const float step_size = lr / bc1;
-  if (i4 + 3 < n) {
-    float4 pp = *reinterpret_cast<float4*>(p + i4), gg = *reinterpret_cast<const float4*>(g + i4);
-    float4 mm = *reinterpret_cast<float4*>(m + i4), vv = *reinterpret_cast<float4*>(v + i4);
-    float4 ee;
-    if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
-    float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x; float* E = &ee.x;
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      const float gs = mul_rounded(G[c4], scale);
-      const float gr = gs + wd * P[c4];
-      M[c4] = b1 * M[c4] + (1.f - b1) * gr;
-      V[c4] = b2 * V[c4] + (1.f - b2) * gr * gr;
-      P[c4] -= step_size * M[c4] / (sqrtf(V[c4]) / bc2_sqrt + eps);
-      if (EMA) E[c4] += ce * (P[c4] - E[c4]);
-    }
-    *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
-    *reinterpret_cast<float4*>(v + i4) = vv;
-    if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
-  } else {
-    for (long i = i4; i < n; ++i) {
-      const float gs = mul_rounded(g[i], scale);
-      const float gr = gs + wd * p[i];
-      m[i] = b1 * m[i] + (1.f - b1) * gr;
-      v[i] = b2 * v[i] + (1.f - b2) * gr * gr;
-      p[i] -= step_size * m[i] / (sqrtf(v[i]) / bc2_sqrt + eps);
-      if (EMA) ema[i] += ce * (p[i] - ema[i]);
-    }
-  }
+  adam_thread<true, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, scale, ce);
 }
 
 // a <-> b over n floats, 16 bytes per thread and a scalar tail behind the last whole float4 (FlatAdam.swap_ema: the flat parameters and
@@ -281,6 +241,9 @@ __global__ __launch_bounds__(256) void k_swap_f32(float* __restrict__ a, float* 
   }
 }
 
+// What kind of box is this?  (DESIGN.md "Box variance")  32 KB of straight-line code -- 4096 dependent 8-byte v_fma_f32, nothing the
+// compiler can fold --, one wave, clock64 around it: cold (its code in no cache) about 80 ticks per 64-byte line where the hardware
+// fetches instructions ahead, 400-450 where it does not; warm 45-55 / 75-95.  tools/probe_clocks.hip is the standalone form.
 __global__ __launch_bounds__(64) void k_ifetch_probe(float* out, unsigned long long* t, float a, float b) {
   float x = (float)threadIdx.x;
   const unsigned long long c0 = clock64();
@@ -288,6 +251,64 @@ __global__ __launch_bounds__(64) void k_ifetch_probe(float* out, unsigned long l
   const unsigned long long c1 = clock64();
   out[threadIdx.x] = x;
   if (threadIdx.x == 0) t[0] = c1 - c0;
+}
+
+// ---- one launch path behind the eight rd_adam_step* entry points -------------------------------------------------------------------
+// What an entry point was given; the fields its form does not have stay zero.
+struct AdamCall {
+  int64_t n; float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
+  float beta1, beta2, eps;
+  void* stream;
+  float lr = 0.f, weight_decay = 0.f; int64_t step = 0;                         // host forms: the scalars of this step
+  const void* state = nullptr;                                                  // _dev forms: the device step state
+  const void* partial = nullptr; size_t partial_bytes = 0; void* clip = nullptr;   // _clip forms
+  float* ema = nullptr; void* ema_cell = nullptr;                               // _ema forms
+};
+
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+
+// the names the launch log knows the eight instantiations by, indexed [CLIP][EMA][DEV]
+constexpr const char* kAdamLaunch[2][2][2] = {{{"k_adam", "k_adam_dev"}, {"k_adam_ema", "k_adam_dev_ema"}},
+                                              {{"k_adam_clip", "k_adam_clip_dev"}, {"k_adam_clip_ema", "k_adam_clip_ema_dev"}}};
+
+// Validation, the host's bias corrections, the grid and the <DEV, CLIP, EMA> dispatch, once.  Everything refused is RD_EINVAL before
+// any launch.  n == 0 is an empty update ONLY for plain rd_adam_step (RD_OK, no launch: its callers may hold an empty buffer); every
+// other form refuses it, as rd_grad_sumsq does (the ABI as it grew; the host tests pin both answers).
+template <bool DEV, bool CLIP, bool EMA>
+int adam_launch(const AdamCall& c) {
+  RD_REQUIRE(DEV || c.step >= 1, "bad step");
+  RD_REQUIRE(!DEV || (c.state != nullptr && aligned16(c.state)), "NULL / misaligned optimizer state");
+  RD_REQUIRE(c.n > 0 || (c.n == 0 && !DEV && !CLIP && !EMA), "bad n");
+  RD_REQUIRE(c.param && c.grad && c.exp_avg && c.exp_avg_sq && (!CLIP || (c.partial && c.clip)), "NULL tensor");
+  RD_REQUIRE(!EMA || (c.ema && c.ema_cell), "NULL ema / ema_cell");
+  RD_REQUIRE(aligned16(c.param, c.grad, c.exp_avg, c.exp_avg_sq) && aligned16(c.partial, c.clip, c.ema, c.ema_cell),
+             "buffers must be 16-byte aligned");
+  RD_REQUIRE(!CLIP || c.partial_bytes >= (size_t)kClipGrid * sizeof(double), "partial buffer too small (rd_grad_sumsq_bytes)");
+  if (c.n == 0) return RD_OK;
+  float bc1 = 0.f, bc2_sqrt = 0.f;                                // the _dev forms form them on the device, from the state
+  if (!DEV) {
+    bc1 = (float)(1.0 - pow((double)c.beta1, (double)c.step));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)c.beta2, (double)c.step));
+  }
+  const long threads = (c.n + 3) / 4;
+  const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+  const hipStream_t stream = (hipStream_t)c.stream;
+  const AdamState* state = (const AdamState*)c.state;
+  EmaCell* cell = (EmaCell*)c.ema_cell;
+  const long step = EMA && !DEV ? (long)c.step : 0L;             // only the EMA count's slot needs the step number on the device
+  if constexpr (CLIP)
+    hipLaunchKernelGGL((k_adam_clip<DEV, EMA>), grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.beta1,
+                       c.beta2, c.eps, state, c.lr, c.weight_decay, bc1, bc2_sqrt, (const double*)c.partial, (double*)c.clip, c.ema,
+                       cell, step);
+  else if constexpr (DEV)
+    hipLaunchKernelGGL(k_adam_dev<EMA>, grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.beta1, c.beta2,
+                       c.eps, state, c.ema, cell);
+  else
+    hipLaunchKernelGGL(k_adam<EMA>, grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.lr, c.beta1,
+                       c.beta2, c.eps, c.weight_decay, bc1, bc2_sqrt, c.ema, cell, step);
+  return check_launch(kAdamLaunch[CLIP][EMA][DEV]);
 }
 
 }  // namespace
@@ -301,37 +322,20 @@ extern "C" void rd_debug_ifetch_probe(void* ticks_dev, void* scratch_dev, void* 
                      1.0000001f, 0.5f);
 }
 
+// ---- the eight forms of the update (include/raindrop_hip.h): rd_adam_step [_clip] [_ema] [_dev] --------------------------------------
 extern "C" int rd_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                             void* stream) {
-  RD_REQUIRE(n >= 0 && step >= 1, "bad n / step");
-  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
-               reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
-             "buffers must be 16-byte aligned");
-  if (n == 0) return RD_OK;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2),
-                     (float*)nullptr, (EmaCell*)nullptr, 0L);
-  return check_launch("k_adam");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.weight_decay = weight_decay; c.step = step;
+  return adam_launch<false, false, false>(c);
 }
 
-// rd_adam_step with the step state on the device: `state` = 64 bytes {t, beta1^t, beta2^t, lr, -, weight_decay, -, -} (doubles) OF THE
-// STEP BEING APPLIED (advanced beforehand: rd_adam_state_advance, or the step's first launch after rd_set_adam_state) -- ONE launch a
-// hipGraph can replay, read-only on the state.
 extern "C" int rd_adam_step_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                                 float beta1, float beta2, float eps, const void* state, void* stream) {
-  RD_REQUIRE(n > 0 && state != nullptr, "bad n / NULL optimizer state");
-  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-               reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(state)) & 15) == 0, "buffers must be 16-byte aligned");
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam_dev<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, (float*)nullptr, (EmaCell*)nullptr);
-  return check_launch("k_adam_dev");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state;
+  return adam_launch<true, false, false>(c);
 }
 
 extern "C" int rd_adam_state_advance(void* state, float beta1, float beta2, void* stream) {
@@ -340,7 +344,6 @@ extern "C" int rd_adam_state_advance(void* state, float beta1, float beta2, void
   return check_launch("k_adam_advance");
 }
 
-// ---- gradient clipping / non-finite guard -----------------------------------------------------------------------------------------
 extern "C" int32_t rd_grad_sumsq_grid(void) { return kClipGrid; }
 extern "C" size_t rd_grad_sumsq_bytes(void) { return (size_t)kClipGrid * sizeof(double); }
 
@@ -353,107 +356,58 @@ extern "C" int rd_grad_sumsq(int64_t n, const float* grad, void* partial, size_t
   return check_launch("k_sumsq_partial");
 }
 
-static int clip_args_ok(int64_t n, const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
-                        const void* partial, size_t partial_bytes, const void* clip) {
-  RD_REQUIRE(n > 0, "bad n");
-  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq && partial && clip, "NULL tensor");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-               reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(clip)) & 15) == 0,
-             "buffers must be 16-byte aligned");
-  RD_REQUIRE(partial_bytes >= rd_grad_sumsq_bytes(), "partial buffer too small (rd_grad_sumsq_bytes)");
-  return RD_OK;
-}
-
 extern "C" int rd_adam_step_clip(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
                                  float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
                                  size_t partial_bytes, void* clip, void* stream) {
-  RD_REQUIRE(step >= 1, "bad step");
-  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL((k_adam_clip<false, false>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)nullptr, lr, weight_decay, (float)bc1,
-                     (float)sqrt(bc2), (const double*)partial, (double*)clip, (float*)nullptr, (EmaCell*)nullptr, 0L);
-  return check_launch("k_adam_clip");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.weight_decay = weight_decay; c.step = step;
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  return adam_launch<false, true, false>(c);
 }
 
 extern "C" int rd_adam_step_clip_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
                                      float beta2, float eps, const void* state, const void* partial, size_t partial_bytes,
                                      void* clip, void* stream) {
-  RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
-  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL((k_adam_clip<true, false>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, 0.f, 0.f, 0.f, 0.f,
-                     (const double*)partial, (double*)clip, (float*)nullptr, (EmaCell*)nullptr, 0L);
-  return check_launch("k_adam_clip_dev");
-}
-
-// ---- exponential moving average of the weights: the EMA twins of the four updates, and the in-place exchange -------------------------
-static int ema_args_ok(int64_t n, const float* ema, const void* ema_cell) {
-  RD_REQUIRE(n > 0, "bad n");
-  RD_REQUIRE(ema && ema_cell, "NULL ema / ema_cell");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(ema) | reinterpret_cast<uintptr_t>(ema_cell)) & 15) == 0, "ema / ema_cell must be 16-byte aligned");
-  return RD_OK;
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state;
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  return adam_launch<true, true, false>(c);
 }
 
 extern "C" int rd_adam_step_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
                                 float beta2, float eps, float weight_decay, int64_t step, float* ema, void* ema_cell, void* stream) {
-  RD_REQUIRE(n > 0 && step >= 1, "bad n / step");
-  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) |
-               reinterpret_cast<uintptr_t>(exp_avg) | reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0,
-             "buffers must be 16-byte aligned");
-  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (long)n, lr, beta1, beta2, eps, weight_decay, (float)bc1, (float)sqrt(bc2), ema, (EmaCell*)ema_cell,
-                     (long)step);
-  return check_launch("k_adam_ema");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.weight_decay = weight_decay; c.step = step;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<false, false, true>(c);
 }
 
 extern "C" int rd_adam_step_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
                                     float beta2, float eps, const void* state, float* ema, void* ema_cell, void* stream) {
-  RD_REQUIRE(n > 0 && state != nullptr, "bad n / NULL optimizer state");
-  RD_REQUIRE(param && grad && exp_avg && exp_avg_sq, "NULL tensor");
-  RD_REQUIRE(((reinterpret_cast<uintptr_t>(param) | reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(exp_avg) |
-               reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(state)) & 15) == 0, "buffers must be 16-byte aligned");
-  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL(k_adam_dev<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
-                     exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, ema, (EmaCell*)ema_cell);
-  return check_launch("k_adam_dev_ema");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<true, false, true>(c);
 }
 
 extern "C" int rd_adam_step_clip_ema(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
                                      float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
                                      size_t partial_bytes, void* clip, float* ema, void* ema_cell, void* stream) {
-  RD_REQUIRE(step >= 1, "bad step");
-  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
-  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL((k_adam_clip<false, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)nullptr, lr, weight_decay, (float)bc1,
-                     (float)sqrt(bc2), (const double*)partial, (double*)clip, ema, (EmaCell*)ema_cell, (long)step);
-  return check_launch("k_adam_clip_ema");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.weight_decay = weight_decay; c.step = step;
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<false, true, true>(c);
 }
 
 extern "C" int rd_adam_step_clip_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
                                          float beta2, float eps, const void* state, const void* partial, size_t partial_bytes,
                                          void* clip, float* ema, void* ema_cell, void* stream) {
-  RD_REQUIRE(state != nullptr && (reinterpret_cast<uintptr_t>(state) & 15) == 0, "NULL / misaligned optimizer state");
-  if (int rc = clip_args_ok(n, param, grad, exp_avg, exp_avg_sq, partial, partial_bytes, clip)) return rc;
-  if (int rc = ema_args_ok(n, ema, ema_cell)) return rc;
-  const long threads = (n + 3) / 4;
-  hipLaunchKernelGGL((k_adam_clip<true, true>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                     exp_avg, exp_avg_sq, (long)n, beta1, beta2, eps, (const AdamState*)state, 0.f, 0.f, 0.f, 0.f,
-                     (const double*)partial, (double*)clip, ema, (EmaCell*)ema_cell, 0L);
-  return check_launch("k_adam_clip_ema_dev");
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state;
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<true, true, true>(c);
 }
 
 extern "C" int rd_swap_f32(int64_t n, float* a, float* b, void* stream) {

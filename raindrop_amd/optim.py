@@ -116,7 +116,7 @@ class FlatAdam:
         self.sync_clip_cell()
 
     def sync_clip_cell(self):
-        """push a changed `max_grad_norm` into the clip cell (TrainStep.run_full calls it next to sync_cell_hyper)"""
+        """push a changed `max_grad_norm` into the clip cell (part of sync_cells)"""
         if self.clip_cell is not None and self.max_grad_norm is not None and self._cell_max_norm != self.max_grad_norm:
             self.clip_cell[0:1] = torch.tensor([_check_max_grad_norm(self.max_grad_norm)], dtype=torch.float64,
                                                device=self.clip_cell.device)
@@ -148,10 +148,11 @@ class FlatAdam:
         self.sync_ema_cell()
         return (ops._ptr(self.ema), ops._ptr(self.ema_cell))
 
-    def _check_not_swapped(self, what):
+    def check_can_step(self, what):
+        """raises while the parameters are exchanged with their average; `what`: the caller, for the message"""
         if self.ema_swapped:
-            raise _lib.RaindropHipError("FlatAdam.%s: the parameters are exchanged with their average (swap_ema / ema_weights): a step "
-                                        "now would train the averaged weights -- swap back first" % what)
+            raise _lib.RaindropHipError("%s: the parameters are exchanged with their average (FlatAdam.swap_ema / ema_weights): a "
+                                        "step now would train the averaged weights -- swap back first" % what)
 
     def set_ema_decay(self, d):
         """A new decay (float in [0, 1)) for the steps enqueued from here on, captured ones included: one 8-byte copy into the EMA
@@ -161,7 +162,7 @@ class FlatAdam:
         self.sync_ema_cell()
 
     def sync_ema_cell(self):
-        """push a changed `ema_decay` into the EMA cell (TrainStep.run_full calls it next to sync_clip_cell), and keep the count
+        """push a changed `ema_decay` into the EMA cell (part of sync_cells), and keep the count
         readable when `t` was set from outside (load_state_dict, a restored snapshot): the launches keep the count in the slot the
         NEXT step number's parity selects, so after a jump of `t` the current count is copied into both slots, on the device."""
         if self.ema_cell is None or self.ema_decay is None:
@@ -198,67 +199,58 @@ class FlatAdam:
         finally:
             self.swap_ema()
 
-    def step(self):
-        self._check_not_swapped("step")
+    def _enqueue_update(self, dev):
+        """The update's launches -- the ONE place that names the eight entry points: rd_adam_step [_clip] [_ema] [_dev], behind
+        rd_grad_sumsq when clipping is on.  dev: the step state is read from the device cell, else `lr`, `weight_decay` and `t` of
+        this step travel as arguments.  The cells of what is on are synchronised on the way (the average's, then the threshold's)."""
+        clip, ema = self.max_grad_norm is not None, self.ema_decay is not None
         p, g = self.param.data, self.param.grad
-        if self.ema_decay is not None:
-            ema = self._ema_args()           # (in front of `t += 1`: it sees a `t` that was set from outside)
-            self.t += 1
-            self._cell_stale = True
-            self._ema_t = self.t
-            head = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq), float(self.lr),
-                    float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
-            if self.max_grad_norm is not None:
-                partial, nbytes, cell = self._clip_args()
-                _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
-                _lib.call("rd_adam_step_clip_ema", *head, partial, nbytes, cell, *ema, ops._stream())
-            else:
-                _lib.call("rd_adam_step_ema", *head, *ema, ops._stream())
-            return
-        self.t += 1
-        self._cell_stale = True              # a captured step that follows re-syncs the device step state (TrainStep.run_full)
-        if self.max_grad_norm is not None:
+        args = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq))
+        if dev:
+            args += (float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell))
+        else:
+            args += (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
+        tail = self._ema_args() if ema else ()
+        if clip:                             # the norm's partial sums, then the clipping instantiation of the update
             partial, nbytes, cell = self._clip_args()
             _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
-            _lib.call("rd_adam_step_clip", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
-                      float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                      self.t, partial, nbytes, cell, ops._stream())
-            return
-        _lib.call("rd_adam_step", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
-                  float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay),
-                  self.t, ops._stream())
+            args += (partial, nbytes, cell)
+        _lib.call("rd_adam_step" + "_clip" * clip + "_ema" * ema + "_dev" * dev, *args, *tail, ops._stream())
+
+    def step(self):
+        self.check_can_step("FlatAdam.step")
+        self.sync_ema_cell()                 # (in front of `t += 1`: it sees a `t` that was set from outside; a no-op with averaging off)
+        self.t += 1
+        self._cell_stale = True              # a captured step that follows re-syncs the device step state (sync_cells)
+        if self.ema_decay is not None:
+            self._ema_t = self.t
+        self._enqueue_update(dev=False)
 
     def step_captured(self, advance=True):
         """The update as launches a hipGraph can hold (rd_adam_step_dev: step count, beta^t, lr and weight decay live on the device).
         advance=True: a one-thread launch first moves the device state to this step (rd_adam_state_advance); advance=False: the
         caller's step already did (raindrop_amd.step.TrainStep.capture_full registers the cell -- `register_cell` -- and its first
         launch advances it: no extra launch).  Every replay is one step -- the owner of the graph keeps `self.t` in step
-        (`note_replay`) and pushes a changed lr / weight decay with `sync_cell_hyper` (no new capture)."""
-        self._check_not_swapped("step_captured")
+        (`note_replay`) and pushes what changed on the host with `sync_cells` (no new capture).  With averaging on, the step number
+        that selects the count's slot is the device state's t."""
+        self.check_can_step("FlatAdam.step_captured")
         self.sync_step_cell(create_only=True)
-        p, g = self.param.data, self.param.grad
         if advance:
             _lib.call("rd_adam_state_advance", ops._ptr(self.step_cell), float(self.betas[0]), float(self.betas[1]), ops._stream())
-        if self.ema_decay is not None:       # the EMA twins: the step number (the count's slot) is the device state's t
-            ema = self._ema_args()
-            head = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq), float(self.betas[0]),
-                    float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell))
-            if self.max_grad_norm is not None:
-                partial, nbytes, cell = self._clip_args()
-                _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
-                _lib.call("rd_adam_step_clip_ema_dev", *head, partial, nbytes, cell, *ema, ops._stream())
-            else:
-                _lib.call("rd_adam_step_ema_dev", *head, *ema, ops._stream())
-            return
-        if self.max_grad_norm is not None:   # the norm's partial sums, then the clipping instantiation of the update
-            partial, nbytes, cell = self._clip_args()
-            _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
-            _lib.call("rd_adam_step_clip_dev", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
-                      float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell), partial, nbytes, cell,
-                      ops._stream())
-            return
-        _lib.call("rd_adam_step_dev", p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq),
-                  float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell), ops._stream())
+        self._enqueue_update(dev=True)
+
+    def sync_cells(self, full=False):
+        """Bring the device cells up to the host's settings in front of a captured step, stream-ordered with the replays around it
+        and never a new capture: lr / weight decay (ReduceLROnPlateau, warm-up or cosine schedules), the clipping threshold, the
+        averaging decay -- small copies, and only of what changed -- and the whole step state {t, beta^t, lr, wd} when host-side
+        steps or load_state_dict left it stale, or always with `full` (in front of a capture)."""
+        if full or self._cell_stale:
+            self.sync_step_cell()            # (lr and weight decay are part of it)
+            self._cell_stale = False
+        else:
+            self.sync_cell_hyper()
+        self.sync_clip_cell()
+        self.sync_ema_cell()
 
     def register_cell(self, on=True):
         """(Un)register the device step state with this host thread's next rd_step_begin launches (include/raindrop_hip.h

@@ -868,9 +868,7 @@ class TrainStep(Step):
         cell + rd_adam_step_dev).  The host side of a step is then ONE replay (run_full).  Raises whatever the capture raises;
         the caller falls back to run_allreduce() + opt.step()."""
         flat = self.flat
-        opt.sync_step_cell()
-        opt.sync_clip_cell()                                               # FlatAdam(max_grad_norm=...): the threshold's cell (no-op when off)
-        opt.sync_ema_cell()                                                # FlatAdam(ema_decay=...): the decay's cell likewise
+        opt.sync_cells(full=True)                                          # the device step state and the cells of whatever the optimizer has on
         # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
         # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
         begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
@@ -920,22 +918,16 @@ class TrainStep(Step):
             raise _lib.RaindropHipError("TrainStep.run_full: call capture_full(opt) first")
         if self._param_ptrs() != self._ptrs:
             raise _lib.RaindropHipError("TrainStep: a parameter or gradient buffer moved since construction: build a new TrainStep")
-        if getattr(self._full_opt, "ema_swapped", False):                  # FlatAdam.swap_ema / ema_weights(): the parameters ARE the average now
-            raise _lib.RaindropHipError("TrainStep.run_full: the optimizer's parameters are exchanged with their average "
-                                        "(FlatAdam.swap_ema): a replay would train the averaged weights -- swap back first")
+        self._full_opt.check_can_step("TrainStep.run_full")               # FlatAdam.swap_ema / ema_weights(): the parameters ARE the average now
         if self.feed is not None:
             self.feed._take("TrainStep.run_full")
         if self._full_opt.hyper() != self._full_hyper:                     # betas / eps changed: launch constants of the captured
             cell = self.seed_cell.clone()                                  # Adam -- capture again
             self.capture_full(self._full_opt)                              # (the warm-up passes advance the dropout stream: put it back)
             self.seed_cell.copy_(cell)
-        self._full_opt.sync_cell_hyper()                                   # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259;
-                                                                           # warm-up / cosine schedules): an 8-byte copy, no new capture
-        self._full_opt.sync_clip_cell()                                    # the clipping threshold likewise (FlatAdam.max_grad_norm)
-        self._full_opt.sync_ema_cell()                                     # and the averaging decay (FlatAdam.ema_decay)
-        if getattr(self._full_opt, "_cell_stale", False):                  # host-side steps were taken since: device state follows self.t
-            self._full_opt.sync_step_cell()
-            self._full_opt._cell_stale = False
+        self._full_opt.sync_cells()                                        # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259; warm-up /
+                                                                           # cosine schedules), threshold, decay: 8-byte copies, no new capture; and
+                                                                           # the step state, when host-side steps were taken since
         self.graph_full.replay()
         self._full_opt.note_replay()
         for p, v in zip(self.flat.params, self.flat.views):

@@ -81,6 +81,63 @@ def test_ema_against_float64(n, form, mode):
     assert float((opt.ema - p.detach()).abs().max()) > 0.0                      # an average, not a copy
 
 
+# ---- 1b. all eight forms of the update against float64 ------------------------------------------------------------------------------
+ALL_FORMS = {"plain": ("step", {}), "dev": ("step_captured", {}), "clip": ("step", dict(max_grad_norm=1.0)),
+             "clip_dev": ("step_captured", dict(max_grad_norm=1.0)),
+             **{k: (m, dict(kw, ema_decay=0.9)) for k, (m, kw) in FORMS.items()}}
+U = 2.0 ** -24                                                                  # one fp32 rounding, relative
+
+
+@pytest.mark.parametrize("form", list(ALL_FORMS))
+@pytest.mark.parametrize("n", [1, 5, 1027, 70001])
+def test_update_against_float64(n, form):
+    """p, exp_avg, exp_avg_sq of every entry point -- rd_adam_step [_clip] [_ema] [_dev] -- at the sizes of test 1 (1 and 5: the
+    scalar tail alone; 1027: float4 slots and a tail in the last workgroup; 70001: many workgroups), weight decay on, 12 steps.
+    Each step is checked on its own, element by element, against the update formed in float64 from the fp32 state read back
+    before it, so the bounds are those of ONE step's roundings (U = 2^-24 each, first order, 1% on top for the second):
+      gr = g s + wd p: three roundings and, clipping, the float the scale is rounded to: |d gr| <= 4 U A, A = |g s| + |wd p|
+      m' = b1 m + (1 - b1) gr: two products, one sum: |d m'| <= U (2 b1 |m| + 6 (1 - b1) A)     (1 - b1, 1 - b2 are exact in fp32)
+      v' = b2 v + (1 - b2) gr gr: three products, one sum, gr twice: |d v'| <= U (2 b2 v + 3 (1 - b2) gr^2 + 8 (1 - b2) |gr| A)
+      p' = p - u, u = (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps) formed from the fp32 m', v' the launch stored: lr, bc1 and
+      sqrt(bc2) rounded to float, one product, one sum, and three divisions and a square root counted at one ulp (2 U) each: 13 U |u|;
+      the final difference one more: |d p'| <= U (13 |u| + |p'|).
+    The clip forms: s = min(1, 1 / (norm + 1e-6)) from numpy's float64 norm of the same gradient (max_grad_norm = 1: all but the
+    smallest gradients are clipped), and the device's own scale must agree with it to (n + 4) 2^-52 relative: n 2^-52 for the norm,
+    the bound of test_norm_against_float64, and the sum and the quotient behind it, 2^-53 each on either side."""
+    method, kw = ALL_FORMS[form]
+    lr, wd, eps = 1e-2, 0.01, 1e-8
+    p, opt = _flat(n, seed=n, weight_decay=wd, **kw)
+    if method == "step_captured":
+        opt.sync_step_cell()
+    b1, b2 = (float(np.float32(b)) for b in opt.betas)                          # the betas as the launches see them
+    worst = dict(m=0.0, v=0.0, p=0.0)
+    for t, g in enumerate(_grads(n, seed=n + 1), start=1):
+        p0, m0, v0 = (x.detach().cpu().double().numpy() for x in (p, opt.exp_avg, opt.exp_avg_sq))
+        g64 = g.cpu().double().numpy()
+        _one(p, opt, method, g)
+        p1, m1, v1 = (x.detach().cpu().double().numpy() for x in (p, opt.exp_avg, opt.exp_avg_sq))
+        s = 1.0
+        if "max_grad_norm" in kw:
+            norm = float(np.sqrt(np.sum(g64 ** 2)))
+            s = min(1.0, 1.0 / (norm + 1e-6))
+            assert abs(opt.grad_stats()["scale"] - s) <= (n + 4) * 2.0 ** -52 * s
+        gs, wp = g64 * s, float(np.float32(wd)) * p0
+        gr, A = gs + wp, np.abs(gs) + np.abs(wp)
+        m_ref = b1 * m0 + (1 - b1) * gr
+        v_ref = b2 * v0 + (1 - b2) * gr * gr
+        u = (lr / (1 - b1 ** t)) * m1 / (np.sqrt(v1) / math.sqrt(1 - b2 ** t) + float(np.float32(eps)))
+        p_ref = p0 - u
+        tol = dict(m=U * (2 * b1 * np.abs(m0) + 6 * (1 - b1) * A),
+                   v=U * (2 * b2 * v0 + 3 * (1 - b2) * gr * gr + 8 * (1 - b2) * np.abs(gr) * A),
+                   p=U * (13 * np.abs(u) + np.abs(p_ref)))
+        for key, got, ref in (("m", m1, m_ref), ("v", v1, v_ref), ("p", p1, p_ref)):
+            ratio = float((np.abs(got - ref) / (1.01 * tol[key])).max())
+            worst[key] = max(worst[key], ratio)
+    print("n %d %s: worst error / bound over %d steps: exp_avg %.3f, exp_avg_sq %.3f, p %.3f" % (n, form, N_STEPS, worst["m"], worst["v"], worst["p"]))
+    assert worst["m"] <= 1.0 and worst["v"] <= 1.0 and worst["p"] <= 1.0
+    assert opt.t == N_STEPS and float(opt.exp_avg.abs().min()) > 0.0            # every element was updated
+
+
 # ---- 2. parameters and moments are the plain twin's ------------------------------------------------------------------------------
 @pytest.mark.parametrize("form", list(FORMS))
 def test_parameters_and_moments_are_bit_equal_to_the_plain_twin(form):
