@@ -382,7 +382,8 @@ int rd_masked_mean_bwd(const rd_shape* s, int32_t D, const float* dout, int32_t 
 
 /* ---- caller step (a19): the optimizer of code/Raindrop.py:256 ------------------------------- */
 
-/* torch.optim.Adam (no amsgrad; weight_decay added to the gradient) over one flat buffer of n floats, as ONE launch, in eight forms:
+/* torch.optim.Adam (no amsgrad; weight_decay added to the gradient) over one flat buffer of n floats, as ONE launch, in eight forms
+ * (and their eight _grp twins further down: per-group learning rate and weight decay, coupled or decoupled):
  *     rd_adam_step [_clip] [_ema] [_dev]
  *   m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps),   g = grad + weight_decay * p.
  * Shared arguments: `n`; `param`, `grad`, `exp_avg`, `exp_avg_sq` (n floats each, 16-byte aligned); `beta1`, `beta2`, `eps` (launch
@@ -449,6 +450,44 @@ int rd_adam_step_clip_ema(int64_t n, float* param, const float* grad, float* exp
 int rd_adam_step_clip_ema_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
                               float beta2, float eps, const void* state, const void* partial, size_t partial_bytes, void* clip,
                               float* ema, void* ema_cell, void* stream);
+/* _grp: parameter groups and decoupled weight decay (raindrop_amd.optim.FlatAdam(groups=..., decoupled=...)): the eight forms above
+ * with `chunk_group` and `group_cell` in front of the stream.
+ *   `chunk_group`: ceil(n / 64) bytes of device memory; byte c is the group id (0..15) of elements [64c, 64c + 64).  The caller lays
+ *     the buffer out so that no 64-element chunk holds elements of two groups (raindrop_amd.dp.FlatGradAllReduce starts every tensor
+ *     on a multiple of 64; the padding behind a tensor takes its group).  The launch uses `byte & 15`: no map indexes outside the cell.
+ *   `group_cell`: 16 rows of four doubles {lr_scale, wd_coupled, wd_decoupled, 0}, 512 bytes, 16-byte aligned.  The launch only reads
+ *     it; the caller writes a row with one 32-byte copy (not a new capture), as it writes slot 0 of the clip and EMA cells.
+ * Element i of group r, with lr the `lr` argument (host forms) or slot 3 of `state` (_dev forms):
+ *     lr_r = (float)((double)lr * lr_scale[r]);   p *= (float)(1 - (double)lr_r * wd_decoupled[r])      (torch.optim.AdamW's decay)
+ *     g = grad * scale + (float)wd_coupled[r] * p;  m, v as above;  p -= lr_r / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+ * `scale` (_clip) stays that of the GLOBAL norm over all groups, the step count, the bias corrections and the EMA coefficient are
+ * shared by all groups, and a skipped step stores nothing in any group.  `weight_decay` of the host forms and slot 5 of `state` are
+ * NOT read: the caller resolves every group's decay into its row.  A row {1, wd, 0, 0} gives the bits of the form without _grp.
+ * RD_EINVAL in addition to the twin's: NULL `chunk_group` / `group_cell`, a misaligned `group_cell`, n <= 0 (all eight forms). */
+int rd_adam_step_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, int64_t step, const uint8_t* chunk_group, const void* group_cell,
+                     void* stream);
+int rd_adam_step_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1, float beta2,
+                         float eps, const void* state, const uint8_t* chunk_group, const void* group_cell, void* stream);
+int rd_adam_step_clip_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int64_t step, const void* partial, size_t partial_bytes,
+                          void* clip, const uint8_t* chunk_group, const void* group_cell, void* stream);
+int rd_adam_step_clip_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                              float beta2, float eps, const void* state, const void* partial, size_t partial_bytes, void* clip,
+                              const uint8_t* chunk_group, const void* group_cell, void* stream);
+int rd_adam_step_ema_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, int64_t step, float* ema, void* ema_cell,
+                         const uint8_t* chunk_group, const void* group_cell, void* stream);
+int rd_adam_step_ema_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                             float beta2, float eps, const void* state, float* ema, void* ema_cell, const uint8_t* chunk_group,
+                             const void* group_cell, void* stream);
+int rd_adam_step_clip_ema_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                              float beta2, float eps, float weight_decay, int64_t step, const void* partial, size_t partial_bytes,
+                              void* clip, float* ema, void* ema_cell, const uint8_t* chunk_group, const void* group_cell,
+                              void* stream);
+int rd_adam_step_clip_ema_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                  float beta2, float eps, const void* state, const void* partial, size_t partial_bytes, void* clip,
+                                  float* ema, void* ema_cell, const uint8_t* chunk_group, const void* group_cell, void* stream);
 /* a <-> b over n floats in place (16-byte accesses, a scalar tail; capturable): FlatAdam.swap_ema exchanges the flat parameters and
  * their average, so that whatever holds the parameters' addresses evaluates the average.  a, b: 16-byte aligned, not overlapping.
  * RD_EINVAL: NULL or misaligned pointers, n <= 0. */

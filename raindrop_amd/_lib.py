@@ -122,6 +122,20 @@ SIGNATURES = {
                                         _P, c_size_t, _P, _P, _P, _P]),
     "rd_adam_step_clip_ema_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P, _P, _P]),
     "rd_swap_f32": (c_int32, [ctypes.c_int64, _P, _P, _P]),
+    # parameter groups / decoupled weight decay (raindrop_amd.optim.FlatAdam(groups=..., decoupled=...)): the twins take `chunk_group`, `group_cell` in front of the stream
+    "rd_adam_step_grp": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float,
+                                   ctypes.c_int64, _P, _P, _P]),
+    "rd_adam_step_grp_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P, _P]),
+    "rd_adam_step_clip_grp": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, ctypes.c_int64,
+                                        _P, c_size_t, _P, _P, _P, _P]),
+    "rd_adam_step_clip_grp_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P, _P, _P]),
+    "rd_adam_step_ema_grp": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float,
+                                       ctypes.c_int64, _P, _P, _P, _P, _P]),
+    "rd_adam_step_ema_grp_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, _P, _P, _P, _P]),
+    "rd_adam_step_clip_ema_grp": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, ctypes.c_int64,
+                                            _P, c_size_t, _P, _P, _P, _P, _P, _P]),
+    "rd_adam_step_clip_ema_grp_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P, _P,
+                                                _P, _P, _P]),
     "rd_linear_fwd": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_fwd_fp32": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32, _P]),
     "rd_linear_bwd_input": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P]),

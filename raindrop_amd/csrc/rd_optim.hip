@@ -1,10 +1,11 @@
 // rd_optim.hip -- Adam update over one flat parameter buffer (the optimizer of code/Raindrop.py:256,
 // torch.optim.Adam(lr=1e-4) with default betas / eps, no amsgrad).  With the live parameters and
 // their gradients held in flat buffers (raindrop_amd/dp.py) the whole update is one elementwise pass.
-// One body, three kernel shells, eight instantiations: the update is written ONCE (adam_element / adam_thread, templates on
-// <CLIP, EMA>); k_adam<EMA>, k_adam_dev<EMA> and k_adam_clip<DEV, EMA> only fetch their scalars and call it; the eight extern "C"
-// entry points fill one AdamCall and share one launcher (adam_launch<DEV, CLIP, EMA>).  A flag that is off does not exist in the
-// instruction stream (rule 40): profiles/adam_refactor_isa.txt holds the eight instantiations against the six hand-kept copies.
+// One body, four kernel shells, sixteen instantiations: the update is written ONCE (adam_element / adam_thread, templates on
+// <CLIP, EMA, GROUPS>); k_adam<EMA>, k_adam_dev<EMA>, k_adam_clip<DEV, EMA> and k_adam_grp<DEV, CLIP, EMA> only fetch their scalars
+// and call it; the sixteen extern "C" entry points fill one AdamCall and share one launcher (adam_launch<DEV, CLIP, EMA, GROUPS>).
+// A flag that is off does not exist in the instruction stream (rule 40): profiles/adam_refactor_isa.txt holds the eight ungrouped
+// instantiations against the six hand-kept copies, profiles/param_groups_isa.txt the same eight with and without the GROUPS flag.
 #include "rd_common.h"
 
 namespace rd {
@@ -37,6 +38,15 @@ __device__ __forceinline__ void ema_count(EmaCell* cell, long step, double k_nex
   if (blockIdx.x == 0 && threadIdx.x == 0) cell->k[(step + 1) & 1] = k_next;
 }
 
+// ---- parameter groups and decoupled weight decay (DESIGN.md "Parameter groups") ------------------------------------------------------
+// dp.FlatGradAllReduce starts every tensor on a 64-element boundary, so elements [64c, 64c + 64) -- and with them the four elements of
+// every thread -- belong to ONE tensor (or to the zero padding behind it): the group of a thread is one byte of `chunk_group`, its
+// scalars one 32-byte row of the group cell.  Sixteen rows {lr_scale, wd_coupled, wd_decoupled, 0}; the byte is masked to 0..15, so
+// no map can index outside the cell.  The launches only read both; the host writes a row with one 32-byte copy (not a new capture).
+// What stays global: the clip scale (the norm over ALL groups), the step count and the bias corrections, the EMA coefficient.
+struct GroupRow { double lr_scale, wd_coupled, wd_decoupled, pad; };
+constexpr int kGroupRows = 16;
+
 // a * b rounded on its own: never the multiply of a fused multiply-add (the compiler contracts a plain `a * b + c`, __fmul_rn included)
 __device__ __forceinline__ float mul_rounded(float a, float b) {
 #pragma clang fp contract(off)
@@ -48,27 +58,43 @@ __device__ __forceinline__ float mul_rounded(float a, float b) {
 // behind it is the expression without the flag: the same bits.  Weight decay is added AFTER the scale (torch clips the raw gradient;
 // Adam adds wd * p inside its step).  EMA: the average follows the new parameter in the same thread.  Without a flag its operand is
 // not in the expression at all (not `* 1.0f`: that is another instruction stream).
-struct AdamCoef { float b1, b2, eps, wd, bc2_sqrt, step_size, scale, ce; };
+// GROUPS: torch.optim.AdamW's p *= 1 - lr * weight_decay stands in front of everything (`shrink`; 1 where the group's decay is coupled).
+struct AdamCoef { float b1, b2, eps, wd, bc2_sqrt, step_size, scale, ce, shrink; };
 
 // (Buffers and index, not references: element i of the flat buffers in the tail, of the thread's four registers in the float4 path;
 // each access is then formed where the expression uses it, which keeps the tail's loads and stores in the order they always had.)
-template <bool CLIP, bool EMA, typename I>
+template <bool CLIP, bool EMA, bool GROUPS, typename I>
 __device__ __forceinline__ void adam_element(float* p, const float* g, float* m, float* v, float* e, I i, const AdamCoef& c) {
-  const float gr = (CLIP ? mul_rounded(g[i], c.scale) : g[i]) + c.wd * p[i];
+  // (GROUPS: the decayed parameter is held in a value of its own.  Without the flag p[i] is named where it always was: reading it
+  // once into a value moved the tail's loads and with them the products the FMA contraction takes -- other bits, see adam_thread.)
+  const float pd = GROUPS ? mul_rounded(p[i], c.shrink) : 0.f;
+  const float gr = (CLIP ? mul_rounded(g[i], c.scale) : g[i]) + c.wd * (GROUPS ? pd : p[i]);
   m[i] = c.b1 * m[i] + (1.f - c.b1) * gr;
   v[i] = c.b2 * v[i] + (1.f - c.b2) * gr * gr;
-  p[i] -= c.step_size * m[i] / (sqrtf(v[i]) / c.bc2_sqrt + c.eps);
+  const float step = c.step_size * m[i] / (sqrtf(v[i]) / c.bc2_sqrt + c.eps);
+  if (GROUPS) p[i] = pd - step;
+  else p[i] -= step;
   if (EMA) e[i] += c.ce * (p[i] - e[i]);
 }
 
 // One thread's four elements: 16-byte loads and stores, or -- the last thread of the buffer -- a scalar tail.  (The buffers are the
 // kernels' __restrict__ arguments; the qualifier is not repeated here.)
-template <bool CLIP, bool EMA>
+// GROUPS: lr and wd are the thread's group's -- lr times the row's scale (formed in double, rounded once), the row's coupled decay;
+// the `wd` argument is not read.
+template <bool CLIP, bool EMA, bool GROUPS = false>
 __device__ __forceinline__ void adam_thread(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1,
-                                            float b2, float eps, float wd, float bc1, float bc2_sqrt, float scale, float ce) {
+                                            float b2, float eps, float wd, float bc1, float bc2_sqrt, float scale, float ce,
+                                            const uint8_t* chunk_group = nullptr, const GroupRow* rows = nullptr) {
   const long i4 = (blockIdx.x * (long)blockDim.x + threadIdx.x) * 4;
   if (i4 >= n) return;
-  const AdamCoef c = {b1, b2, eps, wd, bc2_sqrt, lr / bc1, scale, ce};
+  float shrink = 1.f;
+  if (GROUPS) {
+    const GroupRow r = rows[chunk_group[i4 >> 6] & (kGroupRows - 1)];
+    lr = (float)((double)lr * r.lr_scale);
+    wd = (float)r.wd_coupled;
+    shrink = (float)(1.0 - (double)lr * r.wd_decoupled);
+  }
+  const AdamCoef c = {b1, b2, eps, wd, bc2_sqrt, lr / bc1, scale, ce, shrink};
   if (i4 + 3 < n) {
     // p is loaded LAST.  Which of two products a sum fuses into its FMA follows the order of the sum's operands, and the optimiser
     // orders them by where their loads stand (it sees this function unrolled before it sees the kernel): with p first,
@@ -79,12 +105,12 @@ __device__ __forceinline__ void adam_thread(float* p, const float* g, float* m, 
     float4 ee;
     if (EMA) ee = *reinterpret_cast<float4*>(ema + i4);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) adam_element<CLIP, EMA>(&pp.x, &gg.x, &mm.x, &vv.x, &ee.x, k, c);
+    for (int k = 0; k < 4; ++k) adam_element<CLIP, EMA, GROUPS>(&pp.x, &gg.x, &mm.x, &vv.x, &ee.x, k, c);
     *reinterpret_cast<float4*>(p + i4) = pp; *reinterpret_cast<float4*>(m + i4) = mm;
     *reinterpret_cast<float4*>(v + i4) = vv;
     if (EMA) *reinterpret_cast<float4*>(ema + i4) = ee;
   } else {
-    for (long i = i4; i < n; ++i) adam_element<CLIP, EMA>(p, g, m, v, ema, i, c);
+    for (long i = i4; i < n; ++i) adam_element<CLIP, EMA, GROUPS>(p, g, m, v, ema, i, c);
   }
 }
 
@@ -228,6 +254,49 @@ __global__ __launch_bounds__(256) void k_adam_clip(float* __restrict__ p, const 
   adam_thread<true, EMA>(p, g, m, v, ema, n, lr, b1, b2, eps, wd, bc1, bc2_sqrt, scale, ce);
 }
 
+// The grouped update, all eight forms behind one shell (the three shells above keep their parameter lists and with them their
+// instruction streams): k_adam / k_adam_dev / k_adam_clip's prologues as they stand there, selected by the flags, then
+// adam_thread<CLIP, EMA, GROUPS = true>.  The step cell's wd slot and a host weight decay are not read: every group's decay is in its row.
+template <bool DEV, bool CLIP, bool EMA>
+__global__ __launch_bounds__(256) void k_adam_grp(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, long n, float b1, float b2, float eps,
+                                                  const AdamState* __restrict__ state, float lr_h, float bc1_h, float bc2_sqrt_h,
+                                                  const double* __restrict__ partial, double* clip, float* __restrict__ ema,
+                                                  EmaCell* cell, long step_h, const uint8_t* __restrict__ chunk_group,
+                                                  const GroupRow* __restrict__ rows) {
+  bool finite = true;
+  float scale = 1.f;
+  if (CLIP) {                                                    // (k_adam_clip's prologue: the same sum in the same order)
+    double sum = 0.0;
+    for (int k = 0; k < kClipGrid; ++k) sum += partial[k];
+    const double max_norm = clip[0];
+    finite = fabs(sum) <= 1.7976931348623157e308;
+    const double norm = sqrt(sum);
+    const double sc = norm > max_norm ? max_norm / (norm + 1e-6) : 1.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      clip[1] = norm;
+      clip[2] = finite ? sc : 0.0;
+      if (!finite) clip[3] += 1.0;
+      else if (sc < 1.0) clip[4] += 1.0;
+    }
+    scale = (float)sc;
+  }
+  float ce = 0.f;
+  if (EMA) {
+    const long step = DEV ? (long)state->t : step_h;
+    double k;
+    ce = ema_coef(cell, step, k);
+    ema_count(cell, step, finite ? k + 1.0 : k);
+  }
+  if (!finite) return;                                           // uniform over the launch: no group stores anything
+  float lr = lr_h, bc1 = bc1_h, bc2_sqrt = bc2_sqrt_h;
+  if (DEV) {
+    lr = (float)state->lr;
+    bc1 = (float)(1.0 - state->p1); bc2_sqrt = (float)sqrt(1.0 - state->p2);
+  }
+  adam_thread<CLIP, EMA, true>(p, g, m, v, ema, n, lr, b1, b2, eps, 0.f, bc1, bc2_sqrt, scale, ce, chunk_group, rows);
+}
+
 // a <-> b over n floats, 16 bytes per thread and a scalar tail behind the last whole float4 (FlatAdam.swap_ema: the flat parameters and
 // their average change places IN PLACE, so every holder of a parameter address -- EvalStep, feed.validate -- reads the other one)
 __global__ __launch_bounds__(256) void k_swap_f32(float* __restrict__ a, float* __restrict__ b, long n) {
@@ -253,7 +322,7 @@ __global__ __launch_bounds__(64) void k_ifetch_probe(float* out, unsigned long l
   if (threadIdx.x == 0) t[0] = c1 - c0;
 }
 
-// ---- one launch path behind the eight rd_adam_step* entry points -------------------------------------------------------------------
+// ---- one launch path behind the sixteen rd_adam_step* entry points -------------------------------------------------------------------
 // What an entry point was given; the fields its form does not have stay zero.
 struct AdamCall {
   int64_t n; float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
@@ -263,26 +332,32 @@ struct AdamCall {
   const void* state = nullptr;                                                  // _dev forms: the device step state
   const void* partial = nullptr; size_t partial_bytes = 0; void* clip = nullptr;   // _clip forms
   float* ema = nullptr; void* ema_cell = nullptr;                               // _ema forms
+  const uint8_t* chunk_group = nullptr; const void* group_cell = nullptr;       // _grp forms
 };
 
 inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
   return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
 }
 
-// the names the launch log knows the eight instantiations by, indexed [CLIP][EMA][DEV]
-constexpr const char* kAdamLaunch[2][2][2] = {{{"k_adam", "k_adam_dev"}, {"k_adam_ema", "k_adam_dev_ema"}},
-                                              {{"k_adam_clip", "k_adam_clip_dev"}, {"k_adam_clip_ema", "k_adam_clip_ema_dev"}}};
+// the names the launch log knows the sixteen instantiations by, indexed [GROUPS][CLIP][EMA][DEV]
+constexpr const char* kAdamLaunch[2][2][2][2] = {
+    {{{"k_adam", "k_adam_dev"}, {"k_adam_ema", "k_adam_dev_ema"}},
+     {{"k_adam_clip", "k_adam_clip_dev"}, {"k_adam_clip_ema", "k_adam_clip_ema_dev"}}},
+    {{{"k_adam_grp", "k_adam_grp_dev"}, {"k_adam_ema_grp", "k_adam_ema_grp_dev"}},
+     {{"k_adam_clip_grp", "k_adam_clip_grp_dev"}, {"k_adam_clip_ema_grp", "k_adam_clip_ema_grp_dev"}}}};
 
-// Validation, the host's bias corrections, the grid and the <DEV, CLIP, EMA> dispatch, once.  Everything refused is RD_EINVAL before
-// any launch.  n == 0 is an empty update ONLY for plain rd_adam_step (RD_OK, no launch: its callers may hold an empty buffer); every
-// other form refuses it, as rd_grad_sumsq does (the ABI as it grew; the host tests pin both answers).
-template <bool DEV, bool CLIP, bool EMA>
+// Validation, the host's bias corrections, the grid and the <DEV, CLIP, EMA, GROUPS> dispatch, once.  Everything refused is RD_EINVAL
+// before any launch.  n == 0 is an empty update ONLY for plain rd_adam_step (RD_OK, no launch: its callers may hold an empty buffer);
+// every other form refuses it, as rd_grad_sumsq does (the ABI as it grew; the host tests pin both answers).
+template <bool DEV, bool CLIP, bool EMA, bool GROUPS = false>
 int adam_launch(const AdamCall& c) {
   RD_REQUIRE(DEV || c.step >= 1, "bad step");
   RD_REQUIRE(!DEV || (c.state != nullptr && aligned16(c.state)), "NULL / misaligned optimizer state");
-  RD_REQUIRE(c.n > 0 || (c.n == 0 && !DEV && !CLIP && !EMA), "bad n");
+  RD_REQUIRE(c.n > 0 || (c.n == 0 && !DEV && !CLIP && !EMA && !GROUPS), "bad n");
   RD_REQUIRE(c.param && c.grad && c.exp_avg && c.exp_avg_sq && (!CLIP || (c.partial && c.clip)), "NULL tensor");
   RD_REQUIRE(!EMA || (c.ema && c.ema_cell), "NULL ema / ema_cell");
+  RD_REQUIRE(!GROUPS || (c.chunk_group && c.group_cell), "NULL chunk_group / group_cell");
+  RD_REQUIRE(aligned16(c.group_cell), "group_cell must be 16-byte aligned");
   RD_REQUIRE(aligned16(c.param, c.grad, c.exp_avg, c.exp_avg_sq) && aligned16(c.partial, c.clip, c.ema, c.ema_cell),
              "buffers must be 16-byte aligned");
   RD_REQUIRE(!CLIP || c.partial_bytes >= (size_t)kClipGrid * sizeof(double), "partial buffer too small (rd_grad_sumsq_bytes)");
@@ -298,7 +373,11 @@ int adam_launch(const AdamCall& c) {
   const AdamState* state = (const AdamState*)c.state;
   EmaCell* cell = (EmaCell*)c.ema_cell;
   const long step = EMA && !DEV ? (long)c.step : 0L;             // only the EMA count's slot needs the step number on the device
-  if constexpr (CLIP)
+  if constexpr (GROUPS)
+    hipLaunchKernelGGL((k_adam_grp<DEV, CLIP, EMA>), grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.beta1,
+                       c.beta2, c.eps, state, c.lr, bc1, bc2_sqrt, (const double*)c.partial, (double*)c.clip, c.ema, cell, step,
+                       c.chunk_group, (const GroupRow*)c.group_cell);
+  else if constexpr (CLIP)
     hipLaunchKernelGGL((k_adam_clip<DEV, EMA>), grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.beta1,
                        c.beta2, c.eps, state, c.lr, c.weight_decay, bc1, bc2_sqrt, (const double*)c.partial, (double*)c.clip, c.ema,
                        cell, step);
@@ -308,7 +387,7 @@ int adam_launch(const AdamCall& c) {
   else
     hipLaunchKernelGGL(k_adam<EMA>, grid, block, 0, stream, c.param, c.grad, c.exp_avg, c.exp_avg_sq, (long)c.n, c.lr, c.beta1,
                        c.beta2, c.eps, c.weight_decay, bc1, bc2_sqrt, c.ema, cell, step);
-  return check_launch(kAdamLaunch[CLIP][EMA][DEV]);
+  return check_launch(kAdamLaunch[GROUPS][CLIP][EMA][DEV]);
 }
 
 }  // namespace
@@ -322,7 +401,7 @@ extern "C" void rd_debug_ifetch_probe(void* ticks_dev, void* scratch_dev, void* 
                      1.0000001f, 0.5f);
 }
 
-// ---- the eight forms of the update (include/raindrop_hip.h): rd_adam_step [_clip] [_ema] [_dev] --------------------------------------
+// ---- the sixteen forms of the update (include/raindrop_hip.h): rd_adam_step [_clip] [_ema] [_grp] [_dev] -----------------------------
 extern "C" int rd_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                             float lr, float beta1, float beta2, float eps, float weight_decay, int64_t step,
                             void* stream) {
@@ -409,6 +488,85 @@ extern "C" int rd_adam_step_clip_ema_dev(int64_t n, float* param, const float* g
   c.ema = ema; c.ema_cell = ema_cell;
   return adam_launch<true, true, true>(c);
 }
+
+// The grouped twins: the arguments of the form without _grp, then `chunk_group` and `group_cell` in front of the stream
+// (`weight_decay` of the host forms is accepted and not read: every group's decay is in its row of the cell).
+#define RD_GRP(c) (c).chunk_group = chunk_group, (c).group_cell = group_cell
+extern "C" int rd_adam_step_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, int64_t step, const uint8_t* chunk_group,
+                                const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.step = step; RD_GRP(c);
+  return adam_launch<false, false, false, true>(c);
+}
+
+extern "C" int rd_adam_step_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                    float beta2, float eps, const void* state, const uint8_t* chunk_group, const void* group_cell,
+                                    void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state; RD_GRP(c);
+  return adam_launch<true, false, false, true>(c);
+}
+
+extern "C" int rd_adam_step_clip_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
+                                     size_t partial_bytes, void* clip, const uint8_t* chunk_group, const void* group_cell,
+                                     void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.step = step; RD_GRP(c);
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  return adam_launch<false, true, false, true>(c);
+}
+
+extern "C" int rd_adam_step_clip_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                         float beta2, float eps, const void* state, const void* partial, size_t partial_bytes,
+                                         void* clip, const uint8_t* chunk_group, const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state; RD_GRP(c);
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  return adam_launch<true, true, false, true>(c);
+}
+
+extern "C" int rd_adam_step_ema_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                                    float beta1, float beta2, float eps, float weight_decay, int64_t step, float* ema,
+                                    void* ema_cell, const uint8_t* chunk_group, const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.step = step; RD_GRP(c);
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<false, false, true, true>(c);
+}
+
+extern "C" int rd_adam_step_ema_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float beta1,
+                                        float beta2, float eps, const void* state, float* ema, void* ema_cell,
+                                        const uint8_t* chunk_group, const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state; RD_GRP(c);
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<true, false, true, true>(c);
+}
+
+extern "C" int rd_adam_step_clip_ema_grp(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float lr,
+                                         float beta1, float beta2, float eps, float weight_decay, int64_t step, const void* partial,
+                                         size_t partial_bytes, void* clip, float* ema, void* ema_cell, const uint8_t* chunk_group,
+                                         const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.lr = lr; c.step = step; RD_GRP(c);
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<false, true, true, true>(c);
+}
+
+extern "C" int rd_adam_step_clip_ema_grp_dev(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
+                                             float beta1, float beta2, float eps, const void* state, const void* partial,
+                                             size_t partial_bytes, void* clip, float* ema, void* ema_cell,
+                                             const uint8_t* chunk_group, const void* group_cell, void* stream) {
+  AdamCall c{n, param, grad, exp_avg, exp_avg_sq, beta1, beta2, eps, stream};
+  c.state = state; RD_GRP(c);
+  c.partial = partial; c.partial_bytes = partial_bytes; c.clip = clip;
+  c.ema = ema; c.ema_cell = ema_cell;
+  return adam_launch<true, true, true, true>(c);
+}
+#undef RD_GRP
 
 extern "C" int rd_swap_f32(int64_t n, float* a, float* b, void* stream) {
   RD_REQUIRE(n > 0, "bad n");

@@ -8,6 +8,7 @@ gradients already live in two flat buffers, the whole update is ONE elementwise 
 import contextlib
 import ctypes
 import math
+import re
 
 import torch
 
@@ -26,6 +27,91 @@ def _check_ema_decay(x):
     if isinstance(x, bool) or not isinstance(x, float) or not 0.0 <= x < 1.0:          # NaN fails the comparison
         raise ValueError("ema_decay must be None or a float in [0, 1), got %r" % (x,))
     return x
+
+
+def _check_group_value(what, x):
+    """a finite float >= 0 (a group's lr_scale or weight_decay)"""
+    if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < math.inf:          # NaN fails the comparison
+        raise ValueError("%s must be a finite number >= 0, got %r" % (what, x))
+    return float(x)
+
+
+GROUP_CHUNK = 64         # elements per byte of the chunk map: the alignment dp.FlatGradAllReduce gives every tensor
+GROUP_ROWS = 16          # rows of the group cell (include/raindrop_hip.h rd_adam_step_grp)
+
+
+class ParamGroups:
+    """A partition of a flat layout's tensors into at most 16 groups, each with its own `lr_scale` and `weight_decay`.
+
+    layout: a `dp.FlatGradAllReduce` (anything with `names` and `slices`).  rules: a list of
+    `dict(match=..., lr_scale=1.0, weight_decay=None)`; rule k makes group k + 1, group 0 is every tensor no rule matches.  `match`
+    is a regular expression (`re.search` on the parameter's name), a callable name -> bool, or a list of names;
+    `weight_decay=None`: the optimizer's (it follows later assignments of `opt.weight_decay`).
+    Raises ValueError for a name that matches two rules, a rule that matches nothing, more than `max_groups - 1` rules, a negative or
+    non-finite value, and a slice that does not start on a multiple of 64 (or shares a 64-element chunk with its neighbour).
+    `chunk_map` (host, uint8): the group of elements [64c, 64c + 64); the padding behind a tensor has that tensor's group."""
+
+    def __init__(self, layout, rules, max_groups=GROUP_ROWS):
+        names, slices = list(layout.names), [(int(lo), int(hi)) for lo, hi in layout.slices]
+        if not 1 <= max_groups <= GROUP_ROWS:
+            raise ValueError("max_groups must be in 1..%d, got %r" % (GROUP_ROWS, max_groups))
+        rules = list(rules)
+        if len(rules) > max_groups - 1:
+            raise ValueError("%d rules: at most %d (group 0 is what no rule matches)" % (len(rules), max_groups - 1))
+        if len(names) != len(slices) or len(set(names)) != len(names):
+            raise ValueError("the layout's names must be unique, one per slice")
+        group_of = {}
+        self.names, self.lr_scale, self.weight_decay = [[]], [1.0], [None]
+        for k, rule in enumerate(rules):
+            unknown = set(rule) - {"match", "lr_scale", "weight_decay"}
+            if unknown or "match" not in rule:
+                raise ValueError("rule %d: dict(match=..., lr_scale=1.0, weight_decay=None), got keys %s" % (k, sorted(rule)))
+            match = rule["match"]
+            if isinstance(match, str):
+                hit = [n for n in names if re.search(match, n)]
+            elif callable(match):
+                hit = [n for n in names if match(n)]
+            else:
+                listed = list(match)
+                missing = [n for n in listed if n not in names]
+                if missing:
+                    raise ValueError("rule %d names parameters the layout does not hold: %s" % (k, missing))
+                hit = [n for n in names if n in listed]
+            if not hit:
+                raise ValueError("rule %d (%r) matches no parameter" % (k, match))
+            twice = [n for n in hit if n in group_of]
+            if twice:
+                raise ValueError("rule %d and rule %d both match %s" % (group_of[twice[0]] - 1, k, twice))
+            group_of.update((n, k + 1) for n in hit)
+            wd = rule.get("weight_decay")
+            self.names.append(hit)
+            self.lr_scale.append(_check_group_value("rule %d: lr_scale" % k, rule.get("lr_scale", 1.0)))
+            self.weight_decay.append(None if wd is None else _check_group_value("rule %d: weight_decay" % k, wd))
+        self.names[0] = [n for n in names if n not in group_of]
+        order = sorted(range(len(names)), key=lambda i: slices[i][0])
+        self.n_chunks = max((hi + GROUP_CHUNK - 1) // GROUP_CHUNK for _, hi in slices) if slices else 0
+        self.chunk_map = torch.zeros((self.n_chunks,), dtype=torch.uint8)
+        for name, (lo, hi) in zip(names, slices):
+            if lo % GROUP_CHUNK or lo < 0 or hi < lo:
+                raise ValueError("%s starts at %d: every slice must start on a multiple of %d" % (name, lo, GROUP_CHUNK))
+        for j, i in enumerate(order):
+            lo, hi = slices[i]
+            end = slices[order[j + 1]][0] if j + 1 < len(order) else self.n_chunks * GROUP_CHUNK
+            if end < hi:
+                raise ValueError("%s [%d, %d) overlaps the slice behind it, which starts at %d" % (names[i], lo, hi, end))
+            self.chunk_map[lo // GROUP_CHUNK:end // GROUP_CHUNK] = group_of.get(names[i], 0)
+
+    def __len__(self):
+        return len(self.names)
+
+    def partition(self):
+        """the groups as tuples of names: what has to agree for a state dictionary to be loaded"""
+        return tuple(tuple(g) for g in self.names)
+
+
+def no_decay(layout):
+    """the usual rule: no weight decay for every parameter with ndim <= 1 (biases, LayerNorm weights) of a `dp.FlatGradAllReduce`"""
+    return dict(match=[n for n, p in zip(layout.names, layout.params) if p.dim() <= 1], weight_decay=0.0)
 
 
 class FlatAdam:
@@ -58,12 +144,28 @@ class FlatAdam:
     `swap_ema()` exchanges parameters and average IN PLACE (rd_swap_f32): whatever holds the parameters' addresses -- a captured
     `EvalStep`, `feed.validate`, the eager forward -- then evaluates the average; `ema_weights()` is the context manager around two
     swaps.  While swapped, `step()` / `step_captured()` (and the whole-step replays) raise instead of training the average.
-    The average covers the flat parameters, which is everything: the model has no buffers (no batch-norm statistics)."""
+    The average covers the flat parameters, which is everything: the model has no buffers (no batch-norm statistics).
+
+    groups, decoupled (default None, False: off -- the launches, the code path, `hyper()` and the `state_dict()` keys of an optimizer
+    built without the keywords): `groups` is a `ParamGroups` over the layout the flat buffers come from; every group has its own
+    learning rate `lr * lr_scale` and its own weight decay (None: the optimizer's `weight_decay`), applied by the update's own launch
+    (the _grp twins rd_adam_step[_clip][_ema]_grp[_dev]: one byte per 64 elements names the group, a 16-row device cell holds the
+    scalars), so they exist in `step()`, `step_captured()` and a whole-step hipGraph alike and combine with `max_grad_norm` and
+    `ema_decay`.  `decoupled=True` is torch.optim.AdamW: p *= 1 - lr * weight_decay in front of the Adam step instead of
+    weight_decay * p added to the gradient; without `groups` it runs the grouped forms with one group.  The clipping norm stays the
+    GLOBAL norm over all groups, the step count and the average are shared.  `set_group(i, lr_scale=, weight_decay=)` is a copy of
+    one 32-byte row, stream-ordered with the launches around it and not a new capture (lr_scale=0.0 holds a group still: its
+    parameters keep their bits, its moments go on); assigning `weight_decay` re-resolves the rows of the groups that follow it at
+    the next `sync_cells`.  Switching the feature on or off is a new capture / another optimizer."""
 
     def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
-                 ema_warmup=False):
+                 ema_warmup=False, groups=None, decoupled=False):
         if flat_param.grad is None:
             raise ValueError("flat_param.grad must be the flat gradient buffer")
+        if groups is not None and not isinstance(groups, ParamGroups):
+            raise ValueError("groups must be None or an optim.ParamGroups, got %r" % (groups,))
+        self.groups, self.decoupled = groups, bool(decoupled)
+        self.chunk_group = self.group_cell = None
         self.max_grad_norm = None if max_grad_norm is None else _check_max_grad_norm(max_grad_norm)
         self.clip_cell = self.clip_partial = None
         self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay)
@@ -81,6 +183,8 @@ class FlatAdam:
             self._make_clip_buffers()
         if self.ema_decay is not None:
             self._make_ema_buffers()
+        if self.groups is not None or self.decoupled:
+            self._make_group_buffers()
 
     def hyper(self):
         """the values a captured launch holds as CONSTANTS (TrainStep.run_full captures again when they change): betas and eps, and
@@ -89,7 +193,9 @@ class FlatAdam:
         h = (float(self.betas[0]), float(self.betas[1]), float(self.eps))
         if self.max_grad_norm is not None:
             h = h + ("clip",)
-        return h if self.ema_decay is None else h + ("ema",)             # the EMA twin of the update is another launch
+        if self.ema_decay is not None:                                   # the EMA twin of the update is another launch
+            h = h + ("ema",)
+        return h if self.chunk_group is None else h + ("grp",)           # and so is the grouped twin
 
     def cell_hyper(self):
         return (float(self.lr), float(self.weight_decay))
@@ -129,6 +235,77 @@ class FlatAdam:
             raise ValueError("clipping is off: construct FlatAdam with max_grad_norm")
         c = self.clip_cell.cpu().tolist()
         return dict(norm=c[1], scale=c[2], skipped=int(c[3]), clipped=int(c[4]))
+
+    # ---- parameter groups / decoupled weight decay (groups, decoupled) ----
+    def _make_group_buffers(self):
+        """the chunk map (one byte per 64 elements) and the group cell, 16 rows {lr_scale, wd_coupled, wd_decoupled, 0}
+        (include/raindrop_hip.h rd_adam_step_grp); made outside any capture (the constructor)"""
+        n_chunks = (self.param.numel() + GROUP_CHUNK - 1) // GROUP_CHUNK
+        if self.groups is None:              # decoupled alone: one group, everything follows the optimizer
+            cmap, self._group_lr_scale, self._group_wd = torch.zeros((n_chunks,), dtype=torch.uint8), [1.0], [None]
+        else:
+            cmap, self._group_lr_scale, self._group_wd = self.groups.chunk_map, list(self.groups.lr_scale), list(self.groups.weight_decay)
+            if cmap.numel() != n_chunks:
+                raise ValueError("groups cover %d chunks of %d elements, the flat buffer has %d: another layout?"
+                                 % (cmap.numel(), GROUP_CHUNK, n_chunks))
+        dev = self.param.device
+        self.chunk_group = cmap.to(dev)
+        self.group_cell = torch.tensor(self._group_rows(), dtype=torch.float64).to(dev)
+        self._cell_group_wd = self.weight_decay
+
+    def _group_row(self, i):
+        wd = self.weight_decay if self._group_wd[i] is None else self._group_wd[i]
+        wd = _check_group_value("weight_decay", wd)
+        return [self._group_lr_scale[i], 0.0, wd, 0.0] if self.decoupled else [self._group_lr_scale[i], wd, 0.0, 0.0]
+
+    def _group_rows(self):
+        """all 16 rows; the rows behind the last group stay zero (no map the host builds names them)"""
+        k = len(self._group_wd)
+        return [self._group_row(i) for i in range(k)] + [[0.0] * 4] * (GROUP_ROWS - k)
+
+    def _groups_on(self):
+        if self.group_cell is None:
+            raise ValueError("parameter groups are off: construct FlatAdam with groups or decoupled=True (the step's launches differ)")
+
+    def _group_args(self):
+        self.sync_group_cell()
+        return (ops._ptr(self.chunk_group), ops._ptr(self.group_cell))
+
+    def _write_group_row(self, i):
+        self.group_cell[i] = torch.tensor(self._group_row(i), dtype=torch.float64, device=self.group_cell.device)
+
+    def set_group(self, i, lr_scale=None, weight_decay=None):
+        """New scalars for group i, for the steps enqueued from here on, captured ones included: one 32-byte copy into the group
+        cell, stream-ordered with the launches around it.  None leaves a value as it is; a `weight_decay` given here stops
+        following the optimizer's."""
+        self._groups_on()
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(self._group_wd):
+            raise ValueError("group %r: the optimizer has groups 0..%d" % (i, len(self._group_wd) - 1))
+        if lr_scale is not None:
+            lr_scale = _check_group_value("lr_scale", lr_scale)
+        if weight_decay is not None:
+            weight_decay = _check_group_value("weight_decay", weight_decay)
+        self.sync_group_cell()
+        if lr_scale is not None:
+            self._group_lr_scale[i] = lr_scale
+        if weight_decay is not None:
+            self._group_wd[i] = weight_decay
+        self._write_group_row(i)
+
+    def sync_group_cell(self):
+        """push a changed `weight_decay` into the rows of the groups that follow it (part of sync_cells)"""
+        if self.group_cell is not None and self._cell_group_wd != self.weight_decay:
+            for i, wd in enumerate(self._group_wd):
+                if wd is None:
+                    self._write_group_row(i)
+            self._cell_group_wd = self.weight_decay
+
+    def group_info(self):
+        """per group: dict(names, lr_scale, weight_decay) with the decay resolved (a group that follows the optimizer's shows it)"""
+        self._groups_on()
+        names = self.groups.names if self.groups is not None else [None]
+        return [dict(names=None if names[i] is None else list(names[i]), lr_scale=self._group_lr_scale[i],
+                     weight_decay=float(self.weight_decay if wd is None else wd)) for i, wd in enumerate(self._group_wd)]
 
     # ---- exponential moving average of the weights (ema_decay) ----
     def _make_ema_buffers(self, updates=0):
@@ -200,22 +377,22 @@ class FlatAdam:
             self.swap_ema()
 
     def _enqueue_update(self, dev):
-        """The update's launches -- the ONE place that names the eight entry points: rd_adam_step [_clip] [_ema] [_dev], behind
+        """The update's launches -- the ONE place that names the sixteen entry points: rd_adam_step [_clip] [_ema] [_grp] [_dev], behind
         rd_grad_sumsq when clipping is on.  dev: the step state is read from the device cell, else `lr`, `weight_decay` and `t` of
         this step travel as arguments.  The cells of what is on are synchronised on the way (the average's, then the threshold's)."""
-        clip, ema = self.max_grad_norm is not None, self.ema_decay is not None
+        clip, ema, grp = self.max_grad_norm is not None, self.ema_decay is not None, self.chunk_group is not None
         p, g = self.param.data, self.param.grad
         args = (p.numel(), ops._ptr(p), ops._ptr(g), ops._ptr(self.exp_avg), ops._ptr(self.exp_avg_sq))
         if dev:
             args += (float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell))
         else:
             args += (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
-        tail = self._ema_args() if ema else ()
+        tail = (self._ema_args() if ema else ()) + (self._group_args() if grp else ())
         if clip:                             # the norm's partial sums, then the clipping instantiation of the update
             partial, nbytes, cell = self._clip_args()
             _lib.call("rd_grad_sumsq", p.numel(), ops._ptr(g), partial, nbytes, ops._stream())
             args += (partial, nbytes, cell)
-        _lib.call("rd_adam_step" + "_clip" * clip + "_ema" * ema + "_dev" * dev, *args, *tail, ops._stream())
+        _lib.call("rd_adam_step" + "_clip" * clip + "_ema" * ema + "_grp" * grp + "_dev" * dev, *args, *tail, ops._stream())
 
     def step(self):
         self.check_can_step("FlatAdam.step")
@@ -251,6 +428,7 @@ class FlatAdam:
             self.sync_cell_hyper()
         self.sync_clip_cell()
         self.sync_ema_cell()
+        self.sync_group_cell()
 
     def register_cell(self, on=True):
         """(Un)register the device step state with this host thread's next rd_step_begin launches (include/raindrop_hip.h
@@ -303,13 +481,28 @@ class FlatAdam:
             if self.ema_swapped:
                 raise _lib.RaindropHipError("FlatAdam.state_dict: the parameters are exchanged with their average: swap back first")
             sd.update(ema=self.ema, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=self.ema_updates())
+        if self.group_cell is not None:      # (off: the keys of an optimizer without the keywords)
+            names = self.groups.names if self.groups is not None else [None]
+            sd.update(decoupled=self.decoupled,
+                      groups=[dict(names=None if names[i] is None else list(names[i]), lr_scale=self._group_lr_scale[i], weight_decay=wd)
+                              for i, wd in enumerate(self._group_wd)])
         return sd
 
     def load_state_dict(self, sd):
         """In place (the moment buffers and `ema` keep their addresses: a captured step stays valid); the device step state follows
-        at the next captured step.  A dictionary without the `ema` keys leaves the average and its settings as they are."""
+        at the next captured step.  A dictionary without the `ema` keys leaves the average and its settings as they are; so does
+        one without `groups` / `decoupled`.  One whose groups partition the parameters differently than this optimizer's (which
+        includes one with groups into an optimizer without) raises before anything is changed: the chunk map is part of a capture."""
         if self.ema_swapped:
             raise _lib.RaindropHipError("FlatAdam.load_state_dict: the parameters are exchanged with their average: swap back first")
+        if "groups" in sd:
+            mine = None if self.group_cell is None else (self.groups.partition() if self.groups is not None else (None,))
+            theirs = tuple(None if g["names"] is None else tuple(g["names"]) for g in sd["groups"])
+            if mine != theirs:
+                raise ValueError("FlatAdam.load_state_dict: the dictionary's parameter groups are another partition than this "
+                                 "optimizer's: construct FlatAdam with the same groups")
+            values = [(_check_group_value("lr_scale", g["lr_scale"]),
+                       None if g["weight_decay"] is None else _check_group_value("weight_decay", g["weight_decay"])) for g in sd["groups"]]
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.t = int(sd["t"])
@@ -333,3 +526,8 @@ class FlatAdam:
                 self.ema_cell.copy_(torch.tensor([self.ema_decay, float(self.ema_warmup), k, k] + [0.0] * 4, dtype=torch.float64))
                 self._cell_ema_decay, self._ema_t = self.ema_decay, self.t
             self.ema.copy_(sd["ema"])
+        if "groups" in sd:                   # in place: the cell keeps its address
+            self._group_lr_scale, self._group_wd = [v[0] for v in values], [v[1] for v in values]
+            self.decoupled = bool(sd.get("decoupled", self.decoupled))
+            self.group_cell.copy_(torch.tensor(self._group_rows(), dtype=torch.float64))
+            self._cell_group_wd = self.weight_decay

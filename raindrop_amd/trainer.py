@@ -3,8 +3,9 @@
 `fit` puts together what the library has: `feed.EpochPlanner` (the script's batch plan, same numpy calls), `feed.EpochFeed` (the
 plan on the device), `TrainStep` / `BetaTrainStep` with the feed attached, `FlatAdam` inside `capture_full`, `feed.validate` and a
 plateau scheduler.  An epoch is one upload of the plan, `n_batches` replays of ONE hipGraph and one read-back of the per-batch
-losses and hit counts; validation is the captured evaluation pass.  `ReduceOnPlateau` restates torch's scheduler on the host,
-because `FlatAdam` has no `param_groups` for torch's to act on.
+losses and hit counts; validation is the captured evaluation pass.  `ReduceOnPlateau` restates torch's scheduler on the host:
+`FlatAdam` keeps ONE base rate, `opt.lr`, which its parameter groups (`optim.ParamGroups`) scale on the device, not a list of
+torch `param_groups` for torch's scheduler to act on.
 """
 import math
 
@@ -12,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, dp, feed as feed_mod
+from . import optim as optim_mod
 from .optim import FlatAdam
 
 VAL_FIELDS = ("auroc", "auprc", "loss", "accuracy", "precision", "recall", "f1")
@@ -59,8 +61,24 @@ class ReduceOnPlateau:
         return float(self.opt.lr)
 
 
-def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy):
+def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False):
     """what can be refused without a device"""
+    if not isinstance(decoupled_weight_decay, bool):
+        raise ValueError("decoupled_weight_decay must be True or False, got %r" % (decoupled_weight_decay,))
+    if isinstance(param_groups, str):
+        if param_groups != "no_decay":
+            raise ValueError("param_groups: the only named recipe is 'no_decay', got %r" % (param_groups,))
+    elif param_groups is not None:
+        if not isinstance(param_groups, (list, tuple)) or not all(isinstance(r, dict) for r in param_groups):
+            raise ValueError("param_groups must be None, 'no_decay' or a list of dict(match=..., lr_scale=1.0, weight_decay=None)")
+        if len(param_groups) > optim_mod.GROUP_ROWS - 1:
+            raise ValueError("param_groups: %d rules, at most %d" % (len(param_groups), optim_mod.GROUP_ROWS - 1))
+        for k, r in enumerate(param_groups):
+            if "match" not in r or set(r) - {"match", "lr_scale", "weight_decay"}:
+                raise ValueError("param_groups[%d]: dict(match=..., lr_scale=1.0, weight_decay=None), got keys %s" % (k, sorted(r)))
+            optim_mod._check_group_value("param_groups[%d]: lr_scale" % k, r.get("lr_scale", 1.0))
+            if r.get("weight_decay") is not None:
+                optim_mod._check_group_value("param_groups[%d]: weight_decay" % k, r["weight_decay"])
     if strategy not in (1, 2, 3):
         raise ValueError("strategy must be 1, 2 or 3, got %r" % (strategy,))
     if int(batch_size) != batch_size or batch_size <= 0:
@@ -81,7 +99,8 @@ def _live_names(model):
 
 
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
-        class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True):
+        class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
+        param_groups=None, decoupled_weight_decay=False):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -89,7 +108,10 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
       `np.random.seed` before the call (or `seed=`, which also seeds the step's dropout stream) reproduces its batches;
     * the step: `TrainStep` (`BetaTrainStep` for a `use_beta` model, with `distance_weight`) on one `feed.EpochFeed`, `FlatAdam(lr,
       weight_decay, max_grad_norm, ema_decay)` inside `capture_full`; `class_weight` / `label_smoothing` set the criterion of the
-      step and of the validation loss.  The model is put into training mode to build the step (that is when dropout is read) and
+      step and of the validation loss.  `param_groups` -- a list of `optim.ParamGroups` rules, `dict(match=..., lr_scale=1.0,
+      weight_decay=None)`, or "no_decay" (`optim.no_decay`: biases and LayerNorm parameters without weight decay) -- and
+      `decoupled_weight_decay` (AdamW) become the optimizer's `groups` / `decoupled`, built on the flat layout made here; the
+      scheduler still moves the one base rate every group scales.  The model is put into training mode to build the step (that is when dropout is read) and
       gets its previous mode back at the end; evaluation runs with dropout off whatever the mode;
     * per epoch: `load_epoch`, `n_batches` x `run_full`, `feed.history()`; then `feed.validate(model, val_ds, transform=...)` (on the
       averaged weights, `validate_ema`, when `ema_decay` is set), the scheduler's step on `auprc` (:368) and, when `auroc` beats the
@@ -103,7 +125,7 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
 
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
-    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy)
+    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -116,7 +138,11 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     model.train()
     named = dict(model.named_parameters())
     flat = dp.FlatGradAllReduce([(n, named[n]) for n in _live_names(model)], n_buckets=2)
-    opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay)
+    groups = None
+    if param_groups is not None:
+        groups = optim_mod.ParamGroups(flat, [optim_mod.no_decay(flat)] if param_groups == "no_decay" else param_groups)
+    opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
+                   groups=groups, decoupled=decoupled_weight_decay)
     planner = feed_mod.EpochPlanner(train_ds.y.cpu().numpy(), batch_size=B, strategy=strategy, n_total=train_ds.N)
     fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1))
     P, Pstatic, Ptime, y, lengths = train_ds.batch(np.arange(B) % train_ds.N)          # valid contents for the step's checks
