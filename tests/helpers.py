@@ -100,3 +100,16 @@ def build_ours(cfg, gs, device, param_seed, param_scale=1.0, **extra):
     synth.fill_params_(m, seed=param_seed, scale=param_scale)
     zero_dropout(m)
     return m.to(device)
+
+
+def plan_ref(lengths, T):
+    """numpy statement of rd_plan.h: stable descending sort by clamped length."""
+    L = np.clip(np.asarray(lengths, dtype=np.int64), 0, T)
+    B = len(L)
+    order = np.array(sorted(range(B), key=lambda b: (-L[b], b)), dtype=np.int64)
+    rank = np.empty(B, dtype=np.int64); rank[order] = np.arange(B)
+    lenr = L[order]
+    off = np.concatenate([[0], np.cumsum(lenr)])
+    cnt = np.array([(L > t).sum() for t in range(T + 1)])
+    coff = np.concatenate([[0], np.cumsum((lenr + 15) // 16)])          # 16-row groups of the per-sample group space
+    return dict(off=off, rank=rank, order=order, lenr=lenr, cnt=cnt, coff=coff, mlive=int(off[-1]))

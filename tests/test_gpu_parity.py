@@ -696,7 +696,7 @@ def test_encoder_layer_dropout_is_consistent():
 
 
 def test_dropout_keep_fraction():
-    """The Philox masks keep ~ (1-p) of the elements and rescale by 1/(1-p) (observation-embedding site)."""
+    """The Threefry masks (rd_rng.h) keep ~ (1-p) of the elements and rescale by 1/(1-p) (observation-embedding site)."""
     from raindrop_amd import _lib, ops
     cfg = synth.make_config("P19")
     B, T, F, d = 16, 60, 34, 4

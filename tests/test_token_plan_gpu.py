@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from raindrop_amd import _lib, dp, synth
-from tests.helpers import build_ours
+from tests.helpers import build_ours, plan_ref as _plan_ref
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -17,19 +17,6 @@ DEV = "cuda"
 
 def _rel(a, b):
     return float(np.abs(a - b).max() / (np.abs(b).max() + 1e-30))
-
-
-def _plan_ref(lengths, T):
-    """numpy statement of rd_plan.h: stable descending sort by clamped length."""
-    L = np.clip(np.asarray(lengths, dtype=np.int64), 0, T)
-    B = len(L)
-    order = np.array(sorted(range(B), key=lambda b: (-L[b], b)), dtype=np.int64)
-    rank = np.empty(B, dtype=np.int64); rank[order] = np.arange(B)
-    lenr = L[order]
-    off = np.concatenate([[0], np.cumsum(lenr)])
-    cnt = np.array([(L > t).sum() for t in range(T + 1)])
-    coff = np.concatenate([[0], np.cumsum((lenr + 15) // 16)])          # 16-row groups of the per-sample group space
-    return dict(off=off, rank=rank, order=order, lenr=lenr, cnt=cnt, coff=coff, mlive=int(off[-1]))
 
 
 @pytest.mark.parametrize("B,T,seed", [(256, 60, 0), (1, 60, 1), (37, 60, 2), (5, 16, 3), (1000, 60, 4)])
