@@ -126,7 +126,11 @@ int rd_drop_trailing(void);
  * chains (ceil(D / 32) == 5, ceil(nhid / 32) == 9: P19 and P12), head_dim <= 96, the fused head -- at any T (T <= 64: in_proj + attention
  * as one launch per direction, rd_attnfuse.hip; beyond: the multi-tile attention kernels on plan rows) and with either message-passing
  * form (fused LDS-resident, or the panel products whose last scatter follows the plan; rd_pe_mask writes the PE rows the same way).
- * Other shapes / modes return RD_EUNSUPPORTED while a plan is registered (raindrop_amd.step.plan_supported is the host-side test).
+ * The row-block path also needs ceil(3 D / 32) == 15 (in_proj's input gradient), so the encoder widths a plan runs at are D = 152 .. 160:
+ * D = 136 / 144, which the fused attention launch alone would take, are refused.  A length of 0 is legal: such a sample owns no row and
+ * contributes to no gradient (tests/test_plan_layer_gpu.py holds both).
+ * Other shapes / modes are refused while a plan is registered -- rd_encoder_layer_fwd / _bwd / _fwd_infer with RD_EINVAL ("token plan:
+ * ...") before any launch, kernels further down with RD_EUNSUPPORTED (raindrop_amd.step.plan_supported is the host-side test).
  * plan_out: rd_token_plan_bytes(s) bytes of int32 (layout: raindrop_amd/csrc/rd_plan.h; [0] = live rows, [1] = their 32-row chunks,
  * [5] = chunks of the per-sample chunk space the fused attention exports its weight-gradient row tiles in; per-rank off / len,
  * per-sample rank / first row / length).  If seed_cell is not NULL the launch also adds `delta` to it (rd_seed_cell_advance folded

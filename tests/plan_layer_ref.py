@@ -1,0 +1,220 @@
+"""TEST INFRASTRUCTURE ONLY -- one encoder layer on a registered token plan: case table, inputs and float64 reference.
+
+Used by tests/test_plan_layer_host.py (conditions on the reference alone, no GPU) and tests/test_plan_layer_gpu.py (the fused
+in_proj + attention launches of rd_attnfuse.hip, the lean k_enc_post_fwd / k_enc_pre_bwd chains and the weight-gradient stream fed
+from the plan's per-sample group space against this reference).
+
+Layout.  A case's x and dy are [M_live, D] in PLAN order (tests/helpers.plan_ref: sample b's step t at row off[rank[b]] + t), which
+is what the entry points read; `to_padded` spreads them over [T, B, D] (zeros at padded steps) and `to_plan` gathers back.  The
+reference is oracle/restatement.py encoder_layer in float64 on the PADDED layout of the samples of non-zero length, with the padded
+rows' dy zeroed; y and dx are compared on live rows, in plan order, next to all 12 parameter gradients.  A zero-length sample owns no
+row and appears nowhere in the reference.
+
+Decisive ReLU gates.  linear1.bias is replaced by c * s_j, s_j = +1, -1, +1, ... over the hidden units, c the smallest of 2, 4, 8, ...
+for which every FFN pre-activation of the float64 reference (every live row; with and without the dropout masks where the case runs
+with dropout) has |pre| >= GATE_MARGIN: half the units always open, half always shut, so no gate can open on one side of a
+split-bf16 comparison only and every gradient is continuous in the inputs -- the whole layer can be held to the bound of the
+gate-free sub-graph.
+
+Bounds (bound_of below): y 5e-5 x 6 absolute (test_encoder_layer_vs_oracle, test_row_block_layer_vs_float64), every gradient 2e-4 of
+its max-norm (test_attention_core_vs_float64), raised per tensor to 2 x the YARDSTICK's measured error where that exceeds 1e-4.  The
+yardstick is the same inputs on the padded layout with RD_ENC_FUSE=0 and RD_ATTN_FUSE=0: the row-block and attention kernels that
+test_row_block_layer_vs_float64 and test_encoder_layer_vs_oracle already tie to float64.  No bound is taken from the plan path."""
+import functools
+
+import numpy as np
+import torch
+
+from oracle import restatement as O2
+from raindrop_amd import synth
+from tests import dropout_ref as DR
+from tests.helpers import plan_ref
+
+NHEAD, LAYER = 2, 0
+P_DROP, SEED = 0.2, 77
+GATE_MARGIN = 0.05
+ENC_NAMES = DR.ENC_NAMES
+GRAD_NAMES = ("x",) + ENC_NAMES
+W_IN = "self_attn.in_proj_weight"
+
+# name -> (F, D, nhid, environment switch or None); D = 4 F + 16, head_dim D / 2 = 76, 80, 68, 72.
+# attnfuse_ok() (rd_attnfuse.hip) admits all four widths, but a layer reaches the fused launches only on the row-block + tile-stream
+# path (rd_temporal.hip tile_path), whose in_proj input-gradient product needs ceil(3 D / 32) == 15 reduction chunks (rd_rowgemm.hip
+# rowgemm_ok): D = 152 .. 160.  With a plan registered, D = 136 (13 chunks) and D = 144 (14) are REFUSED with RD_EINVAL before any
+# launch, under RD_ENC_SPECIALIZE=0 too -- no kernel of this path can run at those widths.  PLAN_WIDTHS are the widths that run;
+# REFUSED_WIDTHS are pinned as refusals (tests/test_plan_layer_gpu.py test_widths_outside_the_row_block_envelope_are_refused).
+WIDTHS = {"W152": (34, 152, 272, None), "W160": (36, 160, 288, None),
+          "W136": (30, 136, 260, "RD_ENC_SPECIALIZE=0"), "W144": (32, 144, 288, "RD_ENC_SPECIALIZE=0")}
+PLAN_WIDTHS, REFUSED_WIDTHS = ("W152", "W160"), ("W136", "W144")
+
+
+def in_proj_chunks(width):
+    """32-column reduction chunks of dx = dqkv W_in (K = 3 D): the row-block kernels exist for 5, 9 and 15"""
+    return -(-3 * WIDTHS[width][1] // 32)
+
+
+# name -> (T, lengths in the caller's sample order: unsorted, with ties)
+_G64 = (16, 64, 1, 49, 64, 48, 33, 2, 47, 32, 17, 31, 15)
+LENGTHS = {"G64": (64, _G64),                                       # every 16-row group edge, T = 64 twice; 31 groups (odd)
+           "G64e": (64, tuple(l for l in _G64 if l != 2)),          # 30 groups (even): no unowned half chunk
+           "P60": (60, (60, 1, 60, 37, 16)),
+           "S7": (7, (3, 7, 1)),                                    # 11 live rows: less than one 32-row chunk
+           "ONE64": (64, (64,)), "ONE1": (64, (1,)),
+           "Z33": (33, (33, 0, 20, 0))}                             # zero-length samples own no rows
+ALL_SETS = ("G64", "G64e", "P60", "S7", "ONE64", "ONE1", "Z33")
+TIE_CASES = [(w, s) for w in PLAN_WIDTHS for s in ALL_SETS]
+REFUSED_CASES = [(w, s) for w in REFUSED_WIDTHS for s in ("G64", "S7")]
+DROPOUT_CASES = [(w, s) for w in PLAN_WIDTHS for s in ("P60", "G64")]
+VARIANTS = ("key17", "vswap", "swap1615")
+
+# Bounds of the float64 tie.  Measured on the MI355X, maximum over the length sets of a width, yardstick / plan path (y: max absolute
+# error; gradients: max error over the tensor's max-norm; tests/test_plan_layer_gpu.py prints every figure with -s and
+# test_yardstick_meets_the_bounds re-measures the yardstick):
+#                                 W152, p = 0            W160, p = 0            W152, p = 0.2          W160, p = 0.2
+#   y                             1.71e-05 / 1.73e-05    1.82e-05 / 1.81e-05    2.06e-05 / 2.04e-05    1.93e-05 / 2.42e-05
+#   dx                            2.52e-06 / 2.40e-06    2.72e-06 / 2.73e-06    2.41e-06 / 2.29e-06    2.93e-06 / 2.79e-06
+#   in_proj_weight                9.61e-06 / 9.57e-06    1.29e-05 / 1.29e-05    8.03e-06 / 9.19e-06    9.38e-06 / 7.53e-06
+#   in_proj_bias                  8.79e-06 / 9.51e-06    6.85e-06 / 6.68e-06    6.39e-06 / 6.31e-06    6.72e-06 / 5.51e-06
+#   out_proj.weight               1.03e-05 / 1.05e-05    1.18e-05 / 1.18e-05    6.69e-06 / 7.33e-06    1.30e-05 / 9.96e-06
+#   worst other gradient          1.36e-05 / 1.36e-05    1.11e-05 / 1.11e-05    7.32e-06 / 6.76e-06    7.12e-06 / 6.37e-06
+#     (p = 0: linear2.weight at the one-row case ONE1; p = 0.2: linear1.weight; the dropout yardstick runs under its own padded-row
+#     masks against its own masked reference)
+# No yardstick error comes near 1e-4 -- with decisive gates the whole layer meets the bound of the gate-free attention core -- so no
+# bound is raised: RAISED is empty and every gradient is held to the project's 2e-4.
+Y_ABS = 5e-5 * 6.0
+GRAD_REL = 2e-4
+RAISED = {}                                                          # tensor -> bound above GRAD_REL (2 x the yardstick's error)
+
+
+def bound_of(name):
+    """(metric, bound) of a compared tensor, in the form tests/dropout_ref.variant_margin takes"""
+    return ("abs", Y_ABS) if name == "y" else ("rel", RAISED.get(name, GRAD_REL))
+
+
+def _shapes(D, nhid):
+    return {"self_attn.in_proj_weight": (3 * D, D), "self_attn.in_proj_bias": (3 * D,), "self_attn.out_proj.weight": (D, D),
+            "self_attn.out_proj.bias": (D,), "linear1.weight": (nhid, D), "linear1.bias": (nhid,), "linear2.weight": (D, nhid),
+            "linear2.bias": (D,), "norm1.weight": (D,), "norm1.bias": (D,), "norm2.weight": (D,), "norm2.bias": (D,)}
+
+
+def starts_of(pl):
+    """first plan row of every SAMPLE (caller's order)"""
+    return pl["off"][pl["rank"]]
+
+
+def to_padded(rows, starts, lengths, T):
+    """[M_live, D] plan order -> [T, B, D] with zeros at padded steps"""
+    out = np.zeros((T, len(lengths), rows.shape[1]), dtype=rows.dtype)
+    for b, (s, n) in enumerate(zip(starts, lengths)):
+        out[:n, b] = rows[s:s + n]
+    return out
+
+
+def to_plan(padded, starts, lengths, mlive):
+    """[T, B, D] -> [M_live, D] plan order (live steps only)"""
+    out = np.zeros((mlive, padded.shape[2]), dtype=padded.dtype)
+    for b, (s, n) in enumerate(zip(starts, lengths)):
+        out[s:s + n] = padded[:n, b]
+    return out
+
+
+def _masks(c, starts, layout):
+    """the four keep-scale tensors of the layer: numbered by plan rows and ranks, or by the padded layout's rows and samples"""
+    T, B, L = c["T"], c["B"], c["lengths"]
+    if layout == "padded":
+        mk = DR.Masks(SEED, P_DROP, T, B)
+    else:
+        live = np.arange(T)[:, None] < L[None, :]
+        mk = DR.Masks(SEED, P_DROP, T, B, rows=starts[None, :] + np.arange(T, dtype=np.int64)[:, None], bh_rank=c["plan"]["rank"],
+                      live=live)
+    return mk.encoder(LAYER, NHEAD, c["D"], c["nhid"])
+
+
+def _evaluate(c, bias1, p_drop=0.0, variant=None, layout="plan", grads=True):
+    """The float64 layer on the padded layout of the samples of non-zero length -> dict in plan order: y, x (= dx), the 12 parameter
+    gradients, pre (FFN pre-activations of the live rows)."""
+    T, D, nhid, L, pl = c["T"], c["D"], c["nhid"], c["lengths"], c["plan"]
+    starts = starts_of(pl).copy()
+    if variant == "swap1615":                  # the 31 rows of the adjacent ranks (16, 15) read as (15 rows, 16 rows)
+        b16, b15 = int(np.nonzero(L == 16)[0][0]), int(np.nonzero(L == 15)[0][0])
+        assert starts[b15] == starts[b16] + 16
+        starts[b15], starts[b16] = starts[b16], starts[b16] + 15
+    keep = np.nonzero(L > 0)[0]
+    assert p_drop == 0.0 or len(keep) == len(L)
+    x = torch.from_numpy(to_padded(c["x"], starts, L, T)[:, keep]).double().requires_grad_(grads)
+    dy = torch.from_numpy(to_padded(c["dy"], starts, L, T)[:, keep]).double()
+    mask = O2.padding_mask(L[keep], T)
+    if variant == "key17":                     # the last live key of the length-17 sample masked
+        mask[int(np.nonzero(L[keep] == 17)[0][0]), 16] = True
+    p = {n: t.double() for n, t in c["p"].items()}
+    p["linear1.bias"] = bias1.double()
+    p = {n: t.requires_grad_(grads) for n, t in p.items()}
+    pe = {("L." + n): t for n, t in p.items()}
+    if variant == "vswap":                     # the two heads' V blocks exchanged
+        hd = D // NHEAD
+        perm = torch.cat([torch.arange(2 * D), torch.arange(2 * D + hd, 3 * D), torch.arange(2 * D, 2 * D + hd)])
+        pe["L." + W_IN] = p[W_IN][perm]
+        pe["L.self_attn.in_proj_bias"] = p["self_attn.in_proj_bias"][perm]
+    hook = DR.DropHook(_masks(c, starts, layout)) if p_drop > 0.0 else None
+    gates = {}
+    with torch.set_grad_enabled(grads):
+        y = O2.encoder_layer(x, torch.from_numpy(mask), pe, "L.", NHEAD, drop=hook, gates=gates)
+    assert hook is None or hook.i == 4
+    Lk, sk, ml = L[keep], starts[keep], pl["mlive"]
+    res = dict(pre=to_plan(gates["L.linear1"].numpy(), sk, Lk, ml))
+    if grads:
+        g = torch.autograd.grad(y, [x] + [p[n] for n in ENC_NAMES], dy)
+        res["y"] = to_plan(y.detach().numpy(), sk, Lk, ml)
+        res["x"] = to_plan(g[0].numpy(), sk, Lk, ml)
+        res.update((n, t.numpy()) for n, t in zip(ENC_NAMES, g[1:]))
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def case(width, lset):
+    """Inputs of one (width, length set): x, dy [M_live, D] fp32 in plan order, the parameters (linear1.bias = c s_j), the plan."""
+    F, D, nhid, env = WIDTHS[width]
+    T, lengths = LENGTHS[lset]
+    assert D == 4 * F + 16
+    L = np.asarray(lengths, dtype=np.int64)
+    pl = plan_ref(L, T)
+    rng = np.random.default_rng([D, T, len(L), int(L.sum())])
+    x = rng.standard_normal((pl["mlive"], D)).astype(np.float32)
+    dy = rng.standard_normal((pl["mlive"], D)).astype(np.float32)
+    shapes = _shapes(D, nhid)
+    p = {n: synth.param_values("L." + n, shapes[n], seed=D) for n in ENC_NAMES}
+    c = dict(width=width, lset=lset, F=F, D=D, nhid=nhid, env=env, T=T, B=len(L), lengths=L, plan=pl, x=x, dy=dy, p=p)
+    sign = torch.from_numpy(np.where(np.arange(nhid) % 2 == 0, 1.0, -1.0).astype(np.float32))
+    drops = (0.0, P_DROP) if (width, lset) in DROPOUT_CASES else (0.0,)
+    scale = 2.0
+    while True:                                # the smallest c of 2, 4, 8, ... that puts every gate GATE_MARGIN away from zero
+        pres = [_evaluate(c, sign * scale, pd, grads=False)["pre"] for pd in drops]
+        if len(drops) == 2:
+            pres.append(_evaluate(c, sign * scale, P_DROP, layout="padded", grads=False)["pre"])       # the yardstick's own masks
+        if min(float(np.abs(q).min()) for q in pres) >= GATE_MARGIN:
+            break
+        scale *= 2.0
+        assert scale <= 64.0
+    c["c"] = scale
+    c["p"] = dict(p)
+    c["p"]["linear1.bias"] = sign * scale
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def reference(width, lset, p_drop=0.0, variant=None, layout="plan"):
+    """{y, x, 12 gradients, pre} in plan order, float64.  layout "padded": the dropout masks numbered as the padded layout numbers
+    them (the yardstick's reference); without dropout both layouts have the same reference."""
+    c = case(width, lset)
+    return _evaluate(c, c["p"]["linear1.bias"], p_drop, variant, layout)
+
+
+def compared(ref):
+    """the tensors the device comparison holds to bounds (everything but the gate pre-activations)"""
+    return {k: v for k, v in ref.items() if k != "pre"}
+
+
+def groups(lset):
+    """16-row groups of the per-sample group space (rd_plan.h coff[B])"""
+    T, lengths = LENGTHS[lset]
+    return int(plan_ref(lengths, T)["coff"][-1])
