@@ -1,6 +1,6 @@
 /*
  * raindrop_hip_debug.h -- profiling hooks of libraindrop_hip.so.  NOT part of the C-ABI (include/raindrop_hip.h): no host binding
- * in raindrop_amd/_lib.py, no stability promise; used by tools/*_timing.py and the tests only.  Each stamp setter registers (process-wide) a device
+ * in raindrop_amd/_lib.py (but the route query, DEBUG_SIGNATURES there), no stability promise; used by tools/*_timing.py and the tests only.  Each stamp setter registers (process-wide) a device
  * buffer into which the named kernels write clock64() stamps per phase, or restores normal operation when passed NULL; the
  * pointer travels to the kernels as an argument of the launches enqueued while it is registered.
  */
@@ -28,6 +28,19 @@ void rd_debug_set_splitk_want(int workgroups);       /* target workgroup count o
  * names so far, joined by '\n' and NUL-terminated, into out[cap] (whole names only) and returns the length all of them need. */
 void rd_debug_launch_log(int on);
 size_t rd_debug_launch_log_read(char* out, size_t cap);
+/* The route one encoder layer of this shape takes (rd_temporal.hip enc_route) in the current arithmetic mode and switches, with or
+ * without a token plan: which of its kernel forms run, nothing more.  Needs no device.  Bit i of *bits:
+ *    0 rg           all four forward products on the row-block kernels       9 chain_fwd   out_proj .. LayerNorm2 as one launch
+ *    1 dx_rowblock  rg and the in_proj input-gradient product too           10 chain_bwd   LayerNorm2' .. out_proj' as one launch
+ *    2 tw           weight gradients as one tile stream fed by the products 11 attn_tiles  prepare splits the fused attention's tiles
+ *    3 panel        tiled GEMM family on its panel form                     12 afuse_fwd   in_proj + attention as one launch
+ *    4 tw2          panel: tile stream fed by a conversion pass             13 afuse_bwd   attention' + in_proj' as one launch
+ *    5 big          attention with materialised scores                      14 lean        the chains skip the fp32 FFN hidden and x1
+ *    6 lnf1         out_proj with the add + LayerNorm epilogue              15 infer       the layer has an inference forward
+ *    7 lnf2         linear2 with the add + LayerNorm epilogue               16 plan_ok     a token plan can run
+ *    8 lnb          LayerNorm backward as the prologue of the next product
+ * Returns RD_OK or the error of a bad shape. */
+int rd_debug_encoder_route(const struct rd_shape* s, int32_t with_plan, uint32_t* bits);
 
 #ifdef __cplusplus
 }

@@ -204,6 +204,13 @@ SIGNATURES = {
     "rd_rank_metrics": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "rd_confusion": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P]),
 }
+# hooks of include/raindrop_hip_debug.h that tests call through this binding (not part of the ABI)
+DEBUG_SIGNATURES = {
+    "rd_debug_encoder_route": (c_int32, [_SHP, c_int32, _P]),       # bits: ROUTE_BITS below
+}
+# bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
+ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
+              "afuse_fwd", "afuse_bwd", "lean", "infer", "plan_ok")
 
 _lib = None
 
@@ -224,7 +231,7 @@ def load():
         lib = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise RaindropHipError("cannot load %s: %s" % (LIB_PATH, e))
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(DEBUG_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

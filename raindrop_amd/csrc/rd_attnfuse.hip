@@ -108,7 +108,7 @@ __device__ __forceinline__ bf8 frag_ts(const __bf16* P, int k0, int col0, int la
   const sh8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf8, o);
 }
-// acc[j] += A(16 x KK) B(KK x 16 NT), split-bf16 (lo*hi + hi*lo + hi*hi per reduction step: the order of rd_temporal.hip's mma_b16).
+// acc[j] += A(16 x KK) B(KK x 16 NT), split-bf16 (lo*hi + hi*lo + hi*hi per reduction step: the order of rd_attention.hip's mma_b16).
 // AT / BT: the operand is read transposed (its reduction index runs along plane rows).  a0: first row (AT: column) of A's 16-wide
 // slice; B tile j starts at row (BT: column) b0 + 16 j.  ASW / BSW: the operand lives in a swizzled [.][TS] plane (lda / ldb unused).
 template <int NT, bool AT, bool BT, bool ASW, bool BSW>
@@ -855,7 +855,7 @@ constexpr int AF_NTH = 5, AF_KCX = 5;
 
 extern "C" void rd_debug_set_attnfuse_stamps(void* p) { g_af_stamps = (unsigned long long*)p; }   // not part of the ABI
 
-// ---- host interface (rd_temporal.hip) -----------------------------------------------------------------------------------------
+// ---- host interface (rd_encoder.h; driven by rd_temporal.hip) -----------------------------------------------------------------------------------------
 // RD_ATTN_FUSE=0: the round-3 launches (QKV row-block product + attention per (sample, head) + QKV input-gradient product)
 bool attnfuse_ok(int T, int D, int H, int hd) {
   const char* e = getenv("RD_ATTN_FUSE");               // read per call (tests compare both paths in one process)

@@ -956,7 +956,7 @@ int device_cus() {
 
 extern "C" void rd_debug_set_encfuse_stamps(void* p) { g_ef_stamps = (unsigned long long*)p; }   // not part of the ABI
 
-bool encfuse_ok(int D, int H) {
+static bool encfuse_ok(int D, int H) {
   const char* e = getenv("RD_ENC_FUSE");               // read per call (tests compare the fused and the unfused path in one process)
   const bool enabled = !(e && atoi(e) == 0);
   // widths: the two compiled-in pairs (P19, P12).  The runtime-width instantiation of the backward chain spills 84 bytes per lane
@@ -1014,8 +1014,8 @@ int launch_enc_post_fwd(long M, int D, int H, const float* attn, const float* x,
   return check_launch("k_enc_post_fwd");
 }
 
-// the widths with a save-free chain instantiation, in the current mode and switches
-bool encfuse_infer_ok(int D, int H) { return encfuse_ok(D, H) && ef_specialize(D, H) == 1; }
+// in the current mode and switches -- 0: no fused chain at these widths; 1: the training chains; 2: and the save-free (inference) instantiation
+int encfuse_level(int D, int H) { return !encfuse_ok(D, H) ? 0 : ef_specialize(D, H) == 1 ? 2 : 1; }
 
 int encfuse_part_rows(long M) { return (int)((M + 31) / 32); }
 

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "rd_common.h"
+#include "rd_encoder.h"
 #include "rd_k1_layout.h"
 #include "rd_plan.h"
 #include "rd_rng.h"
@@ -39,16 +40,7 @@ int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, 
 int fused_dw(const k1::Layout& L, const k1::DwPlan& P, const void* tpX, const void* tpY1, const void* tpD1,
              const void* tpD2, const void* ones, float* part, const float* rupart, float* dW1, float* db1, float* dW2, float* db2,
              float* dRu, hipStream_t st);
-// streamed weight gradients from row tiles (rd_tile_wgrad.hip, rd_tiles_export.hip; declarations as in rd_temporal.hip)
-struct TileWgradJob { const void *tA, *tB; float* part; float *dW, *db; int N, K; const int32_t* s32; int S; int hd, hdp, H, D; };
-struct TileColsumJob { const float* x; int M, N, n1; float *out1, *out2; };
-size_t tile_elems(long M, int cols);
-size_t tile_wgrad_ones_elems();
-size_t tile_wgrad_part_floats(int N, int K);
-bool tile_wgrad_ok(int N, int K);
-int launch_rows_to_tiles(long M, int n, const float* const* x, const long* ld, const int* cols, void* const* tiles, hipStream_t st);
-int launch_tile_wgrad(long M, int njobs, const TileWgradJob* jobs, const void* ones, int ncs, const TileColsumJob* cs,
-                      hipStream_t st, const int32_t* s32);
+// (the streamed weight gradients from row tiles, rd_tile_wgrad.hip / rd_tiles_export.hip: rd_encoder.h)
 
 namespace {
 

@@ -44,7 +44,7 @@ struct RowGemmArgs {
   int one_product;                                  // RD_PREC_BF16
   // LayerNorm epilogue (N <= one round of columns): s = residual + dropout(A W^T + bias) -> ln_s (saved for the backward),
   // C = LayerNorm(s) * ln_g + ln_b, (mean, rstd) -> ln_stats.  Replaces the separate add+LayerNorm kernel of the encoder
-  // layer (rd_temporal.hip k_add_ln_fwd_v: same lane <-> column assignment, same reduction order, same dropout quads).
+  // layer (rd_layernorm.hip k_add_ln_fwd_v: same lane <-> column assignment, same reduction order, same dropout quads).
   const float* ln_g; const float* ln_b; float* ln_s; float* ln_stats;
   // Tile export (rd_tile_wgrad.hip): the split A planes, transposed into MFMA operand tiles whose reduction index is the
   // ROW -- [chunk of 32 rows][column tile of 16][hi, lo][64][8] -- the operand format of the weight-gradient stream.
@@ -52,7 +52,7 @@ struct RowGemmArgs {
   // LayerNorm-backward prologue (template flag LNB): the A operand is not read but COMPUTED -- A = dropout-masked gradient of the
   // LayerNorm input, from dy (lnb_dy), the saved pre-norm sum (lnb_s), (mean, rstd) (lnb_stats) and gamma (lnb_g); the
   // unmasked gradient goes to lnb_ds (the residual branch), per-workgroup dgamma | dbeta partials to lnb_part
-  // [workgroup][2K].  Same arithmetic and lane <-> column assignment as k_ln_bwd_v (rd_temporal.hip), which it replaces
+  // [workgroup][2K].  Same arithmetic and lane <-> column assignment as k_ln_bwd_v (rd_layernorm.hip), which it replaces
   // together with the write + re-read of its second output.
   const float *lnb_dy, *lnb_s, *lnb_stats, *lnb_g; float *lnb_ds, *lnb_part; float lnb_p; uint32_t lnb_site; uint64_t lnb_seed;
   // Live row count on the device (token plan, rd_plan.h: plan[0]) or null.  The grid is sized for the padded M; a workgroup
@@ -481,7 +481,7 @@ extern "C" void rd_debug_set_rowgemm_stamps(void* p) {   // not part of the ABI
   g_rg_stamps = (unsigned long long*)p;
 }
 
-// ---- host interface (used by rd_temporal.hip) -----------------------------------------------------
+// ---- host interface (rd_encoder.h; used by rd_temporal.hip) -----------------------------------------------------
 bool rowgemm_ok(int N, int K, long lda, long ldc) {
   static const bool enabled = [] { const char* e = getenv("RD_ROWGEMM"); return !(e && atoi(e) == 0); }();
   const int kc = (K + 31) / 32;

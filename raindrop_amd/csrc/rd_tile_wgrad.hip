@@ -182,7 +182,7 @@ __global__ __launch_bounds__(TWR_THR) void k_twg_reduce(TwArgs a) {
 
 }  // namespace
 
-// ---- host interface (rd_temporal.hip) ---------------------------------------------------------------------
+// ---- host interface (rd_encoder.h; rd_temporal.hip) ---------------------------------------------------------------------
 size_t tile_elems(long M, int cols) { return (size_t)cdiv((int)M, 32) * cdiv(cols, 16) * 2 * TILE; }   // bf16 elements of a tile tensor
 size_t tile_wgrad_ones_elems() { return 3 * TILE; }   // [ones hi][zeros][zeros], written by k_wsplit (rd_rowgemm.hip)
 size_t tile_wgrad_part_floats(int N, int K) {

@@ -39,7 +39,7 @@ W_IN = "self_attn.in_proj_weight"
 
 # name -> (F, D, nhid, environment switch or None); D = 4 F + 16, head_dim D / 2 = 76, 80, 68, 72.
 # attnfuse_ok() (rd_attnfuse.hip) admits all four widths, but a layer reaches the fused launches only on the row-block + tile-stream
-# path (rd_temporal.hip tile_path), whose in_proj input-gradient product needs ceil(3 D / 32) == 15 reduction chunks (rd_rowgemm.hip
+# path (rd_temporal.hip enc_route `tw`), whose in_proj input-gradient product needs ceil(3 D / 32) == 15 reduction chunks (rd_rowgemm.hip
 # rowgemm_ok): D = 152 .. 160.  With a plan registered, D = 136 (13 chunks) and D = 144 (14) are REFUSED with RD_EINVAL before any
 # launch, under RD_ENC_SPECIALIZE=0 too -- no kernel of this path can run at those widths.  PLAN_WIDTHS are the widths that run;
 # REFUSED_WIDTHS are pinned as refusals (tests/test_plan_layer_gpu.py test_widths_outside_the_row_block_envelope_are_refused).

@@ -63,7 +63,7 @@ def keep(seed, site, idx, p):
 
 
 def site_of(family, layer=0):
-    """Site number of an encoder family in layer `layer` (rd_temporal.hip:2740-2787: SITE_x + L)."""
+    """Site number of an encoder family in layer `layer` (rd_temporal.hip rd_encoder_layer_fwd / _bwd: SITE_x + L)."""
     return int(family) + int(layer)
 
 
@@ -84,12 +84,12 @@ def obs_embed_index(T, B, F, d):
 
 
 def padded_rows(T, B):
-    """int64 [T, B]: row t*B + b of a [T, B, *] tensor (rd_temporal.hip:136: "row of step t = t*B + b")."""
+    """int64 [T, B]: row t*B + b of a [T, B, *] tensor (rd_attention.hip:58: "row of step t = t*B + b")."""
     return np.arange(T, dtype=np.int64)[:, None] * B + np.arange(B, dtype=np.int64)[None, :]
 
 
 def plan_rows(off, rank, T):
-    """int64 [T, B]: row off[rank[b]] + t of step t of sample b on a token plan (rd_temporal.hip:137-138, rd_plan.h: the rows of
+    """int64 [T, B]: row off[rank[b]] + t of step t of sample b on a token plan (rd_attention.hip:59-60, rd_plan.h: the rows of
     the sample of rank r are the block off[r] .. off[r] + len[r]).  Entries with t >= len[b] name rows of other samples: the
     caller masks them out (those steps do not exist on the plan)."""
     off, rank = np.asarray(off, dtype=np.int64), np.asarray(rank, dtype=np.int64)
@@ -98,7 +98,7 @@ def plan_rows(off, rank, T):
 
 def row_local_index(rows, N):
     """int64 [..., N]: element row*N + c of the row-local sites (attention output and FFN output: N = D; FFN hidden: N = nhid) --
-    rd_temporal.hip:1990 / 2102 (add + LayerNorm), rd_gemm.hip:97 / 412, rd_rowgemm.hip:240 / 415 / 449, rd_encfuse.hip:336 / 507 /
+    rd_layernorm.hip:33 / 145 (add + LayerNorm), rd_gemm.hip:97 / 412, rd_rowgemm.hip:240 / 415 / 449, rd_encfuse.hip:336 / 507 /
     689."""
     rows = np.asarray(rows, dtype=np.int64)
     return rows[..., None] * int(N) + np.arange(int(N), dtype=np.int64)
@@ -106,7 +106,7 @@ def row_local_index(rows, N):
 
 def attn_bh(B, H, rank=None):
     """int64 [B, H]: the (sample, head) number of the attention masks: b*H + h with b the SAMPLE index on the padded layout
-    (rd_temporal.hip:260: bh = blockIdx.y, b = bh / H) and the sample's RANK on a token plan (rd_temporal.hip:137 "workgroup index b
+    (rd_attention.hip:182: bh = blockIdx.y, b = bh / H) and the sample's RANK on a token plan (rd_attention.hip:59 "workgroup index b
     is a RANK", rd_attnfuse.hip:22 / 360: attn_quad(rank * H + h, ..))."""
     b = np.arange(B, dtype=np.int64) if rank is None else np.asarray(rank, dtype=np.int64)
     return b[:, None] * H + np.arange(H, dtype=np.int64)[None, :]
@@ -114,7 +114,7 @@ def attn_bh(B, H, rank=None):
 
 def attn_quad(bh, T, q, key):
     """(quad, component) of probability (bh, q, key): quad (bh*T + key)*ceil(T/4) + (q >> 2), component q & 3 --
-    rd_temporal.hip:156-158 (attn_quad) and :159-165 (attn_keep1)."""
+    rd_attention.hip:78-80 (attn_quad) and :81-87 (attn_keep1)."""
     bh, q, key = (np.asarray(v, dtype=np.int64) for v in (bh, q, key))
     return (bh * T + key) * ((T + 3) >> 2) + (q >> 2), q & 3
 

@@ -35,7 +35,7 @@ TUNED = [(h, w) for h in TrainStep.TUNE_HEIGHTS for w in TrainStep.TUNE_WAVES]  
 SETTINGS = list(dict.fromkeys(CORNERS + TUNED))
 
 # (F, D, nhid): D = 4 F + 16.  rowgemm_ok needs ceil(K / 32) of 5, 9 and 15 for K = D, nhid and 3 D, every width a multiple of 4, and
-# the LayerNorm epilogue D <= 256 (rd_temporal.hip `rg`, `tile_path`, `lnf1/lnf2`, `lnf`):
+# the LayerNorm epilogue D <= 256 (rd_temporal.hip enc_route: `rg`, `tw`, `lnf1/lnf2`, `lnb`):
 #   152 / 272 / 456 -> 5 / 9 / 15 (P19);  160 / 288 / 480 -> 5 / 9 / 15 (P12: no padding column in any plane);
 #   156 / 260 / 468 -> 5 / 9 / 15: not compiled into any chain; N = 260 leaves 4 valid columns in a plain product's second round,
 #   N = 468 (in_proj) 212 of 256.
@@ -333,7 +333,7 @@ POISON = 0x7FC07FC0                                  # fp32 NaN = a pair of bf16
 
 
 def _plan_step(cfg, gs, batch, p_drop=0.2):
-    """One eager training step on the token plan (the configuration in which the chains run LEAN: rd_temporal.hip enc_lean), run
+    """One eager training step on the token plan (the configuration in which the chains run LEAN: rd_temporal.hip enc_route `lean`), run
     twice with the saved buffers of the encoder layers filled with a NaN pattern in between -> (loss, logits, gradients) of the
     second run and the number of 32-bit words of those buffers the second run did not write."""
     from raindrop_amd import dp
