@@ -1053,6 +1053,8 @@ def test_k1_fused_vs_generic_same_arithmetic(F, T, B, kind, precision_mode, monk
     two leftover graph rows of a sample, a missing dW slice, a wrong gate bit -- fails these by orders of magnitude."""
     if precision_mode != "bf16x3":
         pytest.skip("the fused path exists in split-bf16 mode only")
+    # (F = 64 lies outside the fused envelope, F <= 48: that row runs the generic path twice.  The envelope's own edges are held to
+    # float64 by tests/test_sensor_stage_float64_gpu.py.)
     from raindrop_amd import _lib, ops
     d, K = 4, T * 4
     rng = np.random.default_rng(F * 1000 + T * 10 + B)
