@@ -1,6 +1,6 @@
 /*
  * raindrop_hip_debug.h -- profiling hooks of libraindrop_hip.so.  NOT part of the C-ABI (include/raindrop_hip.h): no host binding
- * in raindrop_amd/_lib.py (but the route query, DEBUG_SIGNATURES there), no stability promise; used by tools/*_timing.py and the tests only.  Each stamp setter registers (process-wide) a device
+ * in raindrop_amd/_lib.py (but the route queries, DEBUG_SIGNATURES there), no stability promise; used by tools/*_timing.py and the tests only.  Each stamp setter registers (process-wide) a device
  * buffer into which the named kernels write clock64() stamps per phase, or restores normal operation when passed NULL; the
  * pointer travels to the kernels as an argument of the launches enqueued while it is registered.
  */
@@ -41,6 +41,14 @@ size_t rd_debug_launch_log_read(char* out, size_t cap);
  *    8 lnb          LayerNorm backward as the prologue of the next product
  * Returns RD_OK or the error of a bad shape. */
 int rd_debug_encoder_route(const struct rd_shape* s, int32_t with_plan, uint32_t* bits);
+/* The route one sensor-stage call of this shape takes (rd_k1_route.h k1_route) in the current arithmetic mode and switches.  ldz: row
+ * stride of z / dz; with_pe: the call writes PE and the mask (rd_sensor_stage_fwd*; 0: rd_msgpass_fwd, rd_msgpass_bwd); with_coef:
+ * a coefficient-dropout table is given.  Needs no device.  Bit i of *bits:
+ *    0 fused         the LDS-resident kernels, else the tiled GEMM family    3 coef          the COEF instantiations
+ *    1 specialised   the <3, 34, 60> instantiation, not <3, 0, 0>            4 tiles         generic: split weights, panel products
+ *    2 infer         the shape has a save-free forward                       5 wgrad_stream  generic: weight gradients by tile stream
+ * and in bits 8-9 rt, the row tiles ceil(F / 16) of a fused call (0 otherwise).  Returns RD_OK or the error of a bad shape. */
+int rd_debug_sensor_route(const struct rd_shape* s, int32_t ldz, int32_t with_pe, int32_t with_coef, uint32_t* bits);
 
 #ifdef __cplusplus
 }

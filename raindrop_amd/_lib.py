@@ -207,10 +207,13 @@ SIGNATURES = {
 # hooks of include/raindrop_hip_debug.h that tests call through this binding (not part of the ABI)
 DEBUG_SIGNATURES = {
     "rd_debug_encoder_route": (c_int32, [_SHP, c_int32, _P]),       # bits: ROUTE_BITS below
+    "rd_debug_sensor_route": (c_int32, [_SHP, c_int32, c_int32, c_int32, _P]),      # ldz, with_pe, with_coef; bits: SENSOR_ROUTE_BITS below
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
               "afuse_fwd", "afuse_bwd", "lean", "infer", "plan_ok")
+# bit i of rd_debug_sensor_route's mask (csrc/rd_k1_route.h K1Route's flags, in declaration order); bits 8-9: the row-tile count rt
+SENSOR_ROUTE_BITS = ("fused", "specialised", "infer", "coef", "tiles", "wgrad_stream")
 
 _lib = None
 

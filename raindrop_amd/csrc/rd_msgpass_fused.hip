@@ -32,7 +32,7 @@
 #include <stdlib.h>
 
 #include "rd_common.h"
-#include "rd_k1_layout.h"
+#include "rd_k1_route.h"
 #include "rd_plan.h"
 #include "rd_rng.h"
 
@@ -82,27 +82,6 @@ constexpr int NTHR = RD_K1_NTHR; // 512: 8 wavefronts, wave w owns output column
 constexpr int NWAVE = NTHR / 64, NJ = 16 / NWAVE;
 constexpr int CPT = 2048 / NTHR; // cells (t, f) per thread and batch of loads (F*T <= 2048 needs one batch)
 constexpr int GTHR = NTHR / 2, GWAVE = NWAVE / 2;   // threads / waves of one of the two groups (A: waves [0, GWAVE), B: the rest)
-
-struct FusedArgs {
-  const float *src, *R_u, *b1, *b2, *ssum;
-  const float *times, *tscale; const int64_t* lengths; uint8_t* mask; int d_pe;   // optional PE / mask (fwd)
-  const __bf16* wt;              // weight tiles [layer 2][orient 2][nct][NKC][hi/lo][64][8]
-  __bf16* ones;                  // bwd writes the constant bias-gradient operand tile of rd_msgpass_dw.hip here
-  __bf16 *tpX, *tpY1, *tpD1, *tpD2;   // row tiles of X, Y1 (fwd writes) and dZ1, dZ2 (bwd writes)
-  // gates (rd_k1_layout.h): m1 = Y1 > 0 as 64-bit lane masks [slot][column tile][RT][4] of the epilogue that made them (the backward's
-  // epilogue has the same lane -> element map and applies them as v_cndmask operands); m2 = Y2 > 0 and mx = X > 0 as one byte per
-  // (slot, t, f) cell, bit c = channel c
-  uint64_t* m1; uint8_t *m2, *mx;
-  float* z;
-  const float* dz;               // bwd
-  float* rupart;
-  int B, T, F, K, ldz, nct, q, rem, per;
-  float p_drop; uint64_t seed; const uint64_t* seed_cell;
-  unsigned long long* stamps;    // debug: per-phase clock64() of every wave of the first 4 workgroups
-  const int32_t* plan;           // token plan (rd_plan.h) or null: which steps of a sample are live, and where its z rows are
-  int* lin;                      // [B] per slot: 1 + last step with a non-zero observation (fwd writes, bwd reads)
-  const float* coef;             // COEF instantiations: [2][B][F] per-(layer, sample, sensor) aggregate coefficients in place of ssum[f]
-};
 
 // Which sample a workgroup owns and where its rows live.  Padded layout (no plan): workgroup i = sample i, every step is
 // live, z row of step t = t*B + b.  With a plan: workgroup i owns the sample of RANK i (longest first); `b` indexes the
@@ -1015,66 +994,44 @@ __global__ __launch_bounds__(NTHR) void k_msg_bwd_fused(FusedArgs a) {
   }
 }
 
-template <int RT, int FC, int TC, bool COEF = false>
-int launch_fused(const FusedArgs& a, bool bwd, hipStream_t st) {
-  const size_t lds = (size_t)4 * RT * 16 * LDX * sizeof(__bf16) + (size_t)(COEF ? 2 : 1) * RT * 16 * sizeof(float) +
-                     (size_t)NWAVE * sizeof(int);   // planes, ssum (COEF: the two coefficient rows), LinW (forward)
-  if (!bwd) {
-    RD_LDS_ATTR((k_msg_fwd_fused<RT, FC, TC, true, COEF>), lds);
-    hipLaunchKernelGGL((k_msg_fwd_fused<RT, FC, TC, true, COEF>), dim3(a.B), dim3(NTHR), lds, st, a);
-    return check_launch("k_msg_fwd_fused");
-  }
-  RD_LDS_ATTR((k_msg_bwd_fused<RT, FC, TC, COEF>), lds);
-  hipLaunchKernelGGL((k_msg_bwd_fused<RT, FC, TC, COEF>), dim3(a.B), dim3(NTHR), lds, st, a);
-  return check_launch("k_msg_bwd_fused");
+
+// planes, ssum (COEF: the two coefficient rows), LinW (forward)
+size_t fused_lds_bytes(int rt, bool coef) {
+  return (size_t)4 * rt * 16 * LDX * sizeof(__bf16) + (size_t)(coef ? 2 : 1) * rt * 16 * sizeof(float) + (size_t)NWAVE * sizeof(int);
+}
+template <auto KERN>
+int launch_k1(const char* name, const FusedArgs& a, int rt, bool coef, hipStream_t st) {
+  const size_t lds = fused_lds_bytes(rt, coef);
+  RD_LDS_ATTR(KERN, lds);
+  hipLaunchKernelGGL(KERN, dim3(a.B), dim3(NTHR), lds, st, a);
+  return check_launch(name);
+}
+template <int RT, int FC, int TC>
+int launch_shape(const FusedArgs& a, bool coef, bool bwd, hipStream_t st) {
+  if (coef)                                            // coefficient dropout: the COEF instantiations
+    return bwd ? launch_k1<k_msg_bwd_fused<RT, FC, TC, true>>("k_msg_bwd_fused", a, RT, coef, st)
+               : launch_k1<k_msg_fwd_fused<RT, FC, TC, true, true>>("k_msg_fwd_fused", a, RT, coef, st);
+  return bwd ? launch_k1<k_msg_bwd_fused<RT, FC, TC, false>>("k_msg_bwd_fused", a, RT, coef, st)
+             : launch_k1<k_msg_fwd_fused<RT, FC, TC, true, false>>("k_msg_fwd_fused", a, RT, coef, st);
 }
 
-// the save-free forward: the P19 instantiation only (fused_msgpass_infer_ok is the host-side test)
-int launch_fused_infer(const FusedArgs& a, hipStream_t st) {
-  const size_t lds = (size_t)4 * 3 * 16 * LDX * sizeof(__bf16) + (size_t)3 * 16 * sizeof(float) + (size_t)NWAVE * sizeof(int);
-  RD_LDS_ATTR((k_msg_fwd_fused<3, 34, 60, false>), lds);
-  hipLaunchKernelGGL((k_msg_fwd_fused<3, 34, 60, false>), dim3(a.B), dim3(NTHR), lds, st, a);
-  return check_launch("k_msg_fwd_fused<save-free>");
-}
-
-static bool k1_specialize_on() {
-  const char* e = getenv("RD_K1_SPECIALIZE");          // read per call
-  return !(e && atoi(e) == 0);
-}
-
-// RD_K1_SPECIALIZE=0 runs the P19 shape on the generic instantiation (A/B, and the parity test of the two)
-int launch_fused_shape(const FusedArgs& a, const k1::Layout& L, bool bwd, hipStream_t st, bool save = true) {
+// the one selection of an instantiation: (specialised or row tiles) x COEF x direction, and the save-free forward of the P19 shape
+int launch_fused(const FusedArgs& a, const K1Route& r, bool bwd, bool save, hipStream_t st) {
   if (a.ldz >= 1024) return fail(RD_EUNSUPPORTED, "fused message passing: ldz (%d) must be < 1024", a.ldz);
-  const char* e = getenv("RD_K1_SPECIALIZE");
-  const bool model_layout = a.ldz == 4 * L.F + 16 && (bwd || a.times == nullptr || a.d_pe == 16);
   if (!save) {
-    if (a.coef) return fail(RD_EUNSUPPORTED, "fused message passing: the save-free forward takes no coefficient table");
-    if (bwd || !(L.F == 34 && L.T == 60 && model_layout && k1_specialize_on()))
-      return fail(RD_EUNSUPPORTED, "fused message passing: no save-free instantiation for this shape");
-    return launch_fused_infer(a, st);
+    if (r.coef) return fail(RD_EUNSUPPORTED, "fused message passing: the save-free forward takes no coefficient table");
+    if (bwd || !r.specialised) return fail(RD_EUNSUPPORTED, "fused message passing: no save-free instantiation for this shape");
+    return launch_k1<k_msg_fwd_fused<3, 34, 60, false>>("k_msg_fwd_fused<save-free>", a, 3, false, st);
   }
-  if (a.coef) {                                        // coefficient dropout: the COEF instantiations, same shape dispatch
-    if (L.F == 34 && L.T == 60 && model_layout && !(e && atoi(e) == 0)) return launch_fused<3, 34, 60, true>(a, bwd, st);
-    switch (L.RT) {
-      case 1: return launch_fused<1, 0, 0, true>(a, bwd, st);
-      case 2: return launch_fused<2, 0, 0, true>(a, bwd, st);
-      case 3: return launch_fused<3, 0, 0, true>(a, bwd, st);
-      default: return fail(RD_EUNSUPPORTED, "fused message passing: F = %d > 48", L.F);
-    }
-  }
-  if (L.F == 34 && L.T == 60 && model_layout && !(e && atoi(e) == 0)) return launch_fused<3, 34, 60>(a, bwd, st);
-  switch (L.RT) {
-    case 1: return launch_fused<1, 0, 0>(a, bwd, st);
-    case 2: return launch_fused<2, 0, 0>(a, bwd, st);
-    case 3: return launch_fused<3, 0, 0>(a, bwd, st);
+  if (r.specialised) return launch_shape<3, 34, 60>(a, r.coef, bwd, st);
+  switch (r.rt) {
+    case 1: return launch_shape<1, 0, 0>(a, r.coef, bwd, st);
+    case 2: return launch_shape<2, 0, 0>(a, r.coef, bwd, st);
+    case 3: return launch_shape<3, 0, 0>(a, r.coef, bwd, st);
     // (RT = 4, 48 < F <= 64: its runtime-shape instantiation spilled 68-88 bytes per lane and no dataset has such a sensor count --
-    // round 4 narrowed the envelope to F <= 48, fused_msgpass_ok; those shapes take the panel-product path)
-    default: return fail(RD_EUNSUPPORTED, "fused message passing: F = %d > 48", L.F);
+    // round 4 narrowed the envelope to F <= 48, k1_envelope; those shapes take the panel-product path)
+    default: return fail(RD_EUNSUPPORTED, "fused message passing: F = %d > 48", a.F);
   }
-}
-
-void fill_layout(FusedArgs& a, const k1::Layout& L) {
-  a.B = L.B; a.T = L.T; a.F = L.F; a.K = L.K; a.nct = L.nct; a.q = L.q; a.rem = L.rem; a.per = L.per;
 }
 
 }  // namespace
@@ -1082,62 +1039,22 @@ void fill_layout(FusedArgs& a, const k1::Layout& L) {
 static unsigned long long* g_stamps = nullptr;
 extern "C" void rd_debug_set_stamps(void* p) { g_stamps = (unsigned long long*)p; }   // not part of the ABI
 
-bool fused_msgpass_ok(const rd_shape* s) {
-  // RD_K1_FUSED=0 routes the fused envelope through the generic tiled path (read per call: the parity tests compare
-  // the two paths in one process)
-  const char* e = getenv("RD_K1_FUSED");
-  const bool enabled = !(e && atoi(e) == 0);
-  const int K = s->T * s->d_ob;
-  // staging tile [F][244] fp32 must fit inside two bf16 planes [RT*16][256]; d_ob == 4 only
-  // index arithmetic of the kernels is 32-bit with 24-bit multiplies: B*T rows < 2^22 (with ldz < 1024, checked at the call)
-  return enabled && precision() == RD_PREC_BF16X3 && s->d_ob == 4 && s->F <= 48 && K <= 240 && (K % 16) == 0 && K >= 16 &&
-         (long)s->B * s->T < (1L << 22);
-}
-
 int fused_wprep(const k1::Layout& L, const float* W1, const float* W2, void* wt, hipStream_t st) {
   hipLaunchKernelGGL(k_wprep, dim3(4 * L.nct), dim3(256), 0, st, W1, W2, (__bf16*)wt, L.K, L.nct);
   return check_launch("k_wprep");
 }
 
-// the sensor stage of this shape has a save-free forward (model layout: ldz = 4 F + 16, d_pe = 16) in the current mode and switches
-bool fused_msgpass_infer_ok(const rd_shape* s) {
-  return fused_msgpass_ok(s) && s->F == 34 && s->T == 60 && s->d_pe == 16 && k1_specialize_on();
-}
-
-// save = false: the save-free instantiation (tpX .. mx are not touched and may be null)
-int fused_msgpass_fwd(const k1::Layout& L, const float* src, const float* R_u, const float* b1, const float* b2,
-                      const float* ssum, const void* wt, float p_drop, uint64_t seed, void* tpX, void* tpY1,
-                      void* m1, void* m2, void* mx, float* z, int ldz, hipStream_t st, const float* times,
-                      const int64_t* lengths, const float* tscale, uint8_t* mask, int d_pe, bool save, const float* coef) {
-  FusedArgs a{};
-  a.coef = coef;
-  fill_layout(a, L);
-  a.times = times; a.lengths = lengths; a.tscale = tscale; a.mask = mask; a.d_pe = d_pe;
-  a.src = src; a.R_u = R_u; a.b1 = b1; a.b2 = b2; a.ssum = ssum; a.wt = (const __bf16*)wt;
-  a.tpX = (__bf16*)tpX; a.tpY1 = (__bf16*)tpY1; a.m1 = (uint64_t*)m1; a.m2 = (uint8_t*)m2; a.mx = (uint8_t*)mx;
-  a.z = z; a.ldz = ldz;
-  a.p_drop = p_drop; a.seed = seed; a.seed_cell = seed_cell(); a.stamps = g_stamps;
-  a.plan = token_plan(); a.lin = save ? reinterpret_cast<int*>(reinterpret_cast<char*>(mx) + k1::lin_offset(L.B, L.T, L.F)) : nullptr;
-  return launch_fused_shape(a, L, false, st, save);
-}
-
-int fused_msgpass_bwd(const k1::Layout& L, const float* src, const float* ssum, const void* wt, float p_drop,
-                      const void* m1, const void* m2, const void* mx, const float* dz, int ldz, void* tpD1, void* tpD2,
-                      void* ones, float* rupart, hipStream_t st, const void* tpX, const void* tpY1, const float* coef) {
-  FusedArgs a{};
-  a.coef = coef;
-  fill_layout(a, L);
-  {   // the forward's row tiles, only touched here (RD_K1_WARM=0: not at all; A/B)
-    static const bool warm = [] { const char* e = getenv("RD_K1_WARM"); return !(e && atoi(e) == 0); }();
-    a.tpX = warm ? (__bf16*)const_cast<void*>(tpX) : nullptr; a.tpY1 = warm ? (__bf16*)const_cast<void*>(tpY1) : nullptr;
-  }
-  a.src = src; a.ssum = ssum; a.wt = (const __bf16*)wt;
-  a.m1 = (uint64_t*)const_cast<void*>(m1); a.m2 = (uint8_t*)const_cast<void*>(m2); a.mx = (uint8_t*)const_cast<void*>(mx);
-  a.dz = dz; a.ldz = ldz; a.tpD1 = (__bf16*)tpD1; a.tpD2 = (__bf16*)tpD2; a.ones = (__bf16*)ones; a.rupart = rupart;
-  a.p_drop = p_drop; a.stamps = g_stamps ? g_stamps + K1_STAMP_WORDS : nullptr;
+int fused_msgpass(FusedArgs a, const k1::Layout& L, const K1Route& r, bool bwd, bool save, hipStream_t st) {
+  a.B = L.B; a.T = L.T; a.F = L.F; a.K = L.K; a.nct = L.nct; a.q = L.q; a.rem = L.rem; a.per = L.per;
   a.plan = token_plan();
-  a.lin = reinterpret_cast<int*>(reinterpret_cast<char*>(const_cast<void*>(mx)) + k1::lin_offset(L.B, L.T, L.F));
-  return launch_fused_shape(a, L, true, st);
+  a.lin = save ? reinterpret_cast<int*>(reinterpret_cast<char*>(a.mx) + k1::lin_offset(L.B, L.T, L.F)) : nullptr;
+  a.seed_cell = bwd ? nullptr : seed_cell();
+  a.stamps = g_stamps && bwd ? g_stamps + K1_STAMP_WORDS : g_stamps;
+  if (bwd) {   // the forward's row tiles, only touched here (RD_K1_WARM=0: not at all; A/B)
+    static const bool warm = [] { const char* e = getenv("RD_K1_WARM"); return !(e && atoi(e) == 0); }();
+    if (!warm) a.tpX = a.tpY1 = nullptr;
+  }
+  return launch_fused(a, r, bwd, save, st);
 }
 
 }  // namespace rd

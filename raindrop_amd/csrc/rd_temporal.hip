@@ -11,13 +11,10 @@
 #include <algorithm>
 
 #include "rd_encoder.h"
+#include "rd_k1_route.h"
 #include "rd_plan.h"
 
 namespace rd {
-int k1_weight_split_specs(const rd_shape* s, const float* W1, const float* W2, void* saved, size_t saved_bytes, WsplitSpec* out);
-bool fused_msgpass_ok(const rd_shape* s);
-bool fused_msgpass_infer_ok(const rd_shape* s);
-
 EncDims enc_dims(const rd_shape* s) {
   EncDims e;
   e.T = s->T; e.B = s->B; e.D = s->F * s->d_ob + s->d_pe; e.H = s->nhead; e.Hd = e.D / e.H;
@@ -367,7 +364,7 @@ extern "C" int rd_step_begin(const rd_shape* s, const int64_t* lengths, int32_t*
 extern "C" int rd_step_prepare_covers(const rd_shape* s, int32_t* encoder, int32_t* sensor_stage) {
   if (check_enc(s)) return RD_EINVAL;
   if (encoder) *encoder = enc_route(enc_dims(s), false, ROUTE_RG).rg ? 1 : 0;
-  if (sensor_stage) *sensor_stage = fused_msgpass_ok(s) ? 1 : 0;
+  if (sensor_stage) *sensor_stage = k1_route(s, K1_FUSED).fused ? 1 : 0;
   return RD_OK;
 }
 
@@ -446,7 +443,7 @@ extern "C" int rd_encoder_layer_fwd(const rd_shape* s, int32_t layer, const floa
 // condition and, like everywhere in the route, is read once per process: flipping it later in the process changes nothing.
 extern "C" int rd_infer_covers(const rd_shape* s, int32_t* sensor_stage, int32_t* encoder) {
   if (check_enc(s)) return RD_EINVAL;
-  if (sensor_stage) *sensor_stage = fused_msgpass_infer_ok(s) ? 1 : 0;
+  if (sensor_stage) *sensor_stage = k1_route(s, K1_SIZES).infer ? 1 : 0;
   if (encoder) *encoder = enc_route(enc_dims(s), false, ROUTE_FWD).infer ? 1 : 0;
   return RD_OK;
 }

@@ -73,9 +73,9 @@ def site_of(family, layer=0):
 
 
 def obs_embed_index(T, B, F, d):
-    """int64 [T, B, F*d]: element ((t*B + b)*F + f)*d + c of h in its own [T, B, F*d] order -- rd_msgpass.hip:73 (k_obs_embed) and,
-    as quad (t*B + b)*F + f with the four channels c as components (d = 4), rd_msgpass_fused.hip:602.  `b` is the caller's sample
-    index on the padded layout AND on a token plan (rd_msgpass_fused.hip:107-110: `b` indexes the caller's tensors)."""
+    """int64 [T, B, F*d]: element ((t*B + b)*F + f)*d + c of h in its own [T, B, F*d] order -- rd_msgpass.hip:45 (k_obs_embed) and,
+    as quad (t*B + b)*F + f with the four channels c as components (d = 4), rd_msgpass_fused.hip:581.  `b` is the caller's sample
+    index on the padded layout AND on a token plan (rd_msgpass_fused.hip:86-89: `b` indexes the caller's tensors)."""
     t = np.arange(T, dtype=np.int64)[:, None, None, None]
     b = np.arange(B, dtype=np.int64)[None, :, None, None]
     f = np.arange(F, dtype=np.int64)[None, None, :, None]

@@ -151,7 +151,7 @@ def bound_of(mode):
 
 
 def in_envelope(F, T):
-    """rd_msgpass.hip fused_envelope at d_ob = 4"""
+    """rd_k1_route.h k1_envelope at d_ob = 4"""
     K = 4 * T
     return F <= 48 and 16 <= K <= 240 and K % 16 == 0
 

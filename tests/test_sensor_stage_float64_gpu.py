@@ -13,7 +13,7 @@ entry points route to the generic kernels.  Cases, inputs, reference and bounds:
   2. the COEF instantiations: the table rd_msgpass_coef_table wrote is read back and handed to the reference as data, the gap-placed
      biases are recomputed with those scales (and the margin conditions re-asserted here, since the host cannot know the table);
   3. F = 34, T = 60 under RD_K1_SPECIALIZE=0: the log does not tell instantiations apart, so the runtime-shape <3, 0, 0> twin must
-     be bit-equal to the specialised <3, 34, 60> run and both must meet the bounds;
+     be bit-equal to the specialised <3, 34, 60> run and both must meet the bounds (and the route query names the instantiation);
   4. a registered token plan (bf16x3): z and PE on live rows, dz rows >= M_live NaN.  The sensor-stage entry points accept a plan at
      every shape -- inside the envelope the fused kernels read it, outside the generic scatter / gather does -- so there is no
      refusal to pin (unlike the encoder layer's widths);
@@ -162,11 +162,23 @@ def _compare(kind, c, mode, got):
     assert not bad, (kind, c["name"], mode, bad)
 
 
+def _route(c):
+    """the route of c's sensor-stage call (rd_debug_sensor_route) in the mode and switches of the moment: the instantiation, which
+    the log does not tell"""
+    L = _L()
+    bits = ctypes.c_uint32(0)
+    L.call("rd_debug_sensor_route", ctypes.byref(L.shape(c["B"], c["T"], c["F"], SR.D_OB)), c["D"], 1, int(c["coef"] is not None),
+           ctypes.byref(bits))
+    return {n for i, n in enumerate(L.SENSOR_ROUTE_BITS) if bits.value >> i & 1} | {"rt%d" % (bits.value >> 8)}
+
+
 def _assert_route(c, mode, names):
     if c["envelope"] and mode == "bf16x3":
         assert FUSED <= names, (c["name"], mode, sorted(names))
+        assert {"fused", "rt%d" % ((c["F"] + 15) // 16)} <= _route(c), (c["name"], sorted(_route(c)))
     else:
         assert not (FUSED & names), (c["name"], mode, sorted(names))
+        assert "fused" not in _route(c), (c["name"], mode, sorted(_route(c)))
 
 
 # ---- 1. padded layout, both modes -----------------------------------------------------------------------------------------------------
@@ -219,8 +231,10 @@ def test_runtime_shape_twin_of_the_specialised_instantiation(name, monkeypatch):
     c = _coef_case(name) if name in SR.COEF_CASES else SR.case(name)
     assert (c["F"], c["T"]) == (34, 60)
     spec, names_s = _run(c, "bf16x3")
+    assert {"fused", "rt3", "specialised"} <= _route(c)
     monkeypatch.setenv("RD_K1_SPECIALIZE", "0")
     twin, names_t = _run(c, "bf16x3")
+    assert {"fused", "rt3"} <= _route(c) and "specialised" not in _route(c)
     assert FUSED <= names_s and FUSED <= names_t
     _compare("specialised", c, "bf16x3", spec)
     _compare("runtime-shape", c, "bf16x3", twin)
