@@ -398,11 +398,16 @@ int rd_masked_mean_bwd(const rd_shape* s, int32_t D, const float* dout, int32_t 
  *   _ema: an exponential moving average of the parameters is kept by the same launch (`ema`, `ema_cell`).
  * The three cells are 64 bytes, 16-byte aligned, eight doubles each; a launch never reads a word another workgroup of the same
  * launch writes, and a value the caller may change between replays (lr, the threshold, the decay) is an 8-byte copy, not a new capture.
- *   `state` {t, beta1^t, beta2^t, lr, 0, weight_decay, 0, 0} OF THE STEP BEING APPLIED; the update only reads it.  It is advanced once
- *     per step by an EARLIER launch: rd_adam_state_advance (one thread: t += 1, beta^t *= beta), or -- no extra launch -- by the
- *     step's first launch: rd_set_adam_state registers the cell on this host thread and rd_step_begin (enqueued while it is
- *     registered) advances it next to the dropout seed bump.  Initialise {steps taken so far, beta1^t, beta2^t, lr, 0, wd, 0, 0}.
- *     (A learning-rate schedule, code/Raindrop.py:257-259, writes slot 3.)
+ *   `state` {t, beta1^t, beta2^t, lr, base lr, weight_decay, n, 0} OF THE STEP BEING APPLIED; the update only reads it (slots 0-3 and
+ *     5).  It is advanced once per step by an EARLIER launch: rd_adam_state_advance (one thread: t += 1, beta^t *= beta), or -- no
+ *     extra launch -- by the step's first launch: rd_set_adam_state registers the cell on this host thread and rd_step_begin
+ *     (enqueued while it is registered) advances it next to the dropout seed bump.  Initialise {steps taken so far, beta1^t,
+ *     beta2^t, lr, 0, wd, 0, 0}.  (A per-epoch schedule, code/Raindrop.py:257-259, writes slot 3.)
+ *     Per-step schedule: slot 6 = n > 0 makes the state 8 + capacity doubles (n <= capacity), a table of factors f[0 .. n) from
+ *     double 8 on; the advancing thread then also writes slot 3 = slot 4 * f[min(t - 1, n - 1)] with the t it has just formed (one
+ *     double product; the last factor holds past the end; a step the non-finite guard skips still moves the position).  With
+ *     n == 0 -- the eight-double state above -- slot 3 is the caller's and slot 4 is not read.  The C entry points take no length:
+ *     a caller that sets n > 0 guarantees the 8 + n doubles (raindrop_amd.optim.FlatAdam checks it on the host).
  *   `clip` {max_norm, last_norm, last_scale, skipped, clipped, 0, 0, 0}: slot 0 is read by the launch and written by the caller only
  *     (+inf: guard without clipping); slots 1-4 are written by one thread of the launch -- the norm and the scale it applied (0 when
  *     it skipped) and two running counts of skipped / clipped steps.

@@ -96,10 +96,21 @@ __device__ __forceinline__ void load_uniform_2xi32(const int32_t* p, const int32
   asm volatile("s_load_dword %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(x), "=&s"(y) : "s"(p), "s"(q) : "memory");
 }
 
-// Device-side Adam step state (rd_optim.hip): {t, beta1^t, beta2^t, lr, -, weight_decay, -, -}; one thread advances it once per step
-// in a launch that precedes the update (rd_adam_state_advance, or the plan workgroup of rd_step_begin).
+// Device-side Adam step state (rd_optim.hip): {t, beta1^t, beta2^t, lr, base lr, weight_decay, n, -}; one thread advances it once per
+// step in a launch that precedes the update (rd_adam_state_advance, or the plan workgroup of rd_step_begin).
+// Learning-rate schedule: slot 6 is n, the number of entries of a table of factors f[0 .. n) that starts at double 8 (the cell is
+// then 8 + capacity doubles, n <= capacity: the caller's to guarantee, raindrop_amd.optim.FlatAdam does).  n > 0: the thread that
+// forms t also forms the rate of step t, lr = base * f[min(t - 1, n - 1)] -- one double product, rounded once; past the end of the
+// table the last factor holds.  n == 0 (the eight-double cell of a caller without a schedule): one more load and one uniform
+// branch in this one thread, slot 3 stays the caller's.  A step the non-finite guard skips has advanced t, and so the position.
 __device__ __forceinline__ void adam_state_advance(double* st, float b1, float b2) {
-  st[0] += 1.0; st[1] *= (double)b1; st[2] *= (double)b2;
+  const double t = st[0] + 1.0;
+  st[0] = t; st[1] *= (double)b1; st[2] *= (double)b2;
+  const double n = st[6];
+  if (n > 0.0) {                                                     // (false for a NaN as well)
+    const double k = fmax(fmin(t - 1.0, n - 1.0), 0.0);              // never in front of the table, whatever t holds
+    st[3] = st[4] * st[8 + (long)k];
+  }
 }
 // the cell registered by rd_set_adam_state on this host thread (nullptr: none); read when rd_step_begin is ENQUEUED
 struct AdamCellReg { double* state; float b1, b2; };

@@ -12,7 +12,7 @@ namespace rd {
 namespace {
 
 // (the device step state: the comment in front of k_adam_dev)
-struct AdamState { double t, p1, p2, lr, pad0, wd, pad1, pad2; };
+struct AdamState { double t, p1, p2, lr, base_lr, wd, sched_n, pad2; };        // (base_lr, sched_n and the table behind the eight: the advance's alone)
 // ---- exponential moving average of the weights (DESIGN.md "Weight averaging") ------------------------------------------------------
 // ema[i] += c_t (p_new[i] - ema[i]) in the thread that holds p_new in a register: one more flat buffer read and written by the update's
 // own launch, no launch of its own.  A template flag of the four update kernels (rule 40): the EMA = false instantiations are the
@@ -131,15 +131,18 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
 }
 
 // The same update with the optimizer's step state on the DEVICE: a captured launch cannot carry the host's bias corrections (they
-// change every step).  The state is eight doubles {t, beta1^t, beta2^t, lr, -, weight_decay, -, -} holding the values OF THE STEP
-// BEING APPLIED; this kernel only READS it.  The state is advanced -- t += 1, beta^t *= beta -- by an earlier launch of the same
+// change every step).  The state is eight doubles {t, beta1^t, beta2^t, lr, base lr, weight_decay, n, -} holding the values OF THE STEP
+// BEING APPLIED; this kernel only READS it (t, beta^t, lr, weight_decay).  The state is advanced -- t += 1, beta^t *= beta -- by an earlier launch of the same
 // step: the step's first launch where there is one (rd_set_adam_state registers the cell, rd_step_begin's plan workgroup does it
 // next to the dropout seed bump), else rd_adam_state_advance (one thread).  Rounds 5's form advanced a second slot from workgroup 0
 // of THIS launch: workgroups dispatched after that store became visible applied step t + 2's corrections (a race wherever the grid
 // does not fit the device in one round).  Round 6's first fix -- an arrival ticket, the last workgroup advances -- was
 // race-free and cost 4.5 us per step (profiles/r06_adam_ticket_vs_begin.txt: 9.85 against 5.4 us: every workgroup waits for the
 // return of a device-scope atomic on ONE line, the last one for a fence and a second atomic on top).
-// lr and weight_decay live in the cell too: a learning-rate schedule is an 8-byte copy, not a new capture.
+// lr and weight_decay live in the cell too: a new rate is an 8-byte copy, not a new capture.  A PER-STEP schedule needs no copy at
+// all: with n = slot 6 > 0 the cell goes on behind the eight doubles with a table of n factors, and the advancing thread -- the one
+// that forms t -- also writes lr = base lr (slot 4) * f[min(t - 1, n - 1)] into slot 3 (adam_state_advance, rd_common.h): the
+// sixteen update kernels read state->lr as before, no launch and no argument is added.  n == 0: slot 3 is the caller's.
 // (beta^t by repeated multiplication differs from pow() by ~t 2^-53 relative: far below the float the correction is rounded to.)
 template <bool EMA>
 __global__ __launch_bounds__(256) void k_adam_dev(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

@@ -114,6 +114,165 @@ def no_decay(layout):
     return dict(match=[n for n, p in zip(layout.names, layout.params) if p.dim() <= 1], weight_decay=0.0)
 
 
+class LRSchedule:
+    """A per-step learning-rate schedule as a TABLE of factors: step t (1-based) of an optimizer with base rate `lr` uses
+    `lr * f[min(t - 1, n - 1)]` -- past the end the last factor holds.  An immutable float64 vector of finite, non-negative entries,
+    length >= 1.  `FlatAdam(schedule=...)` keeps the table on the device, behind its step state, where the thread that forms the step
+    number also forms the rate: no host work per step, inside a whole-step hipGraph too.  A table, not a formula: it is exact (the rate
+    is ONE double product, the one `torch.optim.lr_scheduler.LambdaLR` forms from the same factor) and any schedule fits in it, at 8
+    bytes per step.  The builders state their formulas with k = t - 1, the 0-based index."""
+
+    __slots__ = ("_f",)
+
+    def __init__(self, factors):
+        if isinstance(factors, LRSchedule):
+            f = factors._f
+        else:
+            if isinstance(factors, torch.Tensor):
+                factors = factors.detach().cpu().flatten().tolist()
+            try:
+                f = tuple(factors)
+            except TypeError:
+                raise ValueError("LRSchedule: a sequence of factors, got %r" % (factors,))
+            for x in f:
+                if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0.0 <= x < math.inf:          # NaN fails the comparison
+                    raise ValueError("LRSchedule: every factor must be a finite number >= 0, got %r" % (x,))
+            f = tuple(float(x) for x in f)
+        if len(f) < 1:
+            raise ValueError("LRSchedule: at least one factor")
+        object.__setattr__(self, "_f", f)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("LRSchedule is immutable")
+
+    def __len__(self):
+        return len(self._f)
+
+    def __getitem__(self, k):
+        return self._f[k]
+
+    def __iter__(self):
+        return iter(self._f)
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self._f == other._f
+
+    def __hash__(self):
+        return hash(self._f)
+
+    def __repr__(self):
+        return "LRSchedule(%d factors: %s%s)" % (len(self._f), ", ".join("%g" % x for x in self._f[:4]), ", ..." if len(self._f) > 4 else "")
+
+    @property
+    def factors(self):
+        """the factors as a tuple of Python floats (doubles)"""
+        return self._f
+
+    def factor(self, t):
+        """the factor of step t (1-based; t < 1 reads the first entry)"""
+        return self._f[min(max(int(t) - 1, 0), len(self._f) - 1)]
+
+    def tensor(self):
+        """a fresh float64 CPU tensor of the factors"""
+        return torch.tensor(self._f, dtype=torch.float64)
+
+    @staticmethod
+    def _count(what, x, least=1):
+        if isinstance(x, bool) or not isinstance(x, int) or x < least:
+            raise ValueError("%s must be an integer >= %d, got %r" % (what, least, x))
+        return x
+
+    @classmethod
+    def linear_warmup(cls, warmup, start=0.0):
+        """`warmup` entries: f[k] = start + (1 - start) (k + 1) / warmup for k < warmup - 1, f[warmup - 1] = 1 (which then holds)"""
+        cls._count("warmup", warmup)
+        start = _check_group_value("start", start)
+        return cls([1.0 if k + 1 >= warmup else start + (1.0 - start) * (k + 1) / warmup for k in range(warmup)])
+
+    @classmethod
+    def warmup_cosine(cls, total, warmup=0, min_factor=0.0):
+        """`total` entries: f[k] = (k + 1) / warmup for k < warmup, then min_factor + (1 - min_factor) (1 + cos(pi x)) / 2 with
+        x = (k - warmup) / max(1, total - 1 - warmup): 1 at k = warmup, min_factor at the last entry (which then holds)"""
+        cls._count("total", total)
+        cls._count("warmup", warmup, 0)
+        if warmup >= total:
+            raise ValueError("warmup_cosine: warmup (%d) must be less than total (%d)" % (warmup, total))
+        lo = _check_group_value("min_factor", min_factor)
+        span = max(1, total - 1 - warmup)
+        return cls([(k + 1) / warmup if k < warmup else lo + (1.0 - lo) * 0.5 * (1.0 + math.cos(math.pi * ((k - warmup) / span)))
+                    for k in range(total)])
+
+    @classmethod
+    def step_decay(cls, step_size, gamma, total):
+        """`total` entries: f[k] = gamma ** (k // step_size) (torch's StepLR in closed form)"""
+        cls._count("step_size", step_size)
+        cls._count("total", total)
+        gamma = _check_group_value("gamma", gamma)
+        return cls([gamma ** (k // step_size) for k in range(total)])
+
+    @classmethod
+    def one_cycle(cls, total, pct_start=0.3, div=25.0, final_div=1e4):
+        """`total` >= 2 entries, the RATE of torch's OneCycleLR (cosine annealing, two phases) with the base rate as its max_lr: from
+        1 / div up to 1 at k = u = pct_start total - 1, then down to 1 / (div final_div) at the last entry;
+        f = b + (a - b) (1 + cos(pi x)) / 2 from a to b, x = k / u in the first phase and (k - u) / (total - 1 - u) in the second.
+        (The momentum half of the policy is not here: beta1 is a launch argument.)"""
+        cls._count("total", total, 2)
+        if isinstance(pct_start, bool) or not isinstance(pct_start, float) or not 0.0 < pct_start < 1.0:
+            raise ValueError("pct_start must be a float in (0, 1), got %r" % (pct_start,))
+        for what, x in (("div", div), ("final_div", final_div)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not 1.0 <= x < math.inf:
+                raise ValueError("%s must be a finite number >= 1, got %r" % (what, x))
+        up_end, end = float(pct_start * total) - 1.0, float(total - 1)
+        first, last = 1.0 / div, 1.0 / div / final_div
+
+        def anneal(a, b, x):
+            return b + (a - b) / 2.0 * (math.cos(math.pi * x) + 1.0)
+        return cls([anneal(first, 1.0, k / up_end if up_end > 0.0 else 1.0) if k <= up_end else anneal(1.0, last, (k - up_end) / (end - up_end))
+                    for k in range(total)])
+
+    @classmethod
+    def from_lambda(cls, fn, total):
+        """f[k] = fn(k), k = 0 .. total - 1: the function one would hand to torch's LambdaLR"""
+        cls._count("total", total)
+        if not callable(fn):
+            raise ValueError("from_lambda: fn must be callable, got %r" % (fn,))
+        return cls([fn(k) for k in range(total)])
+
+    @classmethod
+    def from_torch(cls, make_scheduler, total):
+        """Any torch scheduler as a table: `make_scheduler(optimizer)` builds it on a dummy one-parameter CPU optimizer with lr = 1.0;
+        f[k] is the rate that optimizer's step k + 1 would use (the rate in front of the k-th `scheduler.step()`).  torch's chainable
+        schedulers form their rates recursively: at another base rate torch's own doubles can differ from base * f[k] in the last
+        bit."""
+        cls._count("total", total)
+        if not callable(make_scheduler):
+            raise ValueError("from_torch: make_scheduler must be callable (optimizer -> scheduler), got %r" % (make_scheduler,))
+        opt = torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=1.0)
+        sched = make_scheduler(opt)
+        rates = []
+        for k in range(total):
+            rates.append(float(opt.param_groups[0]["lr"]))
+            if k + 1 < total:
+                opt.step()
+                sched.step()
+        return cls(rates)
+
+
+def _check_schedule(schedule, capacity):
+    """(schedule, capacity) of FlatAdam's keywords: (None, None) is off; a capacity alone is the table {1.0} in that much room"""
+    if schedule is None and capacity is None:
+        return None, None
+    if schedule is None:
+        schedule = LRSchedule([1.0])
+    if not isinstance(schedule, LRSchedule):
+        raise ValueError("schedule must be None or an optim.LRSchedule, got %r" % (schedule,))
+    if capacity is None:
+        capacity = len(schedule)
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < len(schedule):
+        raise ValueError("schedule_capacity must be an integer >= the schedule's length (%d), got %r" % (len(schedule), capacity))
+    return schedule, capacity
+
+
 class FlatAdam:
     """Adam over the flat buffers; `step()` with host-computed bias corrections, `step_captured()` with the step state on the device.
 
@@ -156,16 +315,30 @@ class FlatAdam:
     GLOBAL norm over all groups, the step count and the average are shared.  `set_group(i, lr_scale=, weight_decay=)` is a copy of
     one 32-byte row, stream-ordered with the launches around it and not a new capture (lr_scale=0.0 holds a group still: its
     parameters keep their bits, its moments go on); assigning `weight_decay` re-resolves the rows of the groups that follow it at
-    the next `sync_cells`.  Switching the feature on or off is a new capture / another optimizer."""
+    the next `sync_cells`.  Switching the feature on or off is a new capture / another optimizer.
+
+    schedule, schedule_capacity (default None, None: off -- the eight-double step cell, `hyper()` and the `state_dict()` keys of an
+    optimizer built without the keywords): an `LRSchedule`, the rate of step t is `lr * f[min(t - 1, n - 1)]`.  `lr` stays the BASE
+    rate -- what the user and `trainer.ReduceOnPlateau` assign.  The table lives behind the device step state (8 + capacity doubles) and
+    the one thread that advances that state per step (rd_adam_state_advance, or the first launch of a whole-step hipGraph) also writes
+    the step's rate into the slot every update kernel reads: no launch, no argument and no host work per step is added, and the
+    feature combines with `max_grad_norm`, `ema_decay`, `groups` (every group scales the scheduled rate) and `decoupled` (the shrink
+    uses the scheduled rate, as torch's AdamW under a scheduler) with no code of their own.  `step()` passes the same double product
+    as its `lr` argument: the same bits.  A step the non-finite guard skips still moves the position (it moves `t`).  The capacity
+    (default: the schedule's length) is fixed for the optimizer's life -- a captured graph holds the cell's address --:
+    `set_schedule(s)` with len(s) <= capacity is one stream-ordered copy and not a new capture, a longer one raises,
+    `clear_schedule()` installs the table {1.0}.  `schedule_capacity` alone switches the feature on with that table.
+    `current_lr()` reads the device's rate back, `schedule_position()` is min(t, n)."""
 
     def __init__(self, flat_param, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
-                 ema_warmup=False, groups=None, decoupled=False):
+                 ema_warmup=False, groups=None, decoupled=False, schedule=None, schedule_capacity=None):
         if flat_param.grad is None:
             raise ValueError("flat_param.grad must be the flat gradient buffer")
         if groups is not None and not isinstance(groups, ParamGroups):
             raise ValueError("groups must be None or an optim.ParamGroups, got %r" % (groups,))
         self.groups, self.decoupled = groups, bool(decoupled)
         self.chunk_group = self.group_cell = None
+        self.schedule, self.schedule_capacity = _check_schedule(schedule, schedule_capacity)
         self.max_grad_norm = None if max_grad_norm is None else _check_max_grad_norm(max_grad_norm)
         self.clip_cell = self.clip_partial = None
         self.ema_decay = None if ema_decay is None else _check_ema_decay(ema_decay)
@@ -376,6 +549,59 @@ class FlatAdam:
         finally:
             self.swap_ema()
 
+    # ---- per-step learning-rate schedule (schedule, schedule_capacity) ----
+    def _schedule_on(self):
+        if self.schedule is None:
+            raise ValueError("the learning-rate schedule is off: construct FlatAdam with schedule or schedule_capacity (the step "
+                             "cell's size is fixed for the optimizer's life)")
+
+    def _step_lr(self):
+        """the rate of step `self.t` as the host forms pass it: the double product the device forms, or the base rate"""
+        return float(self.lr) if self.schedule is None else float(float(self.lr) * self.schedule.factor(self.t))
+
+    def _schedule_words(self):
+        """{n, 0, f[0 .. n)}: slots 6, 7 and the table, as one contiguous piece of the cell"""
+        return [float(len(self.schedule)), 0.0] + list(self.schedule.factors)
+
+    def set_schedule(self, schedule):
+        """Another table for the steps enqueued from here on, captured ones included (the position, `t`, stays): one copy into the step
+        cell, stream-ordered with the launches around it, not a new capture.  Raises for one longer than `schedule_capacity`."""
+        self._schedule_on()
+        if not isinstance(schedule, LRSchedule):
+            raise ValueError("set_schedule: an optim.LRSchedule, got %r" % (schedule,))
+        if len(schedule) > self.schedule_capacity:
+            raise ValueError("set_schedule: %d entries, the capacity is %d and fixed (a captured graph holds the cell's address): "
+                             "construct FlatAdam with a larger schedule_capacity" % (len(schedule), self.schedule_capacity))
+        self.schedule = schedule
+        if self.step_cell is not None:
+            words = self._schedule_words()
+            self.step_cell[6:6 + len(words)] = torch.tensor(words, dtype=torch.float64, device=self.step_cell.device)
+
+    def _check_step_cell(self, what):
+        """in front of a launch that advances the step state: the advancing thread trusts slot 6 (the C entry points take no
+        length), so the cell must be the 8 + capacity doubles made here and the table must fit -- whatever was assigned from outside"""
+        words = 8 + (self.schedule_capacity or 0)
+        if self.step_cell.numel() != words or self.step_cell.dtype != torch.float64 or \
+                (self.schedule is not None and not (isinstance(self.schedule, LRSchedule) and len(self.schedule) <= self.schedule_capacity)):
+            raise _lib.RaindropHipError("%s: the step cell must hold %d doubles and a schedule of at most %s entries (use set_schedule)"
+                                        % (what, words, self.schedule_capacity))
+
+    def clear_schedule(self):
+        """the table {1.0}: every step from here on uses the base rate (the feature, and the cell, stay)"""
+        self.set_schedule(LRSchedule([1.0]))
+
+    def current_lr(self):
+        """the rate of the last step applied (before any: of the first): slot 3 of the device step state, one device-to-host copy (it
+        waits for the stream) -- or, while host-form steps have left that state behind, the product `step()` passed"""
+        if self.step_cell is None or self._cell_stale:
+            return self._step_lr()
+        return float(self.step_cell[3])
+
+    def schedule_position(self):
+        """entries of the table consumed so far: min(t, n)"""
+        self._schedule_on()
+        return min(int(self.t), len(self.schedule))
+
     def _enqueue_update(self, dev):
         """The update's launches -- the ONE place that names the sixteen entry points: rd_adam_step [_clip] [_ema] [_grp] [_dev], behind
         rd_grad_sumsq when clipping is on.  dev: the step state is read from the device cell, else `lr`, `weight_decay` and `t` of
@@ -386,7 +612,7 @@ class FlatAdam:
         if dev:
             args += (float(self.betas[0]), float(self.betas[1]), float(self.eps), ops._ptr(self.step_cell))
         else:
-            args += (float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
+            args += (self._step_lr(), float(self.betas[0]), float(self.betas[1]), float(self.eps), float(self.weight_decay), self.t)
         tail = (self._ema_args() if ema else ()) + (self._group_args() if grp else ())
         if clip:                             # the norm's partial sums, then the clipping instantiation of the update
             partial, nbytes, cell = self._clip_args()
@@ -413,6 +639,7 @@ class FlatAdam:
         self.check_can_step("FlatAdam.step_captured")
         self.sync_step_cell(create_only=True)
         if advance:
+            self._check_step_cell("FlatAdam.step_captured")
             _lib.call("rd_adam_state_advance", ops._ptr(self.step_cell), float(self.betas[0]), float(self.betas[1]), ops._stream())
         self._enqueue_update(dev=True)
 
@@ -434,30 +661,40 @@ class FlatAdam:
         """(Un)register the device step state with this host thread's next rd_step_begin launches (include/raindrop_hip.h
         rd_set_adam_state): the step's first launch then advances it."""
         self.sync_step_cell(create_only=True)
+        if on:
+            self._check_step_cell("FlatAdam.register_cell")
         _lib.call("rd_set_adam_state", ops._ptr(self.step_cell) if on else None, float(self.betas[0]), float(self.betas[1]))
 
     def sync_step_cell(self, create_only=False):
         """Make the device step state agree with `self.t`, `self.lr`, `self.weight_decay` (before capturing, after load_state_dict,
         after eager steps).  Layout (include/raindrop_hip.h rd_adam_step_dev): {t, beta1^t, beta2^t, lr, 0, wd, 0, 0} with t = steps TAKEN (the step's
-        advance launch moves it to the step being applied)."""
+        advance launch moves it to the step being applied).  With a schedule: {t, beta1^t, beta2^t, lr of step t, base lr, wd, n, 0}
+        and the table behind it, 8 + capacity doubles in all (the entries behind n are 0 and never read)."""
         fresh = getattr(self, "step_cell", None) is None
         if fresh:
-            self.step_cell = torch.zeros((8,), dtype=torch.float64, device=self.param.device)
+            self.step_cell = torch.zeros((8 + (self.schedule_capacity or 0),), dtype=torch.float64, device=self.param.device)
         if fresh or not create_only:
             # beta^t of the betas AS THE KERNELS SEE THEM (float arguments widened to double: rd_adam_step's pow() and the device's
             # running product both start from those) -- 0.999 as a double instead of 0.999f moves 1 - beta2^t by 1e-5 relative
             t = float(self.t)
             b1, b2 = (ctypes.c_float(float(b)).value for b in self.betas)
-            self.step_cell.copy_(torch.tensor([t, b1 ** t, b2 ** t, float(self.lr), 0.0, float(self.weight_decay), 0.0, 0.0],
-                                              dtype=torch.float64))
+            if self.schedule is None:
+                words = [t, b1 ** t, b2 ** t, float(self.lr), 0.0, float(self.weight_decay), 0.0, 0.0]
+            else:
+                words = [t, b1 ** t, b2 ** t, self._step_lr(), float(self.lr), float(self.weight_decay)] + self._schedule_words()
+                words += [0.0] * (8 + self.schedule_capacity - len(words))
+            self.step_cell.copy_(torch.tensor(words, dtype=torch.float64))
             self._cell_hyper = self.cell_hyper()
 
     def sync_cell_hyper(self):
         """lr / weight decay changed on the host (ReduceLROnPlateau, a warm-up or cosine schedule): two 8-byte cells, stream-ordered
-        with the replays around it."""
+        with the replays around it.  With a schedule `lr` is the BASE rate: slot 4, which the next advance multiplies into slot 3."""
         if self.step_cell is not None and getattr(self, "_cell_hyper", None) != self.cell_hyper():
-            self.step_cell[3:6:2] = torch.tensor([float(self.lr), float(self.weight_decay)], dtype=torch.float64,
-                                                 device=self.step_cell.device)
+            vals = torch.tensor([float(self.lr), float(self.weight_decay)], dtype=torch.float64, device=self.step_cell.device)
+            if self.schedule is None:
+                self.step_cell[3:6:2] = vals
+            else:
+                self.step_cell[4:6] = vals
             self._cell_hyper = self.cell_hyper()
 
     def device_steps(self):
@@ -486,15 +723,29 @@ class FlatAdam:
             sd.update(decoupled=self.decoupled,
                       groups=[dict(names=None if names[i] is None else list(names[i]), lr_scale=self._group_lr_scale[i], weight_decay=wd)
                               for i, wd in enumerate(self._group_wd)])
+        if self.schedule is not None:        # (off: the keys of an optimizer without the keywords)
+            sd.update(schedule=list(self.schedule.factors), schedule_capacity=self.schedule_capacity)
         return sd
 
     def load_state_dict(self, sd):
         """In place (the moment buffers and `ema` keep their addresses: a captured step stays valid); the device step state follows
         at the next captured step.  A dictionary without the `ema` keys leaves the average and its settings as they are; so does
         one without `groups` / `decoupled`.  One whose groups partition the parameters differently than this optimizer's (which
-        includes one with groups into an optimizer without) raises before anything is changed: the chunk map is part of a capture."""
+        includes one with groups into an optimizer without) raises before anything is changed: the chunk map is part of a capture.
+        A dictionary with a `schedule` into an optimizer without one, one without into an optimizer with one, and a schedule longer
+        than this optimizer's capacity raise before anything is changed as well: the step cell's size is part of a capture.  The
+        schedule is restored in place; `t` travels, so the run goes on at the entry it had reached."""
         if self.ema_swapped:
             raise _lib.RaindropHipError("FlatAdam.load_state_dict: the parameters are exchanged with their average: swap back first")
+        if ("schedule" in sd) != (self.schedule is not None):
+            raise ValueError("FlatAdam.load_state_dict: the dictionary %s a learning-rate schedule, this optimizer %s: construct "
+                             "FlatAdam with%s schedule / schedule_capacity"
+                             % (("holds", "was built without one", "") if "schedule" in sd else ("holds no", "has one", "out")))
+        if "schedule" in sd:
+            schedule = LRSchedule(sd["schedule"])
+            if len(schedule) > self.schedule_capacity:
+                raise ValueError("FlatAdam.load_state_dict: a schedule of %d entries, the capacity is %d and fixed"
+                                 % (len(schedule), self.schedule_capacity))
         if "groups" in sd:
             mine = None if self.group_cell is None else (self.groups.partition() if self.groups is not None else (None,))
             theirs = tuple(None if g["names"] is None else tuple(g["names"]) for g in sd["groups"])
@@ -507,6 +758,8 @@ class FlatAdam:
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.t = int(sd["t"])
         self.lr, self.betas, self.eps, self.weight_decay = sd["lr"], tuple(sd["betas"]), sd["eps"], sd["weight_decay"]
+        if "schedule" in sd:                 # (the table reaches the device with the rest of the step state: sync_cells)
+            self.schedule = schedule
         self._cell_stale = True
         if "max_grad_norm" in sd:            # (a dictionary from before the keyword leaves the setting and the counts as they are)
             mgn = sd["max_grad_norm"]

@@ -61,8 +61,20 @@ class ReduceOnPlateau:
         return float(self.opt.lr)
 
 
-def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False):
+def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
+                    warmup_steps=0):
     """what can be refused without a device"""
+    if isinstance(lr_schedule, str):
+        if lr_schedule != "warmup_cosine":
+            raise ValueError("lr_schedule: the only named schedule is 'warmup_cosine', got %r" % (lr_schedule,))
+    elif lr_schedule is not None and not isinstance(lr_schedule, optim_mod.LRSchedule) and not callable(lr_schedule):
+        raise ValueError("lr_schedule must be None, an optim.LRSchedule, 'warmup_cosine' or a callable total_steps -> LRSchedule, got %r"
+                         % (lr_schedule,))
+    if isinstance(warmup_steps, bool) or not isinstance(warmup_steps, int) or warmup_steps < 0:
+        raise ValueError("warmup_steps must be a non-negative integer, got %r" % (warmup_steps,))
+    if warmup_steps and lr_schedule != "warmup_cosine":
+        raise ValueError("warmup_steps belongs to lr_schedule='warmup_cosine' (another schedule carries its own warm-up), got %r with %r"
+                         % (warmup_steps, lr_schedule))
     if not isinstance(decoupled_weight_decay, bool):
         raise ValueError("decoupled_weight_decay must be True or False, got %r" % (decoupled_weight_decay,))
     if isinstance(param_groups, str):
@@ -92,6 +104,22 @@ def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups
             raise _lib.RaindropHipError("fit: %s carries no labels (DeviceDataset(..., y=...))" % name)
 
 
+def _resolve_schedule(lr_schedule, warmup_steps, total_steps):
+    """fit's `lr_schedule` as an LRSchedule for `total_steps` steps (None: none, also for a run of no steps)"""
+    if lr_schedule is None or total_steps <= 0:
+        return None
+    if isinstance(lr_schedule, optim_mod.LRSchedule):
+        return lr_schedule
+    if lr_schedule == "warmup_cosine":
+        if warmup_steps >= total_steps:
+            raise ValueError("warmup_steps (%d) must be less than the run's %d steps" % (warmup_steps, total_steps))
+        return optim_mod.LRSchedule.warmup_cosine(total_steps, warmup=warmup_steps)
+    made = lr_schedule(total_steps)
+    if not isinstance(made, optim_mod.LRSchedule):
+        raise ValueError("lr_schedule(%d) must return an optim.LRSchedule, got %r" % (total_steps, made))
+    return made
+
+
 def _live_names(model):
     from . import synth
     cfg = dict(static=bool(model.static), nlayers=len(model.transformer_encoder.layers))
@@ -100,7 +128,7 @@ def _live_names(model):
 
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
-        param_groups=None, decoupled_weight_decay=False):
+        param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -111,7 +139,10 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
       step and of the validation loss.  `param_groups` -- a list of `optim.ParamGroups` rules, `dict(match=..., lr_scale=1.0,
       weight_decay=None)`, or "no_decay" (`optim.no_decay`: biases and LayerNorm parameters without weight decay) -- and
       `decoupled_weight_decay` (AdamW) become the optimizer's `groups` / `decoupled`, built on the flat layout made here; the
-      scheduler still moves the one base rate every group scales.  The model is put into training mode to build the step (that is when dropout is read) and
+      scheduler still moves the one base rate every group scales.  `lr_schedule` -- an `optim.LRSchedule`, "warmup_cosine"
+      (`LRSchedule.warmup_cosine(total_steps, warmup=warmup_steps)`) or a callable total_steps -> LRSchedule, with total_steps =
+      epochs x the planner's batches per epoch -- becomes the optimizer's `schedule`: a per-step rate formed on the device inside
+      the captured step, `lr` (and the plateau scheduler) being the base rate it scales.  The model is put into training mode to build the step (that is when dropout is read) and
       gets its previous mode back at the end; evaluation runs with dropout off whatever the mode;
     * per epoch: `load_epoch`, `n_batches` x `run_full`, `feed.history()`; then `feed.validate(model, val_ds, transform=...)` (on the
       averaged weights, `validate_ema`, when `ema_decay` is set), the scheduler's step on `auprc` (:368) and, when `auroc` beats the
@@ -121,11 +152,12 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     scheduler: True = `ReduceOnPlateau` with the script's settings, False / None = a constant rate, or a `ReduceOnPlateau` of your own.
     Returns a dict of per-epoch lists -- `train_loss` (the float32 mean of the epoch's per-batch losses), `train_accuracy`, `lr` (the
     rate after the epoch's scheduler step), `val_auroc`, `val_auprc`, `val_loss`, `val_accuracy`, `val_precision`, `val_recall`,
-    `val_f1` -- plus `best_epoch` (None when no epoch's auroc exceeded 0) and `best_auroc`.
+    `val_f1` -- plus `best_epoch` (None when no epoch's auroc exceeded 0) and `best_auroc`; with `lr_schedule` also `lr_step`, the
+    device's rate after each epoch's last step (`lr` stays the base rate).
 
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
-    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay)
+    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -141,9 +173,10 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     groups = None
     if param_groups is not None:
         groups = optim_mod.ParamGroups(flat, [optim_mod.no_decay(flat)] if param_groups == "no_decay" else param_groups)
-    opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
-                   groups=groups, decoupled=decoupled_weight_decay)
     planner = feed_mod.EpochPlanner(train_ds.y.cpu().numpy(), batch_size=B, strategy=strategy, n_total=train_ds.N)
+    schedule = _resolve_schedule(lr_schedule, warmup_steps, int(epochs) * int(planner.n_batches))
+    opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
+                   groups=groups, decoupled=decoupled_weight_decay, schedule=schedule)
     fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1))
     P, Pstatic, Ptime, y, lengths = train_ds.batch(np.arange(B) % train_ds.N)          # valid contents for the step's checks
     batch = dict(src=P, static=Pstatic if model.static else None, times=Ptime, y=y, lengths=lengths)
@@ -155,6 +188,8 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     if sched is not None and sched.opt is None:
         sched.opt = opt
     out = {k: [] for k in ("train_loss", "train_accuracy", "lr") + tuple("val_" + f for f in VAL_FIELDS)}
+    if schedule is not None:
+        out["lr_step"] = []
     best, best_auroc, best_epoch = None, 0.0, None
     vkw = dict(transform=transform, class_weight=class_weight, label_smoothing=label_smoothing)
     try:
@@ -166,6 +201,8 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
             loss, correct = fd.history()
             out["train_loss"].append(float(loss.mean()) if loss.size else float("nan"))
             out["train_accuracy"].append(float(correct.sum()) / max(correct.size * B, 1))
+            if schedule is not None:
+                out["lr_step"].append(opt.current_lr())
             v = feed_mod.validate_ema(model, val_ds, opt, **vkw) if ema_decay is not None else feed_mod.validate(model, val_ds, **vkw)
             for f in VAL_FIELDS:
                 out["val_" + f].append(v[f])
