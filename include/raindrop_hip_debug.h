@@ -49,6 +49,13 @@ int rd_debug_encoder_route(const struct rd_shape* s, int32_t with_plan, uint32_t
  *    2 infer         the shape has a save-free forward                       5 wgrad_stream  generic: weight gradients by tile stream
  * and in bits 8-9 rt, the row tiles ceil(F / 16) of a fused call (0 otherwise).  Returns RD_OK or the error of a bad shape. */
 int rd_debug_sensor_route(const struct rd_shape* s, int32_t ldz, int32_t with_pe, int32_t with_coef, uint32_t* bits);
+/* The route one use_beta graph-operator call (rd_graph_beta_fwd* / _bwd*) of these dimensions takes (rd_graph_beta.hip beta_fwd_route /
+ * beta_bwd_route, the functions the launch sites call) at d_ob = 4, K = 4 T, under the RD_BETA_V1 / RD_BETA_LARGE settings of the
+ * moment; with_alpha: the backward gets an alpha cotangent; with_drop: p_drop > 0.  Needs no device.  Bit i of *bits:
+ *    0 fwd_lds   forward on the LDS-staged form, else the workspace form      2 stage_v   k_graph_beta_fwd2<true, .>: V staged in LDS
+ *    1 bwd_lds   backward on the LDS-staged form                              3 v1        the rounds 2-5 kernels
+ * and in bits 8-23 Tc, the steps per pass of an LDS-form backward (0 on the workspace form).  Returns RD_OK or the error of bad dims. */
+int rd_debug_graph_beta_route(int32_t B, int32_t N, int32_t T, int32_t E, int32_t with_alpha, int32_t with_drop, uint32_t* bits);
 
 #ifdef __cplusplus
 }

@@ -208,12 +208,15 @@ SIGNATURES = {
 DEBUG_SIGNATURES = {
     "rd_debug_encoder_route": (c_int32, [_SHP, c_int32, _P]),       # bits: ROUTE_BITS below
     "rd_debug_sensor_route": (c_int32, [_SHP, c_int32, c_int32, c_int32, _P]),      # ldz, with_pe, with_coef; bits: SENSOR_ROUTE_BITS below
+    "rd_debug_graph_beta_route": (c_int32, [c_int32] * 6 + [_P]),   # B, N, T, E, with_alpha, with_drop; bits: BETA_ROUTE_BITS below
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
               "afuse_fwd", "afuse_bwd", "lean", "infer", "plan_ok")
 # bit i of rd_debug_sensor_route's mask (csrc/rd_k1_route.h K1Route's flags, in declaration order); bits 8-9: the row-tile count rt
 SENSOR_ROUTE_BITS = ("fused", "specialised", "infer", "coef", "tiles", "wgrad_stream")
+# bit i of rd_debug_graph_beta_route's mask (csrc/rd_graph_beta.hip BetaFwdRoute / BetaBwdRoute); bits 8-23: the backward's chunk Tc
+BETA_ROUTE_BITS = ("fwd_lds", "bwd_lds", "stage_v", "v1")
 
 _lib = None
 

@@ -744,6 +744,35 @@ bool fits_lds(int N, int T, int E, bool bwd) {
   return lds_bytes(N, T, next_pow2(E > 1 ? E : 2), Kc, false) <= 160 * 1024;
 }
 
+// The launch path of one call, decided ONCE per direction: graph_beta_fwd / graph_beta_bwd launch what these return and
+// rd_debug_graph_beta_route (include/raindrop_hip_debug.h) reports it -- the launch log names k_graph_beta_fwd2 / _bwd2 whatever the
+// instantiation and the chunk.  lds: the LDS-staged form (else the workspace form, nothing below is set); v1: the rounds 2-5
+// kernels (RD_BETA_V1=1, K % 4 != 0, or a backward whose round 6 layout does not fit with one step per pass); bytes: dynamic LDS.
+struct BetaFwdRoute { bool lds = false, v1 = false, stage_v = false; int P2 = 0; size_t bytes = 0; };
+struct BetaBwdRoute { bool lds = false, v1 = false; int Tc = 0; size_t bytes = 0; };
+BetaFwdRoute beta_fwd_route(int N, int K, int T, int E, bool drop) {
+  BetaFwdRoute r;
+  if (!fits_lds(N, T, E, false)) return r;
+  const int Kk = (int)((double)E * 0.5), Kc = Kk > 0 ? Kk : 1;
+  r.lds = true; r.P2 = next_pow2(E > 1 ? E : 2);
+  r.v1 = beta_v1() || (K & 3) != 0;
+  if (r.v1) { r.bytes = lds_bytes(N, T, r.P2, Kc, false); return r; }
+  r.stage_v = lds2_fwd(N, T, K, r.P2, Kc, true, drop) <= 160 * 1024;
+  r.bytes = lds2_fwd(N, T, K, r.P2, Kc, r.stage_v, drop);
+  return r;
+}
+BetaBwdRoute beta_bwd_route(int N, int K, int T, int E, bool with_alpha, bool drop) {
+  BetaBwdRoute r;
+  if (!fits_lds(N, T, E, true)) return r;
+  const int Kk = (int)((double)E * 0.5), Kc = Kk > 0 ? Kk : 1;
+  r.lds = true;
+  // one step per pass always fits round 6's layout: N <= 64 and Kk <= 2048 bound it by ~125 KB with the keep-code plane and the alpha arrays
+  r.v1 = beta_v1() || (K & 3) != 0 || lds2_bwd(N, 1, Kc, with_alpha, drop) > 160 * 1024;
+  r.Tc = r.v1 ? bwd_chunk(N, T, Kc) : bwd2_chunk(N, T, Kc, with_alpha, drop);
+  r.bytes = r.v1 ? lds_bytes(N, r.Tc, 0, Kc, true) : lds2_bwd(N, r.Tc, Kc, with_alpha, drop);
+  return r;
+}
+
 }  // namespace
 }  // namespace rd
 
@@ -776,30 +805,21 @@ static int graph_beta_fwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_
   a.B = B; a.N = N; a.K = K; a.T = T; a.d = d_ob; a.E = E; a.Kk = rd_graph_beta_kept(E);
   if ((rc = set_dropout(a, p_drop, seed))) return rc;
   const bool drop = a.p_drop > 0.f;
-  if (!fits_lds(N, T, E, false)) return beta_large_fwd(a, workspace, workspace_bytes, (hipStream_t)stream);
-  const int P2 = next_pow2(E > 1 ? E : 2);
-  if (!beta_v1() && (K & 3) == 0 && drop) {                      // the same kernel, instantiated with the coefficient dropout
-    const int Kc = a.Kk > 0 ? a.Kk : 1;
-    const bool stage = lds2_fwd(N, T, K, P2, Kc, true, true) <= 160 * 1024;
-    const size_t lds2 = lds2_fwd(N, T, K, P2, Kc, stage, true);
-    RD_REQUIRE(lds2 <= 160 * 1024, "rd_graph_beta_fwd_dropout: %zu bytes of LDS", lds2);   // (cannot happen where fits_lds holds)
-    if (stage) { RD_LDS_ATTR((k_graph_beta_fwd2<true, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
-    else { RD_LDS_ATTR((k_graph_beta_fwd2<false, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
+  const BetaFwdRoute r = beta_fwd_route(N, K, T, E, drop);
+  if (!r.lds) return beta_large_fwd(a, workspace, workspace_bytes, (hipStream_t)stream);
+  const int P2 = r.P2;
+  if (drop && r.v1 && !beta_v1()) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: K = %d is not a multiple of 4", K);   // (d_ob == 4: cannot happen)
+  if (drop && r.v1) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: the rounds 2-5 kernels (RD_BETA_V1=1) have no coefficient dropout");
+  if (!r.v1) {                                                   // round 6: 16 waves, every (edge, step) quantity once; the same bits
+    RD_REQUIRE(r.bytes <= 160 * 1024, "rd_graph_beta_fwd: %zu bytes of LDS", r.bytes);     // (cannot happen where fits_lds holds)
+    if (r.stage_v && drop) { RD_LDS_ATTR((k_graph_beta_fwd2<true, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, true>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, P2); }
+    else if (drop) { RD_LDS_ATTR((k_graph_beta_fwd2<false, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, true>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, P2); }
+    else if (r.stage_v) { RD_LDS_ATTR((k_graph_beta_fwd2<true, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, false>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, P2); }
+    else { RD_LDS_ATTR((k_graph_beta_fwd2<false, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, false>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, P2); }
     return check_launch("k_graph_beta_fwd2");
   }
-  if (drop && !beta_v1()) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: K = %d is not a multiple of 4", K);   // (d_ob == 4: cannot happen)
-  if (drop) return fail(RD_EUNSUPPORTED, "rd_graph_beta_fwd_dropout: the rounds 2-5 kernels (RD_BETA_V1=1) have no coefficient dropout");
-  if (!beta_v1() && (K & 3) == 0) {                              // round 6: 16 waves, every (edge, step) quantity once; the same bits
-    const int Kc = a.Kk > 0 ? a.Kk : 1;
-    const bool stage = lds2_fwd(N, T, K, P2, Kc, true) <= 160 * 1024;
-    const size_t lds2 = lds2_fwd(N, T, K, P2, Kc, stage);
-    if (stage) { RD_LDS_ATTR((k_graph_beta_fwd2<true, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<true, false>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
-    else { RD_LDS_ATTR((k_graph_beta_fwd2<false, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_fwd2<false, false>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, P2); }
-    return check_launch("k_graph_beta_fwd2");
-  }
-  const size_t lds = lds_bytes(N, T, P2, a.Kk > 0 ? a.Kk : 1, false);
   RD_LDS_ATTR(k_graph_beta_fwd, 160 * 1024);
-  hipLaunchKernelGGL(k_graph_beta_fwd, dim3(B), dim3(GB_THR), lds, (hipStream_t)stream, a, P2);
+  hipLaunchKernelGGL(k_graph_beta_fwd, dim3(B), dim3(GB_THR), r.bytes, (hipStream_t)stream, a, P2);
   return check_launch("k_graph_beta_fwd");
 }
 
@@ -850,42 +870,24 @@ static int graph_beta_bwd(int32_t B, int32_t N, int32_t K, int32_t T, int32_t d_
   a.dout = dout; a.dV = dV; a.dH = dH; a.dmap_part = dmap_part; a.dw = dw; a.dalpha = dalpha;
   a.B = B; a.N = N; a.K = K; a.T = T; a.d = d_ob; a.E = E; a.Kk = rd_graph_beta_kept(E);
   if ((rc = set_dropout(a, p_drop, seed))) return rc;
-  if (!fits_lds(N, T, E, true)) return beta_large_bwd(a, workspace, workspace_bytes, (hipStream_t)stream);
-  const int Kc = a.Kk > 0 ? a.Kk : 1;
-  const bool al = dalpha != nullptr;
-  if (a.p_drop > 0.f) {
+  const bool al = dalpha != nullptr, drop = a.p_drop > 0.f;
+  const BetaBwdRoute r = beta_bwd_route(N, K, T, E, al, drop);
+  if (!r.lds) return beta_large_bwd(a, workspace, workspace_bytes, (hipStream_t)stream);
+  if (drop && r.v1) {
     if (beta_v1()) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: the rounds 2-5 kernels (RD_BETA_V1=1) have no coefficient dropout");
     if ((K & 3) != 0) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: K = %d is not a multiple of 4", K);   // (d_ob == 4: cannot happen)
-    // one step per pass always fits: N <= 64 and Kk <= 2048 bound the layout by ~125 KB with the keep-code plane and the alpha arrays
-    if (lds2_bwd(N, 1, Kc, al, true) > 160 * 1024)
-      return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: %zu bytes of LDS for one step per pass", lds2_bwd(N, 1, Kc, al, true));
-    const int Tc2 = bwd2_chunk(N, T, Kc, al, true);
-    const size_t lds2 = lds2_bwd(N, Tc2, Kc, al, true);
-    if (al) {
-      RD_LDS_ATTR((k_graph_beta_bwd2<true, true>), 160 * 1024);
-      hipLaunchKernelGGL((k_graph_beta_bwd2<true, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, Tc2);
-    } else {
-      RD_LDS_ATTR((k_graph_beta_bwd2<false, true>), 160 * 1024);
-      hipLaunchKernelGGL((k_graph_beta_bwd2<false, true>), dim3(B), dim3(GB2_THR), lds2, (hipStream_t)stream, a, Tc2);
-    }
-    return check_launch("k_graph_beta_bwd2");
+    return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_dropout: more than 160 KB of LDS for one step per pass");
   }
-  if (!beta_v1() && (K & 3) == 0 && lds2_bwd(N, 1, Kc, al) <= 160 * 1024) {
-    const int Tc2 = bwd2_chunk(N, T, Kc, al);
-    if (al) {
-      RD_LDS_ATTR((k_graph_beta_bwd2<true, false>), 160 * 1024);
-      hipLaunchKernelGGL((k_graph_beta_bwd2<true, false>), dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc, true), (hipStream_t)stream, a, Tc2);
-    } else {
-      RD_LDS_ATTR((k_graph_beta_bwd2<false, false>), 160 * 1024);
-      hipLaunchKernelGGL((k_graph_beta_bwd2<false, false>), dim3(B), dim3(GB2_THR), lds2_bwd(N, Tc2, Kc), (hipStream_t)stream, a, Tc2);
-    }
+  if (!r.v1) {
+    if (al && drop) { RD_LDS_ATTR((k_graph_beta_bwd2<true, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_bwd2<true, true>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, r.Tc); }
+    else if (drop) { RD_LDS_ATTR((k_graph_beta_bwd2<false, true>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_bwd2<false, true>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, r.Tc); }
+    else if (al) { RD_LDS_ATTR((k_graph_beta_bwd2<true, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_bwd2<true, false>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, r.Tc); }
+    else { RD_LDS_ATTR((k_graph_beta_bwd2<false, false>), 160 * 1024); hipLaunchKernelGGL((k_graph_beta_bwd2<false, false>), dim3(B), dim3(GB2_THR), r.bytes, (hipStream_t)stream, a, r.Tc); }
     return check_launch("k_graph_beta_bwd2");
   }
   if (al) return fail(RD_EUNSUPPORTED, "rd_graph_beta_bwd_alpha: the rounds 2-5 kernels (RD_BETA_V1=1) take no alpha cotangent");
-  const int Tc = bwd_chunk(N, T, Kc);
-  const size_t lds = lds_bytes(N, Tc, 0, Kc, true);
   RD_LDS_ATTR(k_graph_beta_bwd, 160 * 1024);
-  hipLaunchKernelGGL(k_graph_beta_bwd, dim3(B), dim3(GB_THR), lds, (hipStream_t)stream, a, Tc);
+  hipLaunchKernelGGL(k_graph_beta_bwd, dim3(B), dim3(GB_THR), r.bytes, (hipStream_t)stream, a, r.Tc);
   return check_launch("k_graph_beta_bwd");
 }
 
@@ -917,6 +919,20 @@ extern "C" int rd_graph_beta_bwd_dropout(int32_t B, int32_t N, int32_t K, int32_
                                          void* workspace, size_t workspace_bytes, void* stream) {
   return graph_beta_bwd(B, N, K, T, d_ob, E, V, H, map_weights, p_t, pt_bstride, edge_index, row_stride, edge_weights, w_bstride,
                         beta_save, kept, dout, dalpha, dV, dH, dmap_part, dw, workspace, workspace_bytes, stream, p_drop, seed);
+}
+
+// include/raindrop_hip_debug.h: the routes above as bits; needs no device
+extern "C" int rd_debug_graph_beta_route(int32_t B, int32_t N, int32_t T, int32_t E, int32_t with_alpha, int32_t with_drop,
+                                         uint32_t* bits) {
+  RD_REQUIRE(bits, "NULL bits");
+  *bits = 0;
+  const int rc = check_beta(B, N, 4 * T, T, 4, E);
+  if (rc) return rc;
+  const BetaFwdRoute f = beta_fwd_route(N, 4 * T, T, E, with_drop != 0);
+  const BetaBwdRoute w = beta_bwd_route(N, 4 * T, T, E, with_alpha != 0, with_drop != 0);
+  const unsigned tc = w.lds ? (unsigned)(w.Tc < 0xFFFF ? w.Tc : 0xFFFF) : 0u;
+  *bits = (f.lds ? 1u : 0u) | (w.lds ? 2u : 0u) | (f.lds && f.stage_v ? 4u : 0u) | ((f.lds && f.v1) || (w.lds && w.v1) ? 8u : 0u) | (tc << 8);
+  return RD_OK;
 }
 
 extern "C" int rd_structure_distance(int32_t E, int32_t B, const float* alpha_all, float* workspace, float* distance,

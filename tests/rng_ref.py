@@ -126,3 +126,18 @@ def attn_keep(seed, site, bh, T, p):
     key = np.arange(T, dtype=np.int64)[None, None, None, :]
     quad, comp = attn_quad(bh, T, q, key)
     return keep_quad(seed, site, quad, comp, p)
+
+
+def edge_coeff_quad(B, E, T):
+    """int64 [B, E, T]: quad (b*E + e)*T + t of the use_beta branch's coefficient dropout, e the edge's id in the INPUT list (not
+    its position among the kept ones) -- rd_graph_beta.h beta_drop_base; the four uniforms of the quad are the d_ob = 4 channels."""
+    b = np.arange(B, dtype=np.int64)[:, None, None]
+    e = np.arange(E, dtype=np.int64)[None, :, None]
+    t = np.arange(T, dtype=np.int64)[None, None, :]
+    return (b * E + e) * T + t
+
+
+def edge_coeff_keep(seed, B, E, T, p):
+    """bool [B, E, T, 4]: channel c of (sample, input edge, step) is kept -- rd_graph_beta.h beta_keep_code at SITE_EDGE_COEFF: u >= p
+    in float32, what rd_graph_beta_keep writes as bytes."""
+    return uniform4(seed, SITE_EDGE_COEFF, edge_coeff_quad(B, E, T)) >= np.float32(p)
