@@ -56,6 +56,19 @@ int rd_debug_sensor_route(const struct rd_shape* s, int32_t ldz, int32_t with_pe
  *    1 bwd_lds   backward on the LDS-staged form                              3 v1        the rounds 2-5 kernels
  * and in bits 8-23 Tc, the steps per pass of an LDS-form backward (0 on the workspace form).  Returns RD_OK or the error of bad dims. */
 int rd_debug_graph_beta_route(int32_t B, int32_t N, int32_t T, int32_t E, int32_t with_alpha, int32_t with_drop, uint32_t* bits);
+/* The route one launch_gemm call takes (rd_gemm.hip gemm_check + gemm_route, the functions the launch calls) in the current arithmetic
+ * mode and switches, for a product C[M,N] = A[M,K] B[N,K]^T described by value: the four operand strides, the split-K plan, tile_hint
+ * and flags -- bit 0 a second problem (A2), 1 row sums, 2 batched, 3 scatter, 4 weight tiles given (Btiles), 5 A on a 16-byte
+ * boundary, 6 token plan for the scatter.  Needs no device.  Returns RD_OK or gemm_check's error.  The launch-log name goes to
+ * name[cap] ("" and all words 0 where nothing is launched: M or N <= 0), and
+ *    words[0]  bits 0-1 family (1 k_gemm, 2 k_gemm_bf16x3, 3 k_gemm_panel*), 2 akc, 3 bkc, 4 one_product, 5-6 map (0 XCD round-robin,
+ *              1 row-major, 2 split-K slice per XCD, 3 z grid), 8-11 npre, 12-15 tile (bf16x3: index into 64x64, 128x64, 128x128,
+ *              64x128, 64x160; panel: 0 small, 1 wide, 2 pc)
+ *    words[1..3]  the grid          words[4]  dynamic LDS bytes
+ * rd_debug_splitk_plan: the split of a weight-gradient product's reduction (splitk_plan): returns nsplit, *k_per_split the slice. */
+int rd_debug_gemm_route(int32_t M, int32_t N, int32_t K, int64_t sa_m, int64_t sa_k, int64_t sb_n, int64_t sb_k, int32_t nsplit,
+                        int32_t k_per_split, int32_t tile_hint, uint32_t flags, uint32_t* words, char* name, size_t cap);
+int rd_debug_splitk_plan(int64_t red, int32_t rows, int32_t cols, int32_t* k_per_split);
 
 #ifdef __cplusplus
 }

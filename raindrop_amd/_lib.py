@@ -209,6 +209,9 @@ DEBUG_SIGNATURES = {
     "rd_debug_encoder_route": (c_int32, [_SHP, c_int32, _P]),       # bits: ROUTE_BITS below
     "rd_debug_sensor_route": (c_int32, [_SHP, c_int32, c_int32, c_int32, _P]),      # ldz, with_pe, with_coef; bits: SENSOR_ROUTE_BITS below
     "rd_debug_graph_beta_route": (c_int32, [c_int32] * 6 + [_P]),   # B, N, T, E, with_alpha, with_drop; bits: BETA_ROUTE_BITS below
+    # M, N, K, sa_m, sa_k, sb_n, sb_k, nsplit, k_per_split, tile_hint, flags (GEMM_ROUTE_FLAGS), words[5], name, cap
+    "rd_debug_gemm_route": (c_int32, [c_int32] * 3 + [ctypes.c_int64] * 4 + [c_int32] * 3 + [ctypes.c_uint32, _P, _P, c_size_t]),
+    "rd_debug_splitk_plan": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P]),      # red, rows, cols, *k_per_split -> nsplit
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
@@ -217,6 +220,12 @@ ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", 
 SENSOR_ROUTE_BITS = ("fused", "specialised", "infer", "coef", "tiles", "wgrad_stream")
 # bit i of rd_debug_graph_beta_route's mask (csrc/rd_graph_beta.hip BetaFwdRoute / BetaBwdRoute); bits 8-23: the backward's chunk Tc
 BETA_ROUTE_BITS = ("fwd_lds", "bwd_lds", "stage_v", "v1")
+# bit i of rd_debug_gemm_route's flags; and what its words[0] packs (csrc/rd_gemm.hip GemmRoute)
+GEMM_ROUTE_FLAGS = ("second", "rowsum", "batched", "scatter", "btiles", "a_aligned", "plan")
+GEMM_FAMILIES = (None, "fp32", "bf16x3", "panel")
+GEMM_MAPS = ("xcd", "rowmajor", "slice_xcd", "zgrid")
+GEMM_TILES = ("64x64", "128x64", "128x128", "64x128", "64x160")
+GEMM_PANEL_FORMS = ("small", "wide", "pc")
 
 _lib = None
 

@@ -12,6 +12,7 @@
 // (one rounding per product, bitwise an fmaf chain), so results match a plain fp32 reference to
 // summation-order rounding.  Within each 16-wide K chunk lane l consumes k = 4*(l>>4)+j on MFMA
 // step j for BOTH operands, so each lane fetches its four k values with one ds_read_b128.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "rd_common.h"
@@ -641,53 +642,6 @@ __global__ __launch_bounds__(256) void k_gemm_bf16x3(GemmArgs g) {
   GSTAMP(3);
 }
 
-template <bool A_KC, bool B_KC, int MI, int NI, int NPRE>
-int launch_bf16x3_n(const GemmArgs& g, hipStream_t st) {
-  constexpr int TM = 32 * MI, TN = 32 * NI;
-  const size_t planes = (size_t)2 * (TM + TN) * LDB * sizeof(__bf16);
-  const size_t stage = (size_t)TM * (TN + 4) * sizeof(float);       // epilogue transpose tile (aliases the planes)
-  const size_t lds = (planes > stage ? planes : stage) + TN * sizeof(float);   // + bias
-  const int nz = g.nbatch > 1 ? g.nbatch : (g.nsplit > 1 ? g.nsplit : 1) * (g.A2 ? 2 : 1);
-  dim3 grid((g.nsplit > 1 ? cdiv(g.M, TM) : 8 * cdiv(cdiv(g.M, TM), 8)) * cdiv(g.N, TN), 1, nz);
-  if (g.slice_xcd) grid = dim3(8 * cdiv(nz, 8) * cdiv(g.M, TM) * cdiv(g.N, TN), 1, 1);
-  if (lds > 48 * 1024)
-    RD_LDS_ATTR((k_gemm_bf16x3<A_KC, B_KC, MI, NI, NPRE>), lds);
-  hipLaunchKernelGGL((k_gemm_bf16x3<A_KC, B_KC, MI, NI, NPRE>), grid, dim3(256), lds, st, g);
-  // One name per workgroup tile, form of the reduction loop and workgroup-to-tile map: the launch log tells RD_WGRAD_TILE,
-  // RD_GEMM_NPRE, RD_GEMM_XCD and RD_SPLITK_XCD apart by it.  The plain name is the default map of its kind (single pass: XCD
-  // round-robin; split-K: one reduction slice per XCD), "_rowmajor" / "_zgrid" the map with the switch off.
-  const int map = g.nsplit > 1 ? (g.slice_xcd ? 0 : 1) : (g.xcd_swizzle ? 0 : 2);
-  if (NPRE > 0)
-    return check_launch(map == 0 ? "k_gemm_bf16x3_64x64_npre" : map == 1 ? "k_gemm_bf16x3_64x64_npre_zgrid" : "k_gemm_bf16x3_64x64_npre_rowmajor");
-  if (MI == 2 && NI == 2)
-    return check_launch(map == 0 ? "k_gemm_bf16x3_64x64" : map == 1 ? "k_gemm_bf16x3_64x64_zgrid" : "k_gemm_bf16x3_64x64_rowmajor");
-  if (MI == 4 && NI == 2)
-    return check_launch(map == 0 ? "k_gemm_bf16x3_128x64" : map == 1 ? "k_gemm_bf16x3_128x64_zgrid" : "k_gemm_bf16x3_128x64_rowmajor");
-  if (MI == 4 && NI == 4)
-    return check_launch(map == 0 ? "k_gemm_bf16x3_128x128" : map == 1 ? "k_gemm_bf16x3_128x128_zgrid" : "k_gemm_bf16x3_128x128_rowmajor");
-  if (MI == 2 && NI == 4)
-    return check_launch(map == 0 ? "k_gemm_bf16x3_64x128" : map == 1 ? "k_gemm_bf16x3_64x128_zgrid" : "k_gemm_bf16x3_64x128_rowmajor");
-  return check_launch(map == 0 ? "k_gemm_bf16x3_64x160" : map == 1 ? "k_gemm_bf16x3_64x160_zgrid" : "k_gemm_bf16x3_64x160_rowmajor");
-}
-
-template <bool A_KC, bool B_KC, int MI, int NI>
-int launch_bf16x3(const GemmArgs& g, hipStream_t st) {
-  // Measured on MI355X (tools/gemm_timing.py, tools/bw_probe.py): requesting all K tiles up front
-  // (NPRE = tiles) is neutral at K=152 and 40 % slower at K=272 (register-limited occupancy), because
-  // these products are bound by operand RE-READS at the L2 level (each 64x64 tile loads 39+39 KB to
-  // write 16 KB), not by dependent latency; the looped form with one tile of lookahead stays.
-  // ... except for the handful-of-workgroups products of the classifier head (M = B = 256 rows: 12 workgroups, 3 K tiles):
-  // those are pure dependent-latency chains (measured 14-35 us for a 256 x 186 x 186 product), so the whole K range is
-  // requested up front.
-  static const bool npre_on = [] { const char* e = getenv("RD_GEMM_NPRE"); return !(e && atoi(e) == 0); }();
-  if (MI == 2 && NI == 2 && npre_on) {
-    const long blocks = (long)cdiv(g.M, 64) * cdiv(g.N, 64) * (g.nsplit > 1 ? g.nsplit : 1) * (g.A2 ? 2 : 1);
-    const int kspan = g.nsplit > 1 ? g.k_per_split : g.K;
-    if (blocks <= 128 && kspan <= 256) return launch_bf16x3_n<A_KC, B_KC, 2, 2, 4>(g, st);
-  }
-  return launch_bf16x3_n<A_KC, B_KC, MI, NI, 0>(g, st);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Panel product: C = epilogue(A W'), A [M,K] k-contiguous fp32, W' given as NATIVE operand tiles (k_wsplit, rd_rowgemm.hip:
 // [n tile][k tile][hi, lo][64 lanes][8] -- a B fragment is one contiguous KB per wave, straight from L2 into registers, no
@@ -960,12 +914,6 @@ __global__ __launch_bounds__(512) void k_gemm_panel_wide(GemmArgs g) {
   epilogue_t<RT / 2, NJ, 1, 8, 512>(g, reinterpret_cast<f32x4(&)[RT / 2][NJ]>(acc[RT / 2]), stage, bias_s, m0 + HM, n0, 0, wave, 0, tid, lane);
 }
 
-// the panel form applies: pre-split weight tiles given, A k-contiguous with 16-byte rows, one plain pass
-static bool panel_ok(const GemmArgs& g) {
-  static const bool on = [] { const char* e = getenv("RD_GEMM_PANEL"); return !(e && atoi(e) == 0); }();
-  return on && g.Btiles && g.sa_k == 1 && (g.sa_m & 3) == 0 && (reinterpret_cast<uintptr_t>(g.A) & 15) == 0 && g.nsplit <= 1 &&
-         g.nbatch <= 1 && !g.A2 && !g.rowsum && g.K >= 64;
-}
 // ------------------------------------------------------------------------------------------------
 // Producer / consumer panel product (round 6): 128 x 128 workgroup tile, eight waves with TWO ROLES.  Waves 0-3 (one per SIMD) are
 // consumers: each all 128 rows x 32 columns, weight fragments straight from L2, A fragments from LDS, nothing but MFMAs and fragment
@@ -1095,87 +1043,6 @@ __global__ __launch_bounds__(512) void k_gemm_panel_pc(GemmArgs g) {
   epilogue_t<RT / 2, NJ, 1, 4, 512>(g, reinterpret_cast<f32x4(&)[RT / 2][NJ]>(acc[RT / 2]), stage, bias_s, m0 + HM, n0, 0, cw, 0, tid, lane, consumer);
 }
 
-// Which panel form.  All three run one workgroup per CU, so a launch costs (rounds over the chip's 256 CUs) x (time of one round), and
-// the time of a round relative to the 64 x 128 form's was measured: 128 x 256 (four tiles' worth) 2.8-3.0, 128 x 128 producer /
-// consumer (two tiles' worth) 1.6-1.8 (profiles/r06_panel_wide.txt).  A bigger tile has to be >= 5 % cheaper to be taken; its coarser
-// quantisation is priced in by the rounds.  RD_PANEL_WIDE / RD_PANEL_PC = 0 / 1 exclude / force a form (read per call: tests, A/B);
-// RD_PANEL_WIDE_COST / RD_PANEL_PC_COST (percent) override the measured ratios.
-enum PanelForm { PANEL_SMALL = 0, PANEL_WIDE = 1, PANEL_PC = 2 };
-static PanelForm panel_form(const GemmArgs& g) {
-  const char* fw = getenv("RD_PANEL_WIDE");
-  const char* fp = getenv("RD_PANEL_PC");
-  const int force_w = fw ? atoi(fw) : -1, force_p = fp ? atoi(fp) : -1;
-  static const int cost_w = [] { const char* e = getenv("RD_PANEL_WIDE_COST"); return e ? atoi(e) : 280; }();
-  static const int cost_p = [] { const char* e = getenv("RD_PANEL_PC_COST"); return e ? atoi(e) : 180; }();
-  if (force_p == 1) return PANEL_PC;
-  if (force_w == 1) return PANEL_WIDE;
-  auto rounds = [&](int tm, int tn) { return ((long)cdiv(g.M, tm) * cdiv(g.N, tn) + 255) / 256; };
-  const long cs = rounds(64, 128) * 100, cw = rounds(128, 256) * cost_w, cp = rounds(128, 128) * cost_p;
-  PanelForm best = PANEL_SMALL; long bc = cs * 95;                 // in units of 1 / 100: a bigger tile must beat 0.95 x small
-  if (force_w != 0 && cw * 100 < bc) { best = PANEL_WIDE; bc = cw * 100; }
-  if (force_p != 0 && cp * 100 < bc) { best = PANEL_PC; bc = cp * 100; }
-  return best;
-}
-static int launch_panel_wide(const GemmArgs& g, hipStream_t st) {
-  constexpr int NJ = 2, TM = 128, TN = 128 * NJ;
-  const size_t lds = (size_t)4 * TM * LDB * sizeof(__bf16) + TN * sizeof(float);
-  const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
-  RD_LDS_ATTR((k_gemm_panel_wide<NJ>), lds);
-  hipLaunchKernelGGL((k_gemm_panel_wide<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch(g.xcd_swizzle ? "k_gemm_panel_wide" : "k_gemm_panel_wide_rowmajor");
-}
-static int launch_panel_pc(const GemmArgs& g, hipStream_t st) {
-  constexpr int NJ = 2, TM = 128, TN = 64 * NJ;
-  const size_t lds = (size_t)4 * TM * LDB * sizeof(__bf16) + TN * sizeof(float);
-  const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
-  RD_LDS_ATTR((k_gemm_panel_pc<NJ>), lds);
-  hipLaunchKernelGGL((k_gemm_panel_pc<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch(g.xcd_swizzle ? "k_gemm_panel_pc" : "k_gemm_panel_pc_rowmajor");
-}
-static int launch_panel(const GemmArgs& g, hipStream_t st) {
-  const PanelForm form = panel_form(g);
-  if (form == PANEL_WIDE) return launch_panel_wide(g, st);
-  if (form == PANEL_PC) return launch_panel_pc(g, st);
-  constexpr int NJ = 2, TM = 64, TN = 64 * NJ;
-  const size_t lds = (size_t)8 * TM * LDB * sizeof(__bf16) + TN * sizeof(float);      // planes (stage and hand-over alias them) + bias
-  const dim3 grid(8 * cdiv(cdiv(g.M, TM) * cdiv(g.N, TN), 8));
-  RD_LDS_ATTR((k_gemm_panel<NJ>), lds);
-  hipLaunchKernelGGL((k_gemm_panel<NJ>), grid, dim3(512), lds, st, g);
-  return check_launch(g.xcd_swizzle ? "k_gemm_panel" : "k_gemm_panel_rowmajor");
-}
-
-// padded work / tile efficiency: bigger tiles re-read less and amortise the barrier, but waste
-// more on ragged edges; pick the cheapest legal (MI, NI).
-template <bool A_KC, bool B_KC>
-int dispatch_bf16x3(const GemmArgs& g, hipStream_t st) {
-  // (a 128 x 160 tile was a candidate until round 3: its two instantiations were the last kernels of the library with register
-  // spills -- 656 bytes of scratch per lane -- and no shape of the path ever selected them)
-  static const int cand[][2] = {{2, 2}, {4, 2}, {4, 4}, {2, 4}, {2, 5}};
-  if (g.tile_hint == 1) return launch_bf16x3<A_KC, B_KC, 4, 4>(g, st);
-  int best = 0; double bcost = 1e300;
-  for (int c = 0; c < 5; ++c) {
-    const int mi = cand[c][0], ni = cand[c][1];
-    if (ni == 5 && !B_KC) continue;                  // 160-row staging only exists for k-contiguous operands
-    const double tm = 32.0 * mi, tn = 32.0 * ni;
-    const double padded = (double)cdiv(g.M, (int)tm) * tm * cdiv(g.N, (int)tn) * tn;
-    const double blocks = (double)cdiv(g.M, (int)tm) * cdiv(g.N, (int)tn) * (g.nsplit > 1 ? g.nsplit : 1);
-    // measured on MI355X: with this (unpipelined) main loop the 64x64 tile at 4 workgroups/CU beats
-    // the fatter tiles at 1-2 workgroups/CU by 1.5-3x on every shape of the path, so bigger tiles
-    // are only chosen when they are essentially free of padding AND the grid stays >= 8 blocks/CU.
-    double cost = padded * (1.0 + 16.0 / tm + 16.0 / tn);
-    if (blocks < 2048 && (mi > 2 || ni > 2)) cost *= 4.0;
-    if (blocks < 192) cost *= 192.0 / blocks;        // do not starve the 256 CUs
-    if (cost < bcost) { bcost = cost; best = c; }
-  }
-  switch (best) {
-    case 0: return launch_bf16x3<A_KC, B_KC, 2, 2>(g, st);
-    case 1: return launch_bf16x3<A_KC, B_KC, 4, 2>(g, st);
-    case 2: return launch_bf16x3<A_KC, B_KC, 4, 4>(g, st);
-    case 3: return launch_bf16x3<A_KC, B_KC, 2, 4>(g, st);
-    default: return launch_bf16x3<A_KC, true, 2, 5>(g, st);
-  }
-}
-
 __global__ void k_splitk_reduce2(const float* __restrict__ part, int nsplit, long stride, long e1,
                                  float* __restrict__ out1, long e2, float* __restrict__ out2) {
   const long elems = e1 + e2;
@@ -1254,41 +1121,234 @@ extern "C" void rd_debug_set_gemm_stamps(void* p) {      // not part of the ABI
   g_gemm_stamps = (unsigned long long*)p;
 }
 
-int launch_gemm(const GemmArgs& a, hipStream_t st) {
-  if (a.M <= 0 || a.N <= 0) return RD_OK;
-  // a row-sum request rides on the row-contiguous staging; with a 1-wide operand both strides are 1
-  const bool akc = (a.sa_k == 1) && !(a.rowsum && a.sa_m == 1), bkc = (a.sb_k == 1);
-  if (!akc && a.sa_m != 1) return fail(RD_EINVAL, "gemm: A needs a unit stride");
-  if (!bkc && a.sb_n != 1) return fail(RD_EINVAL, "gemm: B needs a unit stride");
+// ---- the route of a launch_gemm call ------------------------------------------------------------------------------------------
+// Which kernel one product runs on, in the current arithmetic mode and switches, and everything its launch needs that is not an
+// argument already.  Decided HERE and nowhere else, once per call; no HIP call, so rd_debug_gemm_route (include/raindrop_hip_debug.h)
+// answers without a device from the very functions the launch runs.  The route never goes to a kernel.
+enum GemmFamily { GEMM_NONE = 0, GEMM_FP32 = 1, GEMM_X3 = 2, GEMM_PANEL = 3 };     // k_gemm | k_gemm_bf16x3 | k_gemm_panel*
+enum PanelForm { PANEL_SMALL = 0, PANEL_WIDE = 1, PANEL_PC = 2 };
+// workgroup-to-tile map.  Single pass: XCD round-robin (default) or row-major (RD_GEMM_XCD=0); split-K: one reduction slice per XCD
+// (default) or the plain (tile, z) grid (RD_SPLITK_XCD=0)
+enum GemmMap { MAP_XCD = 0, MAP_ROWMAJOR = 1, MAP_SLICE_XCD = 2, MAP_ZGRID = 3 };
+// the (MI, NI) candidates of k_gemm_bf16x3: tile = 32 MI x 32 NI.  (A 128 x 160 tile was a candidate until round 3: its two
+// instantiations were the last kernels of the library with register spills -- 656 bytes of scratch per lane -- and no shape of the
+// path ever selected them)
+constexpr int X3_TILES[5][2] = {{2, 2}, {4, 2}, {4, 4}, {2, 4}, {2, 5}};
+// the panel forms: workgroup tile and hi / lo planes of TM rows in LDS (small: two groups x two buffers; wide, pc: two buffers)
+constexpr struct { int tm, tn, planes; } PANEL_FORMS[3] = {{64, 128, 8}, {128, 256, 4}, {128, 128, 4}};
+
+struct GemmRoute {
+  int family;        // GemmFamily
+  bool akc, bkc;     // operand layouts: k contiguous in memory, else row contiguous
+  int tile;          // GEMM_X3: index into X3_TILES; GEMM_PANEL: the PanelForm
+  int npre;          // GEMM_X3: 4 = the form that requests its whole K range up front (64 x 64 only), else 0
+  int map;           // GemmMap
+  bool one_product;  // RD_PREC_BF16: hi*hi only
+  dim3 grid;
+  size_t lds;        // dynamic LDS bytes
+  const char* name;  // what the launch reports to the error check and the launch log
+};
+
+// One name per kernel family, workgroup tile, form of the reduction loop and workgroup-to-tile map: the launch log tells RD_WGRAD_TILE,
+// RD_GEMM_NPRE, RD_GEMM_XCD, RD_SPLITK_XCD and the panel forms apart by it.  The plain name is the default map of its kind, "_rowmajor" /
+// "_zgrid" the map with the switch off.  Whole literals: the launch log keeps the pointer, and the tests match on these names.
+static const char* gemm_name(const GemmRoute& r) {
+  static const char* const x3[6][3] = {                            // [tile; 5: 64 x 64 npre][default map, _zgrid, _rowmajor]
+      {"k_gemm_bf16x3_64x64", "k_gemm_bf16x3_64x64_zgrid", "k_gemm_bf16x3_64x64_rowmajor"},
+      {"k_gemm_bf16x3_128x64", "k_gemm_bf16x3_128x64_zgrid", "k_gemm_bf16x3_128x64_rowmajor"},
+      {"k_gemm_bf16x3_128x128", "k_gemm_bf16x3_128x128_zgrid", "k_gemm_bf16x3_128x128_rowmajor"},
+      {"k_gemm_bf16x3_64x128", "k_gemm_bf16x3_64x128_zgrid", "k_gemm_bf16x3_64x128_rowmajor"},
+      {"k_gemm_bf16x3_64x160", "k_gemm_bf16x3_64x160_zgrid", "k_gemm_bf16x3_64x160_rowmajor"},
+      {"k_gemm_bf16x3_64x64_npre", "k_gemm_bf16x3_64x64_npre_zgrid", "k_gemm_bf16x3_64x64_npre_rowmajor"}};
+  static const char* const panel[3][2] = {{"k_gemm_panel", "k_gemm_panel_rowmajor"}, {"k_gemm_panel_wide", "k_gemm_panel_wide_rowmajor"},
+                                          {"k_gemm_panel_pc", "k_gemm_panel_pc_rowmajor"}};
+  if (r.family == GEMM_FP32) return "k_gemm";
+  if (r.family == GEMM_PANEL) return panel[r.tile][r.map == MAP_ROWMAJOR];
+  return x3[r.npre ? 5 : r.tile][r.map == MAP_ZGRID ? 1 : r.map == MAP_ROWMAJOR ? 2 : 0];
+}
+
+// a row-sum request rides on the row-contiguous staging; with a 1-wide operand both strides are 1
+static bool gemm_akc(const GemmArgs& a) { return a.sa_k == 1 && !(a.rowsum && a.sa_m == 1); }
+
+static int gemm_check(const GemmArgs& a) {
+  if (!gemm_akc(a) && a.sa_m != 1) return fail(RD_EINVAL, "gemm: A needs a unit stride");
+  if (a.sb_k != 1 && a.sb_n != 1) return fail(RD_EINVAL, "gemm: B needs a unit stride");
   if (a.nbatch > 1 && (a.nsplit > 1 || a.A2 || a.rowsum || a.scatter || a.batch_inner < 1))
     return fail(RD_EINVAL, "gemm: the batched form takes plain single-pass products only");
   // the token plan's scatter exists on the straight epilogue of the bf16 kernels only (16-byte cells, no mask / residual / dropout)
   if (a.sp_row0 && !(a.scatter && a.sd == 4 && (a.N & 3) == 0 && (a.ldz & 3) == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0 &&
                      !a.posmask && !a.residual && !(a.drop_p > 0.f) && a.nsplit <= 1 && a.sp_len && precision() != RD_PREC_FP32))
     return fail(RD_EUNSUPPORTED, "gemm: the plan-following scatter needs d_ob = 4, 16-byte cells and a plain epilogue in a bf16 mode");
-  dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), a.nbatch > 1 ? a.nbatch : (a.nsplit > 1 ? a.nsplit : 1));
+  if (precision() != RD_PREC_FP32 && a.nsplit > 1 && (a.k_per_split % BK2) != 0)
+    return fail(RD_EINVAL, "gemm: k_per_split must be a multiple of 64");
+  return RD_OK;
+}
+
+static GemmRoute gemm_route(const GemmArgs& a) {
+  // read once per process
+  static const int xcd_on = [] { const char* e = getenv("RD_GEMM_XCD"); return e ? atoi(e) : 1; }();
+  static const int slice_on = [] { const char* e = getenv("RD_SPLITK_XCD"); return e ? atoi(e) : 1; }();
+  static const bool panel_on = [] { const char* e = getenv("RD_GEMM_PANEL"); return !(e && atoi(e) == 0); }();
+  static const bool npre_on = [] { const char* e = getenv("RD_GEMM_NPRE"); return !(e && atoi(e) == 0); }();
+  static const int cost_w = [] { const char* e = getenv("RD_PANEL_WIDE_COST"); return e ? atoi(e) : 280; }();
+  static const int cost_p = [] { const char* e = getenv("RD_PANEL_PC_COST"); return e ? atoi(e) : 180; }();
+  const int prec = precision();
+  const int nsplit = a.nsplit > 1 ? a.nsplit : 1, pair = a.A2 ? 2 : 1;
+  GemmRoute r{};
+  r.akc = gemm_akc(a); r.bkc = a.sb_k == 1;
+  r.one_product = prec == RD_PREC_BF16;
+  auto tiles = [&](int tm, int tn) { return (long)cdiv(a.M, tm) * cdiv(a.N, tn); };
+
+  if (prec == RD_PREC_FP32) {                          // exact fp32: one tile, the plain (column block, row block, z) grid
+    r.family = GEMM_FP32;
+    r.map = nsplit > 1 ? MAP_ZGRID : MAP_ROWMAJOR;
+    r.grid = dim3(cdiv(a.N, BN), cdiv(a.M, BM), a.nbatch > 1 ? a.nbatch : nsplit);
+  } else if (panel_on && a.Btiles && a.sa_k == 1 && (a.sa_m & 3) == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0 && nsplit == 1 &&
+             a.nbatch <= 1 && !a.A2 && !a.rowsum && a.K >= 64) {
+    // the panel form applies: pre-split weight tiles given, A k-contiguous with 16-byte rows, one plain pass.
+    // Which form.  All three run one workgroup per CU, so a launch costs (rounds over the chip's 256 CUs) x (time of one round), and
+    // the time of a round relative to the 64 x 128 form's was measured: 128 x 256 (four tiles' worth) 2.8-3.0, 128 x 128 producer /
+    // consumer (two tiles' worth) 1.6-1.8 (profiles/r06_panel_wide.txt).  A bigger tile has to be >= 5 % cheaper to be taken; its
+    // coarser quantisation is priced in by the rounds.  RD_PANEL_WIDE / RD_PANEL_PC = 0 / 1 exclude / force a form (read per call:
+    // tests, A/B); RD_PANEL_WIDE_COST / RD_PANEL_PC_COST (percent) override the measured ratios.
+    r.family = GEMM_PANEL;
+    const char* fw = getenv("RD_PANEL_WIDE");
+    const char* fp = getenv("RD_PANEL_PC");
+    const int force_w = fw ? atoi(fw) : -1, force_p = fp ? atoi(fp) : -1;
+    auto rounds = [&](int f) { return (tiles(PANEL_FORMS[f].tm, PANEL_FORMS[f].tn) + 255) / 256; };
+    const long cw = rounds(PANEL_WIDE) * cost_w, cp = rounds(PANEL_PC) * cost_p;
+    long bc = rounds(PANEL_SMALL) * 100 * 95;          // in units of 1 / 100: a bigger tile must beat 0.95 x small
+    r.tile = PANEL_SMALL;
+    if (force_w != 0 && cw * 100 < bc) { r.tile = PANEL_WIDE; bc = cw * 100; }
+    if (force_p != 0 && cp * 100 < bc) r.tile = PANEL_PC;
+    if (force_w == 1) r.tile = PANEL_WIDE;
+    if (force_p == 1) r.tile = PANEL_PC;
+    const auto& f = PANEL_FORMS[r.tile];
+    r.map = xcd_on ? MAP_XCD : MAP_ROWMAJOR;
+    r.grid = dim3(8 * cdiv((int)tiles(f.tm, f.tn), 8));
+    r.lds = (size_t)f.planes * f.tm * LDB * sizeof(__bf16) + f.tn * sizeof(float);    // planes (stage and hand-over alias them) + bias
+  } else {
+    r.family = GEMM_X3;
+    // padded work / tile efficiency: bigger tiles re-read less and amortise the barrier, but waste more on ragged edges; pick the
+    // cheapest legal (MI, NI).  tile_hint == 1 (split-K weight gradients under RD_WGRAD_TILE=128) forces 128 x 128.
+    r.tile = 2;
+    double bcost = 1e300;
+    for (int c = 0; c < 5 && a.tile_hint != 1; ++c) {
+      const int mi = X3_TILES[c][0], ni = X3_TILES[c][1];
+      if (ni == 5 && !r.bkc) continue;                 // 160-row staging only exists for k-contiguous operands
+      const double tm = 32.0 * mi, tn = 32.0 * ni;
+      const double padded = (double)cdiv(a.M, (int)tm) * tm * cdiv(a.N, (int)tn) * tn;
+      const double blocks = (double)cdiv(a.M, (int)tm) * cdiv(a.N, (int)tn) * nsplit;
+      // measured on MI355X: with this (unpipelined) main loop the 64x64 tile at 4 workgroups/CU beats
+      // the fatter tiles at 1-2 workgroups/CU by 1.5-3x on every shape of the path, so bigger tiles
+      // are only chosen when they are essentially free of padding AND the grid stays >= 8 blocks/CU.
+      double cost = padded * (1.0 + 16.0 / tm + 16.0 / tn);
+      if (blocks < 2048 && (mi > 2 || ni > 2)) cost *= 4.0;
+      if (blocks < 192) cost *= 192.0 / blocks;        // do not starve the 256 CUs
+      if (cost < bcost) { bcost = cost; r.tile = c; }
+    }
+    const int TM = 32 * X3_TILES[r.tile][0], TN = 32 * X3_TILES[r.tile][1];
+    // Measured on MI355X (tools/gemm_timing.py, tools/bw_probe.py): requesting all K tiles up front
+    // (NPRE = tiles) is neutral at K=152 and 40 % slower at K=272 (register-limited occupancy), because
+    // these products are bound by operand RE-READS at the L2 level (each 64x64 tile loads 39+39 KB to
+    // write 16 KB), not by dependent latency; the looped form with one tile of lookahead stays.
+    // ... except for the handful-of-workgroups products of the classifier head (M = B = 256 rows: 12 workgroups, 3 K tiles):
+    // those are pure dependent-latency chains (measured 14-35 us for a 256 x 186 x 186 product), so the whole K range is
+    // requested up front.
+    if (r.tile == 0 && npre_on && tiles(64, 64) * nsplit * pair <= 128 && (nsplit > 1 ? a.k_per_split : a.K) <= 256) r.npre = 4;
+    r.map = nsplit > 1 ? (slice_on ? MAP_SLICE_XCD : MAP_ZGRID) : (xcd_on ? MAP_XCD : MAP_ROWMAJOR);
+    const int nz = a.nbatch > 1 ? a.nbatch : nsplit * pair;
+    // single pass: row blocks padded to a group of 8 (the XCD order's unit); slice per XCD: 8 * ceil(nz / 8) * tiles in x
+    r.grid = dim3((nsplit > 1 ? cdiv(a.M, TM) : 8 * cdiv(cdiv(a.M, TM), 8)) * cdiv(a.N, TN), 1, nz);
+    if (r.map == MAP_SLICE_XCD) r.grid = dim3(8 * cdiv(nz, 8) * (int)tiles(TM, TN), 1, 1);
+    const size_t planes = (size_t)2 * (TM + TN) * LDB * sizeof(__bf16);
+    const size_t stage = (size_t)TM * (TN + 4) * sizeof(float);       // epilogue transpose tile (aliases the planes)
+    r.lds = (planes > stage ? planes : stage) + TN * sizeof(float);   // + bias
+  }
+  r.name = gemm_name(r);
+  return r;
+}
+
+// ---- one launcher per family, each a switch over the route ---------------------------------------------------------------------
+template <auto KERNEL, int THREADS>
+static int gemm_run(const GemmRoute& r, const GemmArgs& g, hipStream_t st) {
+  if (r.lds > 48 * 1024) {                             // dynamic-LDS opt-in, once per process and kernel (RD_LDS_ATTR, under the route's name)
+    static const hipError_t attr = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+    if (attr != hipSuccess) return fail((int)attr, "hipFuncSetAttribute(%s): %s", r.name, hipGetErrorString(attr));
+  }
+  hipLaunchKernelGGL(KERNEL, r.grid, dim3(THREADS), r.lds, st, g);
+  return check_launch(r.name);
+}
+// f(A_KC, B_KC) with the operand layouts as compile-time constants
+template <class F>
+static int by_layout(const GemmRoute& r, F&& f) {
+  if (r.akc) return r.bkc ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return r.bkc ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+static int launch_fp32(const GemmRoute& r, const GemmArgs& g, hipStream_t st) {
+  return by_layout(r, [&](auto akc, auto bkc) { return gemm_run<k_gemm<decltype(akc)::value, decltype(bkc)::value>, 256>(r, g, st); });
+}
+static int launch_x3(const GemmRoute& r, const GemmArgs& g, hipStream_t st) {
+  return by_layout(r, [&](auto akc, auto bkc) {
+    constexpr bool A = decltype(akc)::value, B = decltype(bkc)::value;
+    switch (r.tile) {
+      case 0: return r.npre ? gemm_run<k_gemm_bf16x3<A, B, 2, 2, 4>, 256>(r, g, st) : gemm_run<k_gemm_bf16x3<A, B, 2, 2, 0>, 256>(r, g, st);
+      case 1: return gemm_run<k_gemm_bf16x3<A, B, 4, 2, 0>, 256>(r, g, st);
+      case 2: return gemm_run<k_gemm_bf16x3<A, B, 4, 4, 0>, 256>(r, g, st);
+      case 3: return gemm_run<k_gemm_bf16x3<A, B, 2, 4, 0>, 256>(r, g, st);
+      default: return gemm_run<k_gemm_bf16x3<A, true, 2, 5, 0>, 256>(r, g, st);      // 64 x 160: the route takes it with a k-contiguous B only
+    }
+  });
+}
+static int launch_panel(const GemmRoute& r, const GemmArgs& g, hipStream_t st) {
+  switch (r.tile) {
+    case PANEL_WIDE: return gemm_run<k_gemm_panel_wide<2>, 512>(r, g, st);
+    case PANEL_PC: return gemm_run<k_gemm_panel_pc<2>, 512>(r, g, st);
+    default: return gemm_run<k_gemm_panel<2>, 512>(r, g, st);
+  }
+}
+
+int launch_gemm(const GemmArgs& a, hipStream_t st) {
+  if (a.M <= 0 || a.N <= 0) return RD_OK;
+  if (int rc = gemm_check(a)) return rc;
+  const GemmRoute r = gemm_route(a);
   GemmArgs g = a;
   g.seed_cell = seed_cell();
   g.stamps = g_gemm_stamps;
-  static const int xcd_env = [] { const char* e = getenv("RD_GEMM_XCD"); return e ? atoi(e) : 1; }();
-  g.xcd_swizzle = xcd_env;
+  g.xcd_swizzle = r.map == MAP_XCD; g.slice_xcd = r.map == MAP_SLICE_XCD; g.one_product = r.one_product;
   if (g.nsplit <= 1) { g.nsplit = 1; g.k_per_split = g.K > 0 ? g.K : 1; g.sc_split = 0; }
-  if (precision() != RD_PREC_FP32) {
-    g.one_product = precision() == RD_PREC_BF16;
-    static const int sx_env = [] { const char* e = getenv("RD_SPLITK_XCD"); return e ? atoi(e) : 1; }();
-    g.slice_xcd = (g.nsplit > 1 && sx_env) ? 1 : 0;
-    if (g.nsplit > 1 && (g.k_per_split % BK2) != 0) return fail(RD_EINVAL, "gemm: k_per_split must be a multiple of 64");
-    if (panel_ok(g)) return launch_panel(g, st);
-    if (akc && bkc) return dispatch_bf16x3<true, true>(g, st);
-    if (akc && !bkc) return dispatch_bf16x3<true, false>(g, st);
-    if (!akc && bkc) return dispatch_bf16x3<false, true>(g, st);
-    return dispatch_bf16x3<false, false>(g, st);
+  switch (r.family) {
+    case GEMM_FP32: return launch_fp32(r, g, st);
+    case GEMM_PANEL: return launch_panel(r, g, st);
+    default: return launch_x3(r, g, st);
   }
-  if (akc && bkc) hipLaunchKernelGGL((k_gemm<true, true>), grid, dim3(256), 0, st, g);
-  else if (akc && !bkc) hipLaunchKernelGGL((k_gemm<true, false>), grid, dim3(256), 0, st, g);
-  else if (!akc && bkc) hipLaunchKernelGGL((k_gemm<false, true>), grid, dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((k_gemm<false, false>), grid, dim3(256), 0, st, g);
-  return check_launch("k_gemm");
+}
+
+// not part of the ABI (include/raindrop_hip_debug.h): the route of the product described by value, from the launch's own functions
+extern "C" int rd_debug_gemm_route(int32_t M, int32_t N, int32_t K, int64_t sa_m, int64_t sa_k, int64_t sb_n, int64_t sb_k, int32_t nsplit,
+                                   int32_t k_per_split, int32_t tile_hint, uint32_t flags, uint32_t* words, char* name, size_t cap) {
+  RD_REQUIRE(words && name && cap > 0, "NULL tensor");
+  float* const al = reinterpret_cast<float*>(uintptr_t(64));       // stand-ins: a route reads a pointer's presence and alignment only
+  GemmArgs a{};
+  a.M = M; a.N = N; a.K = K; a.sa_m = sa_m; a.sa_k = sa_k; a.sb_n = sb_n; a.sb_k = sb_k;
+  a.nsplit = nsplit; a.k_per_split = k_per_split; a.tile_hint = tile_hint;
+  a.A = (flags & 32) ? al : al + 1; a.B = al; a.C = al;
+  if (flags & 1) { a.A2 = a.A; a.B2 = al; a.C2 = al; }
+  if (flags & 2) a.rowsum = al;
+  if (flags & 4) { a.nbatch = 2; a.batch_inner = 1; }
+  if (flags & 8) { a.scatter = 1; a.sB = 1; a.sF = M; a.sd = 4; a.ldz = 4 * (long)M; }
+  if (flags & 16) { a.Btiles = al; a.bt_ntile = cdiv(N, 16); a.bt_nkc = cdiv(K, 32); }
+  if (flags & 64) { a.sp_row0 = reinterpret_cast<const int32_t*>(al); a.sp_len = a.sp_row0; }
+  for (int i = 0; i < 5; ++i) words[i] = 0;
+  name[0] = 0;
+  if (M <= 0 || N <= 0) return RD_OK;                  // launch_gemm: nothing to do, nothing launched
+  if (int rc = gemm_check(a)) return rc;
+  const GemmRoute r = gemm_route(a);
+  words[0] = (uint32_t)r.family | (uint32_t)r.akc << 2 | (uint32_t)r.bkc << 3 | (uint32_t)r.one_product << 4 | (uint32_t)r.map << 5 |
+             (uint32_t)r.npre << 8 | (uint32_t)r.tile << 12;
+  words[1] = r.grid.x; words[2] = r.grid.y; words[3] = r.grid.z; words[4] = (uint32_t)r.lds;
+  snprintf(name, cap, "%s", r.name);
+  return RD_OK;
 }
 
 // Weight-gradient products are HBM-traffic-bound (PMC: the 64x64-tile form fetches 4x its operands).
@@ -1315,31 +1375,37 @@ int splitk_plan(long red, int rows, int cols, int* k_per_split) {
   return cdiv(r, per);
 }
 
+extern "C" int rd_debug_splitk_plan(int64_t red, int32_t rows, int32_t cols, int32_t* k_per_split) {   // not part of the ABI
+  return splitk_plan(red, rows, cols, k_per_split);
+}
+
 // dW[N,K] = dy[M,N]^T x[M,K] and db[N] = sum_m dy[m,:] with ONE pass over dy: the split-K product
 // accumulates the row sums of its A operand (= dy^T) on the side.  ws: nsplit*(N*K + N) floats.
 long wgrad_ws_floats(long M, int N, int K) {
   int kps; const int ns = splitk_plan(M, N, K, &kps);
   return (long)ns * ((long)N * K + N);
 }
-int launch_wgrad(long M, int N, int K, const float* dy, long lddy, const float* x, long ldx, float* dW,
-                 float* db, float* ws, hipStream_t st) {
-  int kps; const int ns = splitk_plan(M, N, K, &kps);
+// the product as launch_gemm takes it: the transposed operands under the split-K plan, C (and the row sums, if any) either the final
+// arrays (ns <= 1) or slice z's [dW partial | db partial] in the workspace
+static GemmArgs wgrad_args(long M, int N, int K, const float* dy, long lddy, const float* x, long ldx, int ns, int kps, float* C,
+                           float* rowsum) {
   GemmArgs t{};
   t.M = N; t.N = K; t.K = (int)M;
   t.A = dy; t.sa_m = 1; t.sa_k = lddy;
   t.B = x; t.sb_n = 1; t.sb_k = ldx;
   t.nsplit = ns; t.k_per_split = kps;
   t.tile_hint = (N >= 96 && K >= 96 && wgrad_tile() == 128) ? 1 : 0;
+  t.C = C; t.sc_m = K; t.rowsum = rowsum;
+  if (ns > 1) t.sc_split = t.rowsum_split = (long)N * K + N;
+  return t;
+}
+int launch_wgrad(long M, int N, int K, const float* dy, long lddy, const float* x, long ldx, float* dW,
+                 float* db, float* ws, hipStream_t st) {
+  int kps; const int ns = splitk_plan(M, N, K, &kps);
+  if (ns <= 1) return launch_gemm(wgrad_args(M, N, K, dy, lddy, x, ldx, ns, kps, dW, db), st);
   const long stride = (long)N * K + N;                 // split z: [dW partial | db partial]
-  int rc;
-  if (ns > 1) {
-    t.C = ws; t.sc_m = K; t.sc_split = stride;
-    t.rowsum = db ? ws + (long)N * K : nullptr; t.rowsum_split = stride;
-    if ((rc = launch_gemm(t, st))) return rc;
-    return launch_splitk_reduce_pair(ws, dW, db, nullptr, nullptr, nullptr, ns, stride, (long)N * K, N, st);
-  }
-  t.C = dW; t.sc_m = K; t.rowsum = db; t.rowsum_split = 0;
-  return launch_gemm(t, st);
+  if (int rc = launch_gemm(wgrad_args(M, N, K, dy, lddy, x, ldx, ns, kps, ws, db ? ws + (long)N * K : nullptr), st)) return rc;
+  return launch_splitk_reduce_pair(ws, dW, db, nullptr, nullptr, nullptr, ns, stride, (long)N * K, N, st);
 }
 
 int launch_wgrad2(long M, int N, int K, const float* dyA, const float* xA, float* dWA, float* dbA,
@@ -1352,17 +1418,9 @@ int launch_wgrad2(long M, int N, int K, const float* dyA, const float* xA, float
     return launch_wgrad(M, N, K, dyB, N, xB, K, dWB, dbB, ws + (long)ns * stride, st);
   }
   float* wsB = ws + (long)ns * stride;
-  GemmArgs t{};
-  t.M = N; t.N = K; t.K = (int)M;
-  t.A = dyA; t.sa_m = 1; t.sa_k = N;
-  t.B = xA; t.sb_n = 1; t.sb_k = K;
-  t.nsplit = ns; t.k_per_split = kps;
-  t.tile_hint = (N >= 96 && K >= 96 && wgrad_tile() == 128) ? 1 : 0;
-  t.C = ws; t.sc_m = K; t.sc_split = stride;
-  t.rowsum = ws + (long)N * K; t.rowsum_split = stride;
+  GemmArgs t = wgrad_args(M, N, K, dyA, N, xA, K, ns, kps, ws, ws + (long)N * K);
   t.A2 = dyB; t.B2 = xB; t.C2 = wsB; t.rowsum2 = wsB + (long)N * K;
-  int rc;
-  if ((rc = launch_gemm(t, st))) return rc;
+  if (int rc = launch_gemm(t, st)) return rc;
   return launch_splitk_reduce_pair(ws, dWA, dbA, wsB, dWB, dbB, ns, stride, (long)N * K, N, st);
 }
 

@@ -53,6 +53,9 @@ def _launch_names():
     for text in _sources().values():
         for call in re.findall(r"check_launch\(([^;]*?)\)\s*[;)]", text):
             names.update(re.findall(r'"([A-Za-z0-9_]+)"', call))
+        # rd_gemm.hip reports its route's name, check_launch(r.name): the literals of the one function that names a route
+        for body in re.findall(r"\nstatic const char\* \w+_name\(const \w+Route& r\) \{\n(.*?)\n\}\n", text, re.S):
+            names.update(re.findall(r'"([A-Za-z0-9_]+)"', body))
     return names
 
 
