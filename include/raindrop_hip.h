@@ -501,6 +501,19 @@ int rd_adam_step_clip_ema_grp_dev(int64_t n, float* param, const float* grad, fl
  * their average, so that whatever holds the parameters' addresses evaluates the average.  a, b: 16-byte aligned, not overlapping.
  * RD_EINVAL: NULL or misaligned pointers, n <= 0. */
 int rd_swap_f32(int64_t n, float* a, float* b, void* stream);
+/* Gradient accumulation over a window of k micro-batches (raindrop_amd.step.TrainStep(accumulate=k)): two fp32 element-wise launches
+ * over the flat gradient buffer `g` and an accumulator `acc` of n floats each, capturable, without atomics, the same bits on every
+ * launch.
+ *   rd_grad_accumulate:        acc[i] = acc[i] + g[i]                                   (the micro-batches of a window but the last)
+ *   rd_grad_accumulate_close:  g[i] = (acc[i] + g[i]) * s;  acc[i] = 0                  (the last: `g` holds the window's mean)
+ * `s` is the one float at `scale_cell` (device memory, 4-byte aligned), read when the kernel RUNS: 1/k, or 1/j for a window cut short
+ * after j micro-batches -- a 4-byte copy between replays, not a new capture.  One fp32 add, then one fp32 multiply, both rounded to
+ * nearest on their own (never fused): torch's `(acc + g) * s` bit for bit.  inf / NaN in `g` or `acc` propagate into `g`; `acc` is
+ * +0 after the close whatever it held, so a poisoned window reaches the update's non-finite guard (_clip) and the next one starts clean.
+ * 16-byte accesses with a scalar tail for n % 4; nothing at or behind element n is read or written.  g, acc: 16-byte aligned, not
+ * overlapping.  RD_EINVAL: NULL or misaligned pointers, n < 0; n == 0 is RD_OK without a launch. */
+int rd_grad_accumulate(int64_t n, const float* g, float* acc, void* stream);
+int rd_grad_accumulate_close(int64_t n, float* g, float* acc, const float* scale_cell, void* stream);
 
 /* ---- generic dense pieces (used by the temporal encoder, the head and the large-K path) ---- */
 

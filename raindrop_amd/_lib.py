@@ -122,6 +122,9 @@ SIGNATURES = {
                                         _P, c_size_t, _P, _P, _P, _P]),
     "rd_adam_step_clip_ema_dev": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, _P, _P, c_size_t, _P, _P, _P, _P]),
     "rd_swap_f32": (c_int32, [ctypes.c_int64, _P, _P, _P]),
+    # gradient accumulation over a window of micro-batches (raindrop_amd.step.TrainStep(accumulate=k)): g, acc [, scale_cell], stream
+    "rd_grad_accumulate": (c_int32, [ctypes.c_int64, _P, _P, _P]),
+    "rd_grad_accumulate_close": (c_int32, [ctypes.c_int64, _P, _P, _P, _P]),
     # parameter groups / decoupled weight decay (raindrop_amd.optim.FlatAdam(groups=..., decoupled=...)): the twins take `chunk_group`, `group_cell` in front of the stream
     "rd_adam_step_grp": (c_int32, [ctypes.c_int64, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_float,
                                    ctypes.c_int64, _P, _P, _P]),

@@ -313,6 +313,59 @@ __global__ __launch_bounds__(256) void k_swap_f32(float* __restrict__ a, float* 
   }
 }
 
+// ---- gradient accumulation over a window of micro-batches --------------------------------------------------------------
+// Two element-wise passes over the flat gradient buffer `g` and an accumulator `acc` of the same size: the micro-batches of a window
+// but the last run k_grad_accumulate (acc += g), the last one k_grad_accumulate_close (g = (acc + g) * s, acc = 0), which leaves the
+// window's mean where the all-reduce and the update read it and the accumulator clean for the next window -- whatever it held: an inf
+// or NaN goes into g (the update's non-finite guard sees it) and not into the next window.  One add and one multiply per element, each
+// rounded on its own (torch's `(acc + g) * s`, bit for bit); no atomics, element i depends on element i alone.  `s` is read from a
+// device cell when the kernel RUNS, like the optimizer's other cells: a shorter last window is a 4-byte copy, not a new capture.
+// Grid: one float4 per thread and pass, at most kAccumGridMax workgroups (8 per CU: every one resident at once) striding over the rest;
+// the P19 buffer (0.5 M floats, 2 MB) is about 500 workgroups, one pass each.  The tail behind the last whole float4 is workgroup 0's.
+constexpr int kAccumGridMax = 2048;
+
+__device__ __forceinline__ float add_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+template <bool CLOSE>
+__global__ __launch_bounds__(256) void k_grad_accumulate(float* __restrict__ g, float* __restrict__ acc, long n,
+                                                         const float* __restrict__ scale_cell) {
+  const float s = CLOSE ? *scale_cell : 1.f;
+  const long n4 = n >> 2, stride = (long)gridDim.x * 256;
+  for (long q = blockIdx.x * 256L + threadIdx.x; q < n4; q += stride) {
+    const float4 x = *reinterpret_cast<const float4*>(g + 4 * q), a = *reinterpret_cast<const float4*>(acc + 4 * q);
+    float4 r = {add_rounded(a.x, x.x), add_rounded(a.y, x.y), add_rounded(a.z, x.z), add_rounded(a.w, x.w)};
+    if (CLOSE) {
+      r.x = mul_rounded(r.x, s); r.y = mul_rounded(r.y, s); r.z = mul_rounded(r.z, s); r.w = mul_rounded(r.w, s);
+      *reinterpret_cast<float4*>(g + 4 * q) = r;
+      *reinterpret_cast<float4*>(acc + 4 * q) = float4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      *reinterpret_cast<float4*>(acc + 4 * q) = r;
+    }
+  }
+  const long i = (n4 << 2) + threadIdx.x;                        // n % 4 elements behind the last whole float4
+  if (blockIdx.x == 0 && i < n) {
+    const float r = add_rounded(acc[i], g[i]);
+    if (CLOSE) { g[i] = mul_rounded(r, s); acc[i] = 0.f; }
+    else acc[i] = r;
+  }
+}
+
+template <bool CLOSE>
+int accumulate_launch(int64_t n, float* g, float* acc, const float* scale_cell, void* stream) {
+  RD_REQUIRE(n >= 0, "bad n");
+  RD_REQUIRE(g && acc && (!CLOSE || scale_cell), "NULL tensor");
+  RD_REQUIRE(((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(acc)) & 15) == 0, "buffers must be 16-byte aligned");
+  RD_REQUIRE((reinterpret_cast<uintptr_t>(scale_cell) & 3) == 0, "scale_cell must be 4-byte aligned");
+  if (n == 0) return RD_OK;
+  const long blocks = ((n >> 2) + 255) / 256;
+  const unsigned grid = (unsigned)(blocks < 1 ? 1 : blocks > kAccumGridMax ? kAccumGridMax : blocks);
+  hipLaunchKernelGGL(k_grad_accumulate<CLOSE>, dim3(grid), dim3(256), 0, (hipStream_t)stream, g, acc, (long)n, scale_cell);
+  return check_launch(CLOSE ? "k_grad_accumulate_close" : "k_grad_accumulate");
+}
+
 // What kind of box is this?  (DESIGN.md "Box variance")  32 KB of straight-line code -- 4096 dependent 8-byte v_fma_f32, nothing the
 // compiler can fold --, one wave, clock64 around it: cold (its code in no cache) about 80 ticks per 64-byte line where the hardware
 // fetches instructions ahead, 400-450 where it does not; warm 45-55 / 75-95.  tools/probe_clocks.hip is the standalone form.
@@ -570,6 +623,14 @@ extern "C" int rd_adam_step_clip_ema_grp_dev(int64_t n, float* param, const floa
   return adam_launch<true, true, true, true>(c);
 }
 #undef RD_GRP
+
+extern "C" int rd_grad_accumulate(int64_t n, const float* g, float* acc, void* stream) {
+  return accumulate_launch<false>(n, const_cast<float*>(g), acc, nullptr, stream);
+}
+
+extern "C" int rd_grad_accumulate_close(int64_t n, float* g, float* acc, const float* scale_cell, void* stream) {
+  return accumulate_launch<true>(n, g, acc, scale_cell, stream);
+}
 
 extern "C" int rd_swap_f32(int64_t n, float* a, float* b, void* stream) {
   RD_REQUIRE(n > 0, "bad n");

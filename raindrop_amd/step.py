@@ -29,7 +29,8 @@ How the host layer is laid out:
   rd_step_prepare's K1 weight tiles apply.
 * `capture_graphs` is the one place that warms up on a side stream, joins, synchronizes and captures.
 * `TrainStep` adds what training needs: the two-graph data-parallel form, the autotune of the row-block knobs, the measurement
-  captures of bench.py, `capture_full` with the optimizer inside.
+  captures of bench.py, `capture_full` with the optimizer inside, and gradient accumulation (`accumulate=k`: every form captured
+  twice, the window's accumulate / close launch behind the body).
 
 The captured graph is replayed per step; dropout masks change per replay through the device seed
 cell (`rd_set_seed_cell` / `rd_seed_cell_advance`), which the graph bumps itself.  The gradient
@@ -597,7 +598,7 @@ class TrainStep(Step):
     TUNE_WAVES = (12, 15)
 
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0, feed=None):
+                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0, feed=None, accumulate=1):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
         live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
         of device tensors that are REUSED every step (copy new data into them).
@@ -617,7 +618,28 @@ class TrainStep(Step):
         token_plan: store and process only the live (sample, step) rows (include/raindrop_hip.h "token plan": the padding mask of
         code/models_rd.py:298-299 applied as a layout; same logits, loss and gradients).  None = environment RD_TOKEN_PLAN
         (default on) where the shape supports it.
-        sensor: the sensor-stage object (default: the default branch's; BetaTrainStep passes the use_beta one)."""
+        sensor: the sensor-stage object (default: the default branch's; BetaTrainStep passes the use_beta one).
+        accumulate: k micro-batches per optimizer step (an int >= 1; 1, the default: the step as it always was, no accumulator).
+        With k > 1 the step owns `acc`, an fp32 accumulator the size of flat.flat (zero at construction), and `scale_cell`, one
+        float32 holding 1/k, and every form is captured twice: positions 0 .. k-2 of a window end with rd_grad_accumulate
+        (acc += g), position k-1 with rd_grad_accumulate_close (g = (acc + g) * scale, acc = 0).  `window_position()` is the
+        host's count of micro-batches in the open window; `window_closed` says whether the last call closed one -- that is when
+        flat.flat holds the window's gradient and the caller steps the optimizer.
+          * the window's gradient is the MEAN of the k micro-batch gradients, each normalised by its own denominator (its batch
+            size, or under class weights its own weight sum): what torch users get from `(loss / k).backward()` k times;
+          * the dropout seed cell, the feed's cursor and its loss / correct records advance per micro-batch; the optimizer's step
+            count, its schedule position and its EMA count per window; `max_grad_norm` sees the norm of the window's mean, and a
+            window with a non-finite micro-batch is skipped as a whole (the accumulator is clean afterwards);
+          * `p.grad` views hold the window's mean after a closing call and the LAST micro-batch's own gradient otherwise;
+          * data parallel: every rank accumulates locally, `run_allreduce()` issues NO collective on positions 0 .. k-2 and the
+            closing call's collective averages the ranks' window means (DistributedDataParallel's no_sync);
+          * `module_mode=True` refuses k > 1: the loss is the caller's there, and autograd's own accumulation already works."""
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError("accumulate must be an integer >= 1, got %r" % (accumulate,))
+        if accumulate > 1 and module_mode:
+            raise ValueError("TrainStep(module_mode=True) leaves the loss and its backward to the caller, whose autograd accumulates "
+                             "by itself: accumulate=%d is refused" % accumulate)
+        self.accumulate, self.acc, self.scale_cell, self._pos, self.window_closed = accumulate, None, None, 0, False
         # module_mode (raindrop_amd.graph_module): the loss is the CALLER's -- the step is cut into parts 'mf' (forward up to the
         # logits) and 'mb' (backward from self.dlogits, which the caller fills), batch carries no labels
         self.module_mode = bool(module_mode)
@@ -640,7 +662,11 @@ class TrainStep(Step):
         if feed is not None:
             feed.check_step(model, batch)
         self.graph = self.graph_b = self.graph_full = self._full_opt = self._full_hyper = None
-        self.captures = 0                                                  # whole-step graphs captured so far (capture_full)
+        self.graph_close = self.graph_b_close = self.graph_full_micro = None   # accumulate > 1: the closing twins of graph / graph_b,
+        self.captures = 0                                                  # the micro twin of graph_full; whole-step graphs captured so far
+        if accumulate > 1:                                                 # (not in the arena: accumulate=1 allocates what it always did)
+            self.acc = torch.zeros_like(flat.flat)
+            self.scale_cell = torch.full((1,), 1.0 / accumulate, dtype=torch.float32, device=self.dev)
         if use_graph:
             with self._feed_kept():
                 self._capture()
@@ -657,13 +683,54 @@ class TrainStep(Step):
     @contextlib.contextmanager
     def _feed_kept(self):
         """around a capture: its warm-up passes (and the autotune's timed replays) gather, record and advance the cursor like any
-        step -- the feed is as it was afterwards"""
+        step -- the feed is as it was afterwards, and so is the accumulator of an open window (accumulate > 1: the passes end with
+        the accumulate and close launches)"""
         snap = self.feed.snapshot() if self.feed is not None else None
+        acc = self.acc.clone() if self.acc is not None else None
         try:
             yield
         finally:
             if snap is not None:
                 self.feed.restore(snap)
+            if acc is not None:
+                self.acc.copy_(acc)
+
+    # ---- the window's launch behind the body (nothing with accumulate == 1) -------------------------------------------------------
+    def _window_tail(self, closing, part=None):
+        """What follows part `part` of the body on a window position: behind the whole step (None) or behind 'b' the accumulate
+        launch over the whole buffer (positions 0 .. k-2) or the close launch (position k-1) -- over the whole buffer, or in the
+        split form over the range each part completes: [early_grad_offset(), n) behind 'a', so that the first bucket's collective
+        reads the window's mean, and [0, offset) behind 'b'.  (The offset is a multiple of 64 elements: dp.FlatGradAllReduce.)"""
+        if self.acc is None:
+            return
+        g, n = self.flat.flat, self.flat.flat.numel()
+        if not closing:
+            if part != "a":
+                self._call("rd_grad_accumulate", n, _p(g), _p(self.acc), ops._stream())
+            return
+        off = self.early_grad_offset() if part is not None else 0
+        lo, hi = (off, n) if part == "a" else (0, off) if part == "b" else (0, n)
+        if hi > lo:
+            self._call("rd_grad_accumulate_close", hi - lo, ctypes.c_void_p(g.data_ptr() + 4 * lo),
+                       ctypes.c_void_p(self.acc.data_ptr() + 4 * lo), _p(self.scale_cell), ops._stream())
+
+    def _closing_next(self):
+        """the next call closes a window (always, without accumulation)"""
+        return self._pos == self.accumulate - 1
+
+    def _advance_window(self, closing):
+        self._pos = 0 if closing else self._pos + 1
+        self.window_closed = bool(closing)
+
+    def window_position(self):
+        """micro-batches taken in the open window, 0 .. accumulate - 1 (host count: no synchronisation)"""
+        return self._pos
+
+    def reset_window(self):
+        """Drop the open window: the accumulator is zeroed (stream-ordered) and the next call is position 0."""
+        if self.acc is not None:
+            self.acc.zero_()
+        self._pos, self.window_closed = 0, False
 
     def _capture(self):
         """Capture the step as one hipGraph (two in the split form).  With `autotune`, the step is captured once per setting of the
@@ -697,7 +764,7 @@ class TrainStep(Step):
             _lib.call("rd_set_rowgemm_rows32", r32)
             _lib.call("rd_set_rowgemm_waves16", w16)
             self._capture_one()
-            graphs = (self.graph, self.graph_b)
+            graphs = (self.graph, self.graph_b, self.graph_close, self.graph_b_close)   # (timed: the first two, a non-closing position)
 
             def replay():
                 graphs[0].replay()
@@ -723,28 +790,48 @@ class TrainStep(Step):
             alt_t = agree([alt[0]])[0]
             if alt_t < best_t:
                 best_w16, best_graphs, best_t = w16, alt[1], alt_t
-        self.graph, self.graph_b = best_graphs
+        self.graph, self.graph_b, self.graph_close, self.graph_b_close = best_graphs
         self.tuned_rows32, self.tuned_waves16 = best_r32, best_w16
         _lib.call("rd_set_rowgemm_rows32", best_r32)                 # eager calls of this process follow the same choice
         _lib.call("rd_set_rowgemm_waves16", best_w16)
 
 
+    def _enqueue_whole(self, closing=True):
+        """the step as one piece: feed gather, body, the window's launch, feed record"""
+        self._feed_gather()
+        self._body()
+        self._window_tail(closing)
+        self._feed_record()
+
+    def _enqueue_first(self, closing=True):
+        """the split form's first half: everything up to the point where the gradients from early_grad_offset() on are final"""
+        self._feed_gather()
+        self._body("a")
+        self._window_tail(closing, "a")
+
+    def _enqueue_second(self, closing=True):
+        self._body("b")
+        self._window_tail(closing, "b")
+        self._feed_record()
+
     def _capture_one(self):
-        def whole():
-            self._feed_gather()
-            self._body()
-            self._feed_record()
+        """`graph` (+ `graph_b`, split form): the step.  With accumulate > 1 these are the graphs of a window's positions 0 .. k-2
+        and `graph_close` (+ `graph_b_close`) those of position k-1: the same body captured twice, out of one pool."""
+        whole, first, second = self._enqueue_whole, self._enqueue_first, self._enqueue_second
+        micro = lambda fn: (lambda: fn(False))
 
-        def first():
-            self._feed_gather()
-            self._body("a")
-
-        def second():
-            self._body("b")
-            self._feed_record()
+        def both():                                                        # warm-up: one non-closing and one closing position
+            whole(False)
+            whole(True)
 
         def cap():
-            if self.split:
+            self.graph_close = self.graph_b_close = None
+            if self.acc is not None and self.split:
+                self.graph, self.graph_b, self.graph_close, self.graph_b_close = capture_graphs(
+                    [micro(first), micro(second), first, second], warm=both)
+            elif self.acc is not None:
+                (self.graph, self.graph_close), self.graph_b = capture_graphs([micro(whole), whole], warm=both), None
+            elif self.split:
                 self.graph, self.graph_b = capture_graphs([first, second], warm=whole)
             else:
                 (self.graph,), self.graph_b = capture_graphs([whole]), None
@@ -812,31 +899,35 @@ class TrainStep(Step):
     def run(self, between=None):
         """One forward + loss + backward; gradients land in flat.flat (p.grad views point there).  `between` (split form only) is
         called after the first graph has been enqueued and before the second: gradients at flat offsets >= early_grad_offset() are
-        complete in stream order at that point."""
+        complete in stream order at that point.
+        accumulate > 1: one MICRO-batch.  On positions 0 .. k-2 of a window flat.flat holds this micro-batch's own gradient
+        afterwards (and the accumulator has taken it in); on position k-1 it holds the window's mean -- at `between`, already from
+        early_grad_offset() on -- and `window_closed` is True: step the optimizer."""
         if self._param_ptrs() != self._ptrs:
             raise _lib.RaindropHipError("TrainStep: a parameter or gradient buffer moved since construction (model.to(), "
                                         "flatten_parameters() or a re-assignment): build a new TrainStep")
         if self.feed is not None:
             self.feed._take("TrainStep.run")
+        closing = self._closing_next()
         if self.graph is not None:
-            self.graph.replay()
-            if self.graph_b is not None:
+            first, second = (self.graph_close, self.graph_b_close) if closing and self.acc is not None else (self.graph, self.graph_b)
+            first.replay()
+            if second is not None:
                 if between is not None:
                     between()
-                self.graph_b.replay()
+                second.replay()
         else:
             def eager():
                 with torch.no_grad():
-                    self._feed_gather()
                     if self.split:
-                        self._body("a")
+                        self._enqueue_first(closing)
                         if between is not None:
                             between()
-                        self._body("b")
+                        self._enqueue_second(closing)
                     else:
-                        self._body()
-                    self._feed_record()
+                        self._enqueue_whole(closing)
             self._with_cell(eager)
+        self._advance_window(closing)
         for p, v in zip(self.flat.params, self.flat.views):
             p.grad = v
         return self.loss
@@ -844,8 +935,12 @@ class TrainStep(Step):
     def run_allreduce(self):
         """run() + the gradient all-reduce of `flat` (no-op for one process).  Split form: the collective of the gradients the first
         graph completes (last encoder layer + head: ~0.8 of 2.0 MB at P19) is started between the two graphs and runs beside the
-        rest of the backward pass; the remainder follows the second graph.  Returns the loss tensor."""
+        rest of the backward pass; the remainder follows the second graph.  Returns the loss tensor.
+        accumulate > 1: only the call that closes a window reduces (the window's mean; in the split form with the same overlap);
+        on the other positions no collective is issued at all.  `window_closed` tells the caller which it was."""
         flat = self.flat
+        if not self._closing_next():
+            return self.run()
         if not self.split:
             loss = self.run()
             flat.allreduce()
@@ -866,7 +961,11 @@ class TrainStep(Step):
         joined behind the second one's -- the collectives' own stream forks from and joins the captured stream (RCCL supports
         stream capture; tested on a one-rank group: tests/test_dp_gpu.py) --, then `opt.step_captured()` (FlatAdam: device step
         cell + rd_adam_step_dev).  The host side of a step is then ONE replay (run_full).  Raises whatever the capture raises;
-        the caller falls back to run_allreduce() + opt.step()."""
+        the caller falls back to run_allreduce() + opt.step().
+        accumulate > 1: TWO graphs out of one pool -- `graph_full_micro` for positions 0 .. k-2 of a window (feed gather, body,
+        rd_grad_accumulate, feed record: the optimizer's step cell is not registered, no collective, no update) and `graph_full`
+        for position k-1, which is the graph above with rd_grad_accumulate_close in front of the collective(s).  The accumulator
+        and the window position are kept across the capture."""
         flat = self.flat
         opt.sync_cells(full=True)                                          # the device step state and the cells of whatever the optimizer has on
         # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
@@ -874,8 +973,11 @@ class TrainStep(Step):
         begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
 
         def warm():                                                        # outside the capture: RCCL's lazy inits, too
+            if self.acc is not None:
+                self._enqueue_whole(False)                                 # (a non-closing position and its launch)
             self._feed_gather()
             self._body()
+            self._window_tail(True)
             flat.allreduce()
             self._feed_record()
 
@@ -887,21 +989,29 @@ class TrainStep(Step):
                 off = self.early_grad_offset()
                 self._body("a")
                 opt.register_cell(False)
+                self._window_tail(True, "a")                               # the window's mean in the range the collective takes
                 h1 = flat.allreduce_range_async(off, flat.flat.numel())
                 self._body("b")
+                self._window_tail(True, "b")
                 h0 = flat.allreduce_range_async(0, off)
                 flat.allreduce_wait(h1)
                 flat.allreduce_wait(h0)
             else:
                 self._body()
                 opt.register_cell(False)
+                self._window_tail(True)
                 flat.allreduce()
             opt.step_captured(advance=not begin_adv)
             self._feed_record()
 
         def cap():
             try:
-                self.graph_full, = capture_graphs([whole], warm=warm)
+                if self.acc is not None:
+                    # positions 0 .. k-2: feed gather, body, accumulate, feed record -- the optimizer's cell is not registered (its
+                    # step state stays), no collective, no update
+                    self.graph_full_micro, self.graph_full = capture_graphs([lambda: self._enqueue_whole(False), whole], warm=warm)
+                else:
+                    self.graph_full, = capture_graphs([whole], warm=warm)
             finally:
                 opt.register_cell(False)
         with self._feed_kept():
@@ -912,8 +1022,13 @@ class TrainStep(Step):
         self.captures += 1
         return self.graph_full
 
-    def run_full(self):
-        """One replay of capture_full's graph = one training step including the optimizer; returns the loss tensor."""
+    def run_full(self, close_window=False):
+        """One replay of capture_full's graph = one training step including the optimizer; returns the loss tensor.
+        accumulate > 1: one MICRO-batch -- a replay of the micro graph on positions 0 .. k-2 of a window, of the closing graph (the
+        collectives, the update; `opt.t`, the schedule and the EMA count move) on position k-1; the optimizer's cells are synchronised
+        and its host count advanced on closing replays only.  close_window=True closes the window with THIS micro-batch wherever
+        it stands (an epoch's last, shorter window): 1 / (position + 1) goes into the scale cell (a stream-ordered 4-byte write),
+        the closing graph is replayed and 1/k is put back."""
         if self.graph_full is None:
             raise _lib.RaindropHipError("TrainStep.run_full: call capture_full(opt) first")
         if self._param_ptrs() != self._ptrs:
@@ -925,18 +1040,28 @@ class TrainStep(Step):
             cell = self.seed_cell.clone()                                  # Adam -- capture again
             self.capture_full(self._full_opt)                              # (the warm-up passes advance the dropout stream: put it back)
             self.seed_cell.copy_(cell)
-        self._full_opt.sync_cells()                                        # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259; warm-up /
+        closing = bool(close_window) or self._closing_next()
+        if not closing:                                                    # (accumulate > 1) nothing of the optimizer's moves
+            self.graph_full_micro.replay()
+        else:
+            self._full_opt.sync_cells()                                    # lr / weight decay (ReduceLROnPlateau, code/Raindrop.py:257-259; warm-up /
                                                                            # cosine schedules), threshold, decay: 8-byte copies, no new capture; and
                                                                            # the step state, when host-side steps were taken since
-        self.graph_full.replay()
-        self._full_opt.note_replay()
+            short = not self._closing_next()                               # a window cut short: the mean over the micro-batches it has
+            if short:
+                self.scale_cell.fill_(1.0 / (self._pos + 1))
+            self.graph_full.replay()
+            if short:
+                self.scale_cell.fill_(1.0 / self.accumulate)
+            self._full_opt.note_replay()
+        self._advance_window(closing)
         for p, v in zip(self.flat.params, self.flat.views):
             p.grad = v
         return self.loss
 
     def close(self):
         """Kept for callers of the round-1 API: the seed cell is no longer registered outside run() / capture."""
-        self.graph = self.graph_b = self.graph_full = None
+        self.graph = self.graph_b = self.graph_full = self.graph_close = self.graph_b_close = self.graph_full_micro = None
 
 
 class AutogradStep:

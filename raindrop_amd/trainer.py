@@ -62,8 +62,10 @@ class ReduceOnPlateau:
 
 
 def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
-                    warmup_steps=0):
+                    warmup_steps=0, accumulate=1):
     """what can be refused without a device"""
+    if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+        raise ValueError("accumulate must be an integer >= 1, got %r" % (accumulate,))
     if isinstance(lr_schedule, str):
         if lr_schedule != "warmup_cosine":
             raise ValueError("lr_schedule: the only named schedule is 'warmup_cosine', got %r" % (lr_schedule,))
@@ -120,6 +122,14 @@ def _resolve_schedule(lr_schedule, warmup_steps, total_steps):
     return made
 
 
+def _window_plan(n_batches, accumulate):
+    """(optimizer steps, length of the last window) of an epoch of `n_batches` micro-batches taken `accumulate` at a time: every
+    window but the last is full, the last one takes what is left (fit closes it with run_full(close_window=True)), none is dropped"""
+    n, k = int(n_batches), int(accumulate)
+    steps = -(-n // k)
+    return steps, (n - (steps - 1) * k if steps else 0)
+
+
 def _live_names(model):
     from . import synth
     cfg = dict(static=bool(model.static), nlayers=len(model.transformer_encoder.layers))
@@ -128,7 +138,7 @@ def _live_names(model):
 
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
-        param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0):
+        param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -155,9 +165,18 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     `val_f1` -- plus `best_epoch` (None when no epoch's auroc exceeded 0) and `best_auroc`; with `lr_schedule` also `lr_step`, the
     device's rate after each epoch's last step (`lr` stays the base rate).
 
+    accumulate=k > 1: gradient accumulation (`TrainStep(accumulate=k)`): every batch of the plan is a MICRO-batch, an optimizer step
+    takes k of them (the mean of their gradients, each normalised by its own batch / class-weight sum), and an epoch's last window
+    is closed where the plan ends (`run_full(close_window=True)`: the mean over the micro-batches it has), so no micro-batch is
+    dropped and no gradient leaks into the next epoch.  Optimizer steps per epoch: ceil(n_batches / k); `lr_schedule` totals and
+    `warmup_steps` count optimizer steps.  `train_loss` / `train_accuracy` stay means over the micro-batches.  The result gains
+    `optimizer_steps` (the run's total), and `lr_step` then holds one entry per optimizer step: the rate that step applied (the
+    double product the device forms), not one per epoch.  The plateau scheduler, validation and EMA validation are untouched.
+
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
-    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps)
+    _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps,
+                    accumulate)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -174,7 +193,7 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     if param_groups is not None:
         groups = optim_mod.ParamGroups(flat, [optim_mod.no_decay(flat)] if param_groups == "no_decay" else param_groups)
     planner = feed_mod.EpochPlanner(train_ds.y.cpu().numpy(), batch_size=B, strategy=strategy, n_total=train_ds.N)
-    schedule = _resolve_schedule(lr_schedule, warmup_steps, int(epochs) * int(planner.n_batches))
+    schedule = _resolve_schedule(lr_schedule, warmup_steps, int(epochs) * _window_plan(planner.n_batches, accumulate)[0])
     opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
                    groups=groups, decoupled=decoupled_weight_decay, schedule=schedule)
     fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1))
@@ -183,6 +202,9 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     kw = dict(autotune=autotune, class_weight=class_weight, label_smoothing=label_smoothing, feed=fd)
     if seed is not None:
         kw["seed"] = int(seed)
+    if accumulate > 1:                                                     # (1: the step as it was built before the keyword)
+        kw["accumulate"] = accumulate
+    optimizer_steps = 0
     step = BetaTrainStep(model, flat, batch, distance_weight=distance_weight, **kw) if beta else TrainStep(model, flat, batch, **kw)
     sched = ReduceOnPlateau() if scheduler is True else (scheduler or None)
     if sched is not None and sched.opt is None:
@@ -197,11 +219,18 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         for epoch in range(int(epochs)):
             fd.load_epoch(planner.next_epoch())
             while fd.remaining():
-                step.run_full()
+                if accumulate == 1:
+                    step.run_full()
+                    continue
+                step.run_full(close_window=fd.remaining() == 1)            # the plan's last micro-batch closes whatever window is open
+                if step.window_closed:
+                    optimizer_steps += 1
+                    if schedule is not None:
+                        out["lr_step"].append(opt._step_lr())
             loss, correct = fd.history()
             out["train_loss"].append(float(loss.mean()) if loss.size else float("nan"))
             out["train_accuracy"].append(float(correct.sum()) / max(correct.size * B, 1))
-            if schedule is not None:
+            if schedule is not None and accumulate == 1:
                 out["lr_step"].append(opt.current_lr())
             v = feed_mod.validate_ema(model, val_ds, opt, **vkw) if ema_decay is not None else feed_mod.validate(model, val_ds, **vkw)
             for f in VAL_FIELDS:
@@ -219,4 +248,6 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         step.close()
         model.train(was_training)
     out["best_epoch"], out["best_auroc"] = best_epoch, best_auroc
+    if accumulate > 1:
+        out["optimizer_steps"] = optimizer_steps
     return out
