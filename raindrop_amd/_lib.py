@@ -215,6 +215,8 @@ DEBUG_SIGNATURES = {
     # M, N, K, sa_m, sa_k, sb_n, sb_k, nsplit, k_per_split, tile_hint, flags (GEMM_ROUTE_FLAGS), words[5], name, cap
     "rd_debug_gemm_route": (c_int32, [c_int32] * 3 + [ctypes.c_int64] * 4 + [c_int32] * 3 + [ctypes.c_uint32, _P, _P, c_size_t]),
     "rd_debug_splitk_plan": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P]),      # red, rows, cols, *k_per_split -> nsplit
+    # mode, B, D, d_static, Fe, C, with_crit, words[11] (bits of words[0]: HEAD_ROUTE_BITS below), name, cap
+    "rd_debug_head_route": (c_int32, [c_int32] * 7 + [_P, _P, c_size_t]),
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
@@ -229,6 +231,8 @@ GEMM_FAMILIES = (None, "fp32", "bf16x3", "panel")
 GEMM_MAPS = ("xcd", "rowmajor", "slice_xcd", "zgrid")
 GEMM_TILES = ("64x64", "128x64", "128x128", "64x128", "64x160")
 GEMM_PANEL_FORMS = ("small", "wide", "pc")
+# bit i of rd_debug_head_route's words[0] (csrc/rd_head.hip HeadRoute); bits 8-9: the trailing launch's weight-gradient jobs
+HEAD_ROUTE_BITS = ("narrow", "crit", "emb_lds")
 
 _lib = None
 

@@ -475,6 +475,57 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
                        const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                        float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream);
 
+// ---- the route: every decision of one head call, taken ONCE, from the sizes alone (head_launch runs it; rd_debug_head_route,
+// include/raindrop_hip_debug.h, reports it) ----
+struct HeadRoute {
+  bool narrow;                     // k_head_rows<1, 12, 3, .>: W0 fetched as 192 x 192; else <1, 16, 4, .>: 256 x 256
+  bool crit;                       // the CRIT instantiations
+  bool emb_lds;                    // the static embedding's operands are staged in LDS (else read in place)
+  int touch_bytes;                 // own-code touch of the instantiation (0: RD_CODE_TOUCH=0)
+  int grid;                        // workgroups of k_head_rows: one sample each
+  int njobs;                       // trailing launch: weight-gradient jobs (0: rd_head_forward has none) -- d mlp_static[0], [2], d emb
+  struct { int N, K, tiles_n, tiles_k, blk0; } job[3];
+  int ntiles;                      // workgroups of k_head_wgrad: 16 x 16 output tiles over all jobs
+  int rider_blocks;                // 1024-thread blocks of the deferred form (rd_trailing.h: four tiles per block)
+  const char* name;                // what the launch reports to the error check and the launch log
+};
+
+// one name per instantiation: the launch log tells the four k_head_rows apart
+static const char* head_name(const HeadRoute& r) {
+  if (r.crit) return r.narrow ? "k_head_rows<12,3,crit>" : "k_head_rows<16,4,crit>";
+  return r.narrow ? "k_head_rows<12,3>" : "k_head_rows<16,4>";
+}
+
+static HeadRoute head_route(int mode, int B, int D, int d_static, int Fe, int C, bool crit) {
+  // own-code touch: 14.5 KB of the 15.4 KB <1, 12, 3> kernel, 16 KB of the 16.9 KB generic one (tests/test_kernel_resources.py keeps the
+  // constants below the code lengths); RD_CODE_TOUCH=0 switches it off (A/B)
+  static const int touch = [] { const char* e = getenv("RD_CODE_TOUCH"); return e ? atoi(e) : 1; }();
+  // one sample per workgroup (B workgroups: every CU busy at B = 256); two samples per workgroup measured inside the noise twice
+  // (rounds 2 and 4) and is no longer built (its hid phase spilled at 128 registers).
+  // W0 fetched as 192 x 192 where that covers it (P19: dh = 186), else 256 x 256 (RD_HEAD_NARROW=0: always the latter)
+  static const int narrow = [] { const char* e = getenv("RD_HEAD_NARROW"); return e ? atoi(e) : 1; }();
+  const int dh = D + Fe;
+  HeadRoute r{};
+  r.narrow = narrow && dh <= 192;
+  r.crit = crit;                                                       // the criterion instantiations: touch lengths of their own
+  // the kernel's own predicate (k_head_rows: `const bool emb_lds = ...`), restated: the kernel bodies are not touched by the route
+  r.emb_lds = Fe > 0 && Fe * d_static <= HR_EMBW && d_static <= HR_DS;
+  r.touch_bytes = !touch ? 0 : crit ? (r.narrow ? RD_TL_HEAD_P19_C : RD_TL_HEAD_C) : (r.narrow ? RD_TL_HEAD_P19 : RD_TL_HEAD);
+  r.grid = B;
+  r.name = head_name(r);
+  if (mode == 1) return r;                                             // rd_head_forward: the logits are the result
+  int blk = 0;
+  auto add = [&](int N, int K) {
+    auto& J = r.job[r.njobs++];
+    J.N = N; J.K = K; J.tiles_n = cdiv(N, 16); J.tiles_k = cdiv(K, 16); J.blk0 = blk; blk += J.tiles_n * J.tiles_k;
+  };
+  add(dh, dh);                                                         // d mlp_static[0]
+  add(C, dh);                                                          // d mlp_static[2]
+  if (Fe) add(Fe, d_static);                                           // d emb
+  r.ntiles = blk; r.rider_blocks = cdiv(blk, 4);
+  return r;
+}
+
 extern "C" int rd_head_train(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
                              const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w,
                              const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
@@ -543,39 +594,55 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
   a.dlog = a.demb + (size_t)B * dh; a.lossr = a.dlog + (size_t)B * C;
   a.T = s->T; a.B = B; a.D = D; a.ds = d_static; a.Fe = Fe; a.dh = dh; a.C = C;
   a.plan = token_plan(); a.stamps = g_head_stamps;
-  // own-code touch: 14.5 KB of the 15.4 KB <1, 12, 3> kernel, 16 KB of the 16.9 KB generic one (tests/test_kernel_resources.py keeps the
-  // constants below the code lengths); RD_CODE_TOUCH=0 switches it off (A/B)
-  static const int touch = [] { const char* e = getenv("RD_CODE_TOUCH"); return e ? atoi(e) : 1; }();
-  // one sample per workgroup (B workgroups: every CU busy at B = 256); two samples per workgroup measured inside the noise twice
-  // (rounds 2 and 4) and is no longer built (its hid phase spilled at 128 registers).
-  // W0 fetched as 192 x 192 where that covers it (P19: dh = 186), else 256 x 256 (RD_HEAD_NARROW=0: always the latter)
-  static const int narrow = [] { const char* e = getenv("RD_HEAD_NARROW"); return e ? atoi(e) : 1; }();
-  if (crit) {                                                          // the criterion instantiations: touch lengths of their own
-    if (narrow && dh <= 192) { a.touch_bytes = touch ? RD_TL_HEAD_P19_C : 0; hipLaunchKernelGGL((k_head_rows<1, 12, 3, true>), dim3(B), dim3(HR_THR), 0, st, a); }
-    else { a.touch_bytes = touch ? RD_TL_HEAD_C : 0; hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, true>), dim3(B), dim3(HR_THR), 0, st, a); }
-  } else if (narrow && dh <= 192) { a.touch_bytes = touch ? RD_TL_HEAD_P19 : 0; hipLaunchKernelGGL((k_head_rows<1, 12, 3, false>), dim3(B), dim3(HR_THR), 0, st, a); }
-  else { a.touch_bytes = touch ? RD_TL_HEAD : 0; hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, false>), dim3(B), dim3(HR_THR), 0, st, a); }
-  int rc = check_launch("k_head_rows");
+  const HeadRoute rt = head_route(mode, B, D, d_static, Fe, C, crit != nullptr);
+  a.touch_bytes = rt.touch_bytes;
+  if (rt.crit) {
+    if (rt.narrow) hipLaunchKernelGGL((k_head_rows<1, 12, 3, true>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+    else hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, true>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+  } else if (rt.narrow) hipLaunchKernelGGL((k_head_rows<1, 12, 3, false>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+  else hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, false>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+  int rc = check_launch(rt.name);
   if (rc || mode == 1) return rc;
   HwArgs h{};
   h.B = B; h.lossr = a.lossr; h.loss = loss;             // loss == null (rd_head_backward): no loss mean
-  int blk = 0, n = 0;
-  auto add = [&](const float* u, int ldu, int N, const float* v, int ldv, int K, float* dW, float* db) {
-    HwJob& J = h.j[n++];
-    J.u = u; J.ldu = ldu; J.N = N; J.v = v; J.ldv = ldv; J.K = K; J.dW = dW; J.db = db;
-    J.tiles_k = cdiv(K, 16); J.blk0 = blk; blk += cdiv(N, 16) * J.tiles_k;
+  int n = 0;
+  auto add = [&](const float* u, int ldu, const float* v, int ldv, float* dW, float* db) {     // job n of the route: its operands
+    HwJob& J = h.j[n];
+    J.u = u; J.ldu = ldu; J.N = rt.job[n].N; J.v = v; J.ldv = ldv; J.K = rt.job[n].K; J.dW = dW; J.db = db;
+    J.tiles_k = rt.job[n].tiles_k; J.blk0 = rt.job[n].blk0;
+    ++n;
   };
-  add(a.dhid, dh, dh, a.feat, dh, dh, g_w0, g_b0);                       // d mlp_static[0]
-  add(a.dlog, C, C, a.hid, dh, dh, g_w2, g_b2);                          // d mlp_static[2]
-  if (Fe) add(a.demb, Fe, Fe, stat, d_static, d_static, g_emb_w, g_emb_b);   // d emb
-  h.n = n; h.ntiles = blk;
+  add(a.dhid, dh, a.feat, dh, g_w0, g_b0);                               // d mlp_static[0]
+  add(a.dlog, C, a.hid, dh, g_w2, g_b2);                                 // d mlp_static[2]
+  if (Fe) add(a.demb, Fe, stat, d_static, g_emb_w, g_emb_b);             // d emb
+  h.n = rt.njobs; h.ntiles = rt.ntiles;
   // weight gradients + the loss mean: nothing in the backward chain reads them.  Deferred mode: parked for the next backward chain
   // launch's idle workgroups (rd_trailing.h: four tiles per 1024-thread block); else side branch if registered, else here.
   if (trailing_deferred()) {
     RiderArgs r{};
-    r.kind = RIDER_HEAD; r.nblocks = cdiv(blk, 4); r.hw = h;
+    r.kind = RIDER_HEAD; r.nblocks = rt.rider_blocks; r.hw = h;
     return trailing_park(r, st);
   }
-  hipLaunchKernelGGL(k_head_wgrad, dim3(blk), dim3(256), 0, side_fork(st), h);
+  hipLaunchKernelGGL(k_head_wgrad, dim3(rt.ntiles), dim3(256), 0, side_fork(st), h);
   return check_launch("k_head_wgrad");
+}
+
+// include/raindrop_hip_debug.h: the route above by value; needs no device
+extern "C" int rd_debug_head_route(int32_t mode, int32_t B, int32_t D, int32_t d_static, int32_t Fe, int32_t C, int32_t with_crit,
+                                   uint32_t* words, char* name, size_t cap) {
+  RD_REQUIRE(words && name && cap > 0, "NULL output");
+  for (int i = 0; i < 11; ++i) words[i] = 0;
+  name[0] = 0;
+  RD_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && (!with_crit || mode == 0), "bad mode / shape");
+  RD_REQUIRE(rd_head_train_supported(D, Fe, C), "head_train: unsupported sizes D=%d Fe=%d C=%d", D, Fe, C);
+  RD_REQUIRE(Fe == 0 || d_static > 0, "static embedding tensors missing");
+  const HeadRoute r = head_route(mode, B, D, d_static, Fe, C, with_crit != 0);
+  words[0] = (r.narrow ? 1u : 0u) | (r.crit ? 2u : 0u) | (r.emb_lds ? 4u : 0u) | ((unsigned)r.njobs << 8);
+  words[1] = (uint32_t)r.touch_bytes; words[2] = (uint32_t)r.grid; words[3] = (uint32_t)r.ntiles; words[4] = (uint32_t)r.rider_blocks;
+  for (int i = 0; i < r.njobs; ++i) {
+    words[5 + i] = (uint32_t)r.job[i].blk0;
+    words[8 + i] = ((uint32_t)r.job[i].tiles_n << 16) | (uint32_t)r.job[i].tiles_k;
+  }
+  snprintf(name, cap, "%s", r.name);
+  return RD_OK;
 }
