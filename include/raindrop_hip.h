@@ -545,6 +545,20 @@ int rd_softmax_xent(int32_t B, int32_t C, const float* logits, const int64_t* y,
  * torch); a label outside [0, C) gives a NaN loss and reads nothing out of bounds.  B < 2^24. */
 int rd_softmax_xent_crit(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
                          float* dlogits, void* stream);
+/* The focal loss (Lin et al., "Focal Loss for Dense Object Detection") with class weights, forward + backward in one launch, any C.
+ * crit = [gamma, w_0 .. w_{C-1}] (C + 1 floats on the device, read when the kernel runs; gamma finite in [0, 16], w_c >= 0);
+ * p = softmax(logits[b]), logp_y = logits[b,y_b] - logsumexp(logits[b]), W = sum_b w[y_b]:
+ *   q_b          = sum over c != y_b, ascending, of p[b,c]        (NOT 1 - p[b,y_b]: no cancellation when p[b,y_b] -> 1)
+ *   m_b          = q_b^gamma                                      (gamma == 0: exactly 1; q_b == 0 and gamma > 0: exactly 0)
+ *   g_b          = m_b - gamma p[b,y_b] q_b^(gamma - 1) logp_y    (gamma == 0: exactly 1; q_b == 0 and gamma > 0: exactly 0; the
+ *                                                                   second term exactly 0 where logp_y has rounded to 0: never 0 * inf)
+ *   loss[0]      = sum_b w[y_b] m_b (-logp_y) / W
+ *   dlogits[b,c] = (p[b,c] - [c == y_b]) g_b w[y_b] / W
+ * W is rd_softmax_xent_crit's (per-class label counts, sum over c ascending of n_c w_c) and so is the order of the factors: with
+ * gamma = 0 loss and dlogits are rd_softmax_xent_crit's at eps = 0 bit for bit (CrossEntropyLoss(weight = w); the plain mean at
+ * w = 1).  W == 0 gives NaN; a label outside [0, C) gives a NaN loss and reads nothing out of bounds.  B < 2^24. */
+int rd_softmax_xent_focal(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
+                          float* dlogits, void* stream);
 /* Tuning knob of the encoder's row-block products (process-global, read when a product is enqueued): bit mask of the kernel
  * variants that run on 32-row instead of 64-row workgroups (1: K <= 160, 2: K <= 288, 4: LayerNorm epilogue, 8: LayerNorm-
  * backward prologue); -1 restores the default (environment RD_RG_ROWS32, else 15).  Results do not depend on it beyond
@@ -582,6 +596,16 @@ int rd_head_train_crit(const rd_shape* s, int32_t D, int32_t d_static, int32_t F
                        const int64_t* y, const float* crit, float* loss, float* logits, float* g_emb_w, float* g_emb_b,
                        float* g_w0, float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* rd_head_train with rd_softmax_xent_focal's loss (crit = [gamma, w_0 .. w_{C-1}] on the device, read when the kernels run: a
+ * captured step changes gamma and the weights by a copy into that buffer).  rd_head_train_crit's argument list, support test and
+ * workspace; focal instantiations of its first kernel on the same label count and W -- no atomics, the same bits in every launch.
+ * With gamma = 0: loss, logits, dr and the six parameter gradients are rd_head_train_crit's at eps = 0 bit for bit.  B < 2^24. */
+int rd_head_train_focal(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
+                        const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w,
+                        const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                        const int64_t* y, const float* crit, float* loss, float* logits, float* g_emb_w, float* g_emb_b,
+                        float* g_w0, float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
+                        void* stream);
 /* The same head around a loss the CALLER evaluates -- the reference's loop: outputs = model(..); loss = criterion(outputs, y);
  * loss.backward() (code/Raindrop.py:317-323).  rd_head_forward stops at the logits; rd_head_backward recomputes the head's
  * forward phases (a masked mean and two small products) and continues from the caller's d loss / d logits [B,C].  Same kernel,

@@ -72,9 +72,10 @@ int rd_debug_splitk_plan(int64_t red, int32_t rows, int32_t cols, int32_t* k_per
 /* The route one fused-head call takes (rd_head.hip head_route, the function the launch site calls) under the RD_HEAD_NARROW /
  * RD_CODE_TOUCH settings of the moment.  mode: 0 rd_head_train (with_crit: rd_head_train_crit), 1 rd_head_forward, 2 rd_head_backward.
  * Needs no device.  Returns RD_OK or the error of sizes the head refuses.  The launch-log name of the k_head_rows instantiation goes
- * to name[cap] -- "k_head_rows<12,3>", "k_head_rows<16,4>", each also as "...,crit>" -- and
+ * to name[cap] -- "k_head_rows<12,3>", "k_head_rows<16,4>", each also as "...,crit>" and (with_crit == 2: rd_head_train_focal)
+ * "...,focal>" -- and
  *    words[0]  bit 0 narrow (W0 fetched as 192 x 192: <1, 12, 3>, else <1, 16, 4>), 1 crit, 2 emb_lds (static embedding staged in LDS,
- *              else read in place), bits 8-9 the weight-gradient jobs of the trailing launch (0: mode 1 has none)
+ *              else read in place), 3 focal, bits 8-9 the weight-gradient jobs of the trailing launch (0: mode 1 has none)
  *    words[1]  own-code touch bytes        words[2]  workgroups of k_head_rows        words[3]  workgroups (tiles) of k_head_wgrad
  *    words[4]  1024-thread blocks of the deferred form (rd_set_defer_trailing)
  *    words[5 + j]  first tile blk0 of job j (d mlp_static[0], d mlp_static[2], d emb)   words[8 + j]  its tiles: n << 16 | k */

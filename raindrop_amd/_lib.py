@@ -145,12 +145,14 @@ SIGNATURES = {
     "rd_linear_bwd_input_gated": (c_int32, [c_int32, c_int32, c_int32, _P, c_int32, _P, _P, c_int32, _P, c_int32, _P]),
     "rd_softmax_xent": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P]),
     "rd_softmax_xent_crit": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),
+    "rd_softmax_xent_focal": (c_int32, [c_int32, c_int32, _P, _P, _P, _P, _P, _P]),      # crit = [gamma, w_0 ..]
     "rd_set_rowgemm_rows32": (c_int32, [c_int32]),
     "rd_set_rowgemm_waves16": (c_int32, [c_int32]),
     "rd_head_train_supported": (c_int32, [c_int32, c_int32, c_int32]),
     "rd_head_train_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "rd_head_train": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 20 + [_P, c_size_t, _P]),
     "rd_head_train_crit": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 21 + [_P, c_size_t, _P]),
+    "rd_head_train_focal": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 21 + [_P, c_size_t, _P]),
     "rd_head_forward": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 11 + [_P, c_size_t, _P]),
     "rd_head_backward": (c_int32, [_SHP, c_int32, c_int32, c_int32, c_int32] + [_P] * 18 + [_P, c_size_t, _P]),
     "rd_batch_gather": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64] + [_P] * 12),
@@ -215,7 +217,7 @@ DEBUG_SIGNATURES = {
     # M, N, K, sa_m, sa_k, sb_n, sb_k, nsplit, k_per_split, tile_hint, flags (GEMM_ROUTE_FLAGS), words[5], name, cap
     "rd_debug_gemm_route": (c_int32, [c_int32] * 3 + [ctypes.c_int64] * 4 + [c_int32] * 3 + [ctypes.c_uint32, _P, _P, c_size_t]),
     "rd_debug_splitk_plan": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P]),      # red, rows, cols, *k_per_split -> nsplit
-    # mode, B, D, d_static, Fe, C, with_crit, words[11] (bits of words[0]: HEAD_ROUTE_BITS below), name, cap
+    # mode, B, D, d_static, Fe, C, with_crit (2: the focal form), words[11] (bits of words[0]: HEAD_ROUTE_BITS below), name, cap
     "rd_debug_head_route": (c_int32, [c_int32] * 7 + [_P, _P, c_size_t]),
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
@@ -232,7 +234,7 @@ GEMM_MAPS = ("xcd", "rowmajor", "slice_xcd", "zgrid")
 GEMM_TILES = ("64x64", "128x64", "128x128", "64x128", "64x160")
 GEMM_PANEL_FORMS = ("small", "wide", "pc")
 # bit i of rd_debug_head_route's words[0] (csrc/rd_head.hip HeadRoute); bits 8-9: the trailing launch's weight-gradient jobs
-HEAD_ROUTE_BITS = ("narrow", "crit", "emb_lds")
+HEAD_ROUTE_BITS = ("narrow", "crit", "emb_lds", "focal")
 
 _lib = None
 

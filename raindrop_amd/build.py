@@ -61,6 +61,8 @@ TOUCH_SITES = [
     ("HEAD_P19", r"k_head_rowsILi1ELi12ELi3ELb0E", "step"), ("HEAD", r"k_head_rowsILi1ELi16ELi4ELb0E", "step"),
     # the criterion twins (template flag CRIT: class weights / label smoothing): lengths of their own, the plain ones keep theirs
     ("HEAD_P19_C", r"k_head_rowsILi1ELi12ELi3ELb1E", "step"), ("HEAD_C", r"k_head_rowsILi1ELi16ELi4ELb1E", "step"),
+    # the focal-loss twins (k_head_rows_focal: the same body with the focal loss block): lengths of their own again
+    ("HEAD_P19_F", r"k_head_rows_focalILi1ELi12ELi3EE", "step"), ("HEAD_F", r"k_head_rows_focalILi1ELi16ELi4EE", "step"),
     ("GEMM", r"6k_gemmI", "x"), ("GEMM_X3", r"13k_gemm_bf16x3I", "x"), ("GEMM_PANEL", r"12k_gemm_panelI", "x"), ("GEMM_PANEL_WIDE", r"17k_gemm_panel_wideI", "x"), ("GEMM_PANEL_PC", r"15k_gemm_panel_pcI", "x"), ("ROWGEMM", r"9k_rowgemmI", "x"),
     ("ATTN_FWD_ONE", r"19k_attn_fwd_one_b16wI", "x"), ("ATTN_BWD_ONE", r"19k_attn_bwd_one_b16wI", "x"), ("ATTN_FWD_B16", r"14k_attn_fwd_b16I", "x"),
     ("ATTN_BWD_DQ", r"17k_attn_bwd_dq_b16I", "x"), ("ATTN_BWD_DKV", r"18k_attn_bwd_dkv_b16I", "x"), ("ADD_LN_FWD", r"14k_add_ln_fwd_vE", "x"),

@@ -351,7 +351,89 @@ __global__ __launch_bounds__(256) void k_softmax_xent_crit(const float* __restri
   }
   if (tid == 0) *loss = red[0] * invB;
 }
+
+// The focal loss (Lin et al.) with class weights, forward + backward; crit = [gamma, w_0 .. w_{C-1}], p = softmax(logits[b]):
+//   q_b     = sum over c != y_b ascending of p[b,c]      (not 1 - p[b,y_b]: no cancellation when p[b,y_b] -> 1)
+//   m_b     = q_b^gamma,   g_b = m_b - gamma p[b,y_b] q_b^(gamma - 1) log p[b,y_b]                      (rd_common.h focal_factors)
+//   loss    = sum_b w[y_b] m_b (-log p[b,y_b]) / W,                                                      W = sum_b w[y_b]
+//   dl[b,c] = (p[b,c] - [c == y_b]) g_b w[y_b] / W
+// k_softmax_xent_crit with m_b and g_b where (1 - eps) stands and no smoothing term: W, the factor order, the scaling by B / W and
+// the tree are that kernel's, so at gamma = 0 (m_b = g_b = 1.0f exactly) loss and dlogits are its bits at eps = 0.  It is also the
+// arithmetic of the fused head's FOCAL instantiations (rd_head.hip).
+__global__ __launch_bounds__(256) void k_softmax_xent_focal(const float* __restrict__ logits, const int64_t* __restrict__ y,
+                                                            const float* __restrict__ crit, float* __restrict__ loss,
+                                                            float* __restrict__ dlogits, int B, int C) {
+  __shared__ float red[256];
+  __shared__ int cnt[256];
+  __shared__ float wsum[1];
+  const int tid = threadIdx.x;
+  const float* w = crit + 1;
+  float Wn = 0.f;                                          // thread 0's
+  for (int c0 = 0; c0 < C; c0 += 256) {
+    cnt[tid] = 0;
+    __syncthreads();
+    for (int b = tid; b < B; b += 256) {
+      const long yb = (long)y[b];
+      if (yb >= c0 && yb < min(c0 + 256, C)) atomicAdd(&cnt[(int)(yb - c0)], 1);
+    }
+    __syncthreads();
+    if (tid == 0)
+      // n_c w_c rounded, THEN added (no fused multiply-add): the fused head stores the products (nws) before it sums them, and
+      // k_softmax_xent_crit's sum is compiled that way -- one W for all of them
+      for (int c = c0; c < min(c0 + 256, C); ++c) {
+#pragma clang fp contract(off)
+        const float nw = (float)cnt[c - c0] * w[c];
+        Wn = Wn + nw;
+      }
+    __syncthreads();
+  }
+  if (tid == 0) wsum[0] = Wn;
+  __syncthreads();
+  Wn = wsum[0];
+  const float gamma = crit[0], invB = 1.0f / (float)B, invW = 1.0f / Wn, scale = (float)B / Wn;
+  float acc = 0.f;
+  for (int b = tid; b < B; b += 256) {
+    const float* row = logits + (long)b * C;
+    float m = row[0];
+    for (int c = 1; c < C; ++c) m = fmaxf(m, row[c]);
+    float se = 0.f;
+    for (int c = 0; c < C; ++c) se += expf(row[c] - m);
+    const float lse = m + logf(se);
+    const long yb = (long)y[b];
+    const bool yok = yb >= 0 && yb < C;
+    const int t = yok ? (int)yb : 0;
+    const float wy = w[t], fy = wy * invW, nll = lse - row[t];
+    float q = 0.f, py = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float p = expf(row[c] - lse);
+      if (c == t) py = p; else q += p;
+    }
+    float mf, gf;
+    focal_factors(gamma, q, py, nll, mf, gf);
+    const float term = mf * (wy * nll);
+    acc += yok ? term * scale : __builtin_nanf("");
+    for (int c = 0; c < C; ++c) {
+      const float p = expf(row[c] - lse);
+      dlogits[(long)b * C + c] = ((p - (c == t ? 1.f : 0.f)) * gf) * fy;
+    }
+  }
+  red[tid] = acc;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) *loss = red[0] * invB;
+}
 }  // namespace
+
+extern "C" int rd_softmax_xent_focal(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
+                                     float* dlogits, void* stream) {
+  RD_REQUIRE(B > 0 && C > 0 && B < (1 << 24), "bad dims B=%d C=%d", B, C);
+  RD_REQUIRE(logits && y && crit && loss && dlogits, "NULL tensor");
+  hipLaunchKernelGGL(k_softmax_xent_focal, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, y, crit, loss, dlogits, B, C);
+  return check_launch("k_softmax_xent_focal");
+}
 
 extern "C" int rd_softmax_xent_crit(int32_t B, int32_t C, const float* logits, const int64_t* y, const float* crit, float* loss,
                                     float* dlogits, void* stream) {

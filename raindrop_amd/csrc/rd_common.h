@@ -178,6 +178,27 @@ __device__ __forceinline__ float wave_sum64_dpp(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
+// The two per-sample factors of the focal loss (Lin et al.; rd_head.hip FOCAL instantiations, rd_api.hip k_softmax_xent_focal):
+//   m = q^gamma                                   the factor of the sample's cross entropy nll = -log p_y
+//   g = m + gamma p_y q^(gamma - 1) nll           the factor of (softmax - onehot): d(m nll) / d logits = g (p - onehot)
+// q is the SUM of the other classes' probabilities, not 1 - p_y (no cancellation when p_y -> 1).  gamma == 0: both exactly 1 (the
+// weighted cross entropy, bit for bit).  q == 0 with gamma > 0: both exactly 0 -- for gamma < 1, q^(gamma - 1) is infinite there
+// and nll is 0; the limit of their product is 0.  The same limit holds where q is still positive but nll has already rounded to 0
+// (fp32: q < 2^-24, the sum of exponentials rounds to 1; q stays a positive denormal up to a logit gap of ~103, and for small
+// gamma q^(gamma - 1) overflows there): the second term is exactly 0 whenever nll == 0, never 0 * inf.  With nll > 0, q is at least
+// half an ulp of the logit and the power is finite.
+__device__ __forceinline__ void focal_factors(float gamma, float q, float py, float nll, float& m, float& g) {
+  m = 1.0f; g = 1.0f;
+  if (gamma != 0.f) {
+    if (q == 0.f) { m = 0.f; g = 0.f; }
+    else {
+      const float lq = logf(q);
+      m = expf(gamma * lq);
+      g = nll == 0.f ? m : m + gamma * py * expf((gamma - 1.0f) * lq) * nll;
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------
 // Generic fp32 GEMM on the f32-input MFMA (v_mfma_f32_16x16x4_f32: exact fp32, == fmaf chain).
 //   C(m,n) = epilogue( sum_k A(m,k) * B(n,k) )

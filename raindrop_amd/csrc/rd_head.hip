@@ -43,7 +43,8 @@ struct HeadArgs {
   const int32_t* plan;             // token plan (rd_plan.h) or null: r / dr hold the live rows only, sample b at rows off[rank[b]] + t
   unsigned long long* stamps;      // debug (tools/head_timing.py): clock64 per phase, thread 0 of workgroup 0
   int touch_bytes;                 // > 0: bytes of this kernel's own code requested into L2 at its start (rd_common.h touch_own_code)
-  const float* crit;               // CRIT instantiations (rd_head_train_crit): [eps, w_0 .. w_{C-1}], the criterion's smoothing and class weights
+  const float* crit;               // CRIT instantiations (rd_head_train_crit): [eps, w_0 .. w_{C-1}], the criterion's smoothing and class weights;
+                                   // FOCAL instantiations (rd_head_train_focal): [gamma, w_0 .. w_{C-1}] -- the same size, the same load
 };
 static unsigned long long* g_head_stamps = nullptr;
 #define HSTAMP(i)                                                                           \
@@ -83,8 +84,14 @@ __device__ __forceinline__ float wsum64(float v) { return wave_sum64_dpp(v); }
 // kernels are the kernels as they were.  A workgroup owns one sample but the mean's denominator W = sum_b w[y_b] belongs to the
 // batch: EVERY workgroup counts the labels per class (wave ballots -- integers, no order to fix) and forms
 // W = sum over c ascending of n_c w_c, so all workgroups and any two launches get the same bits with no atomics and no ticket.
-template <int RB, int NRJ, int NKI, bool CRIT>
-__global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
+// FORM (the kernels below instantiate this body): HEAD_PLAIN, HEAD_CRIT, or HEAD_FOCAL -- the focal loss
+//   loss = sum_b w[y_b] q_b^gamma (-log p[b,y_b]) / W,   q_b = sum over c != y_b ascending of p[b,c]      (rd_common.h focal_factors)
+// on CRIT's label count and W (crs[0] carries gamma in place of eps): a third instantiation with a loss block of its own.  At
+// gamma = 0 both focal factors are an exact 1.0f and every output is the CRIT form's at eps = 0.
+constexpr int HEAD_PLAIN = 0, HEAD_CRIT = 1, HEAD_FOCAL = 2;
+template <int RB, int NRJ, int NKI, int FORM>
+__device__ __forceinline__ void head_rows_body(const HeadArgs& a) {
+  constexpr bool CRIT = FORM != HEAD_PLAIN;          // the batch-wide label count and n_c w_c: both criterion forms
   __shared__ __attribute__((aligned(16))) float feat[RB][HR_LD], hid[RB][HR_LD], dhid[RB][HR_LD], dfeat[RB][HR_LD];
   __shared__ __attribute__((aligned(16))) float red[HR_WAVES * RB * HR_LD];     // mean-phase and wave partials
   __shared__ float lg[RB][16], dl[RB][16], invl[RB], b0s[HR_LD];
@@ -336,7 +343,33 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
     const long yb = (long)ys[r];
     const bool yok = yb >= 0 && yb < C;
     const int t = yok ? (int)yb : 0;
-    if constexpr (CRIT) {
+    if constexpr (FORM == HEAD_FOCAL) {
+      // loss = sum_b w[y_b] m_b nll_b / W, dlogits = (p - onehot) g_b w[y_b] / W with the factors m_b, g_b of focal_factors.  The
+      // factor order is the CRIT block's below: m_b multiplies w[y_b] nll_b where (1 - eps) does, g_b multiplies (p - onehot)
+      // where (1 - eps) does, w[y_b] (1 / W) stays the last factor -- at gamma = 0 (m_b = g_b = 1.0f) the CRIT form's bits at
+      // eps = 0, whose smoothing terms are exact zeros.
+      const float gamma = crs[0];
+      float Wn = 0.f;
+      for (int c = 0; c < C; ++c) Wn += nws[c];
+      const float invW = 1.0f / Wn, wy = crs[1 + t], fy = wy * invW;
+      const float nll = lse - lg[r][t];
+      float q = 0.f, py = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float p = expf(lg[r][c] - lse);
+        if (c == t) py = p; else q += p;
+      }
+      float mf, gf;
+      focal_factors(gamma, q, py, nll, mf, gf);
+      const float term = mf * (wy * nll);
+      a.lossr[b] = yok ? term * ((float)B / Wn) : __builtin_nanf("");
+      for (int c = 0; c < C; ++c) {
+        const float p = expf(lg[r][c] - lse);
+        const float d = ((p - (c == t ? 1.f : 0.f)) * gf) * fy;
+        dl[r][c] = d;
+        a.dlog[(long)b * C + c] = d;
+        a.logits[(long)b * C + c] = lg[r][c];
+      }
+    } else if constexpr (CRIT) {
       // loss = (1 - eps) sum_b w[y_b] nll_b / W + (eps / C) sum_b sum_c w_c (-log p[b,c]) / W,  W = sum_b w[y_b] = sum_c n_c w_c.
       // w[y_b] (1 / W) is the LAST factor of the plain term: at eps = 0, w = 1 it is 1.0f / B and the smoothing term an exact zero,
       // i.e. dlogits are the plain kernel's bits.  The per-sample term leaves scaled by B / W (exactly 1 there): the trailing
@@ -438,6 +471,16 @@ __global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
   HSTAMP(11);
 }
 
+// the kernels: plain / CRIT as they were (the template flag the launch sites and the build's touch sites name), FOCAL beside them
+template <int RB, int NRJ, int NKI, bool CRIT>
+__global__ __launch_bounds__(HR_THR) void k_head_rows(HeadArgs a) {
+  head_rows_body<RB, NRJ, NKI, CRIT ? HEAD_CRIT : HEAD_PLAIN>(a);
+}
+template <int RB, int NRJ, int NKI>
+__global__ __launch_bounds__(HR_THR) void k_head_rows_focal(HeadArgs a) {
+  head_rows_body<RB, NRJ, NKI, HEAD_FOCAL>(a);
+}
+
 // dW[n,k] = sum_b u[b,n] v[b,k], db[n] = sum_b u[b,n]: 16 x 16 output tile per workgroup, thread = one output (rd_trailing.h)
 __global__ __launch_bounds__(256) void k_head_wgrad(HwArgs a) {
   __shared__ float us[256][16], vs[256][17];
@@ -472,7 +515,7 @@ extern "C" int rd_head_train_supported(int32_t D, int32_t Fe, int32_t C) {
 static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
                        const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w, const float* emb_b,
                        const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* crit,
-                       const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
+                       int form, const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                        float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream);
 
 // ---- the route: every decision of one head call, taken ONCE, from the sizes alone (head_launch runs it; rd_debug_head_route,
@@ -480,6 +523,7 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
 struct HeadRoute {
   bool narrow;                     // k_head_rows<1, 12, 3, .>: W0 fetched as 192 x 192; else <1, 16, 4, .>: 256 x 256
   bool crit;                       // the CRIT instantiations
+  bool focal;                      // the FOCAL instantiations (never with crit)
   bool emb_lds;                    // the static embedding's operands are staged in LDS (else read in place)
   int touch_bytes;                 // own-code touch of the instantiation (0: RD_CODE_TOUCH=0)
   int grid;                        // workgroups of k_head_rows: one sample each
@@ -490,13 +534,14 @@ struct HeadRoute {
   const char* name;                // what the launch reports to the error check and the launch log
 };
 
-// one name per instantiation: the launch log tells the four k_head_rows apart
+// one name per instantiation: the launch log tells the six k_head_rows apart
 static const char* head_name(const HeadRoute& r) {
+  if (r.focal) return r.narrow ? "k_head_rows<12,3,focal>" : "k_head_rows<16,4,focal>";
   if (r.crit) return r.narrow ? "k_head_rows<12,3,crit>" : "k_head_rows<16,4,crit>";
   return r.narrow ? "k_head_rows<12,3>" : "k_head_rows<16,4>";
 }
 
-static HeadRoute head_route(int mode, int B, int D, int d_static, int Fe, int C, bool crit) {
+static HeadRoute head_route(int mode, int B, int D, int d_static, int Fe, int C, int form) {
   // own-code touch: 14.5 KB of the 15.4 KB <1, 12, 3> kernel, 16 KB of the 16.9 KB generic one (tests/test_kernel_resources.py keeps the
   // constants below the code lengths); RD_CODE_TOUCH=0 switches it off (A/B)
   static const int touch = [] { const char* e = getenv("RD_CODE_TOUCH"); return e ? atoi(e) : 1; }();
@@ -507,10 +552,11 @@ static HeadRoute head_route(int mode, int B, int D, int d_static, int Fe, int C,
   const int dh = D + Fe;
   HeadRoute r{};
   r.narrow = narrow && dh <= 192;
-  r.crit = crit;                                                       // the criterion instantiations: touch lengths of their own
+  const bool crit = form == HEAD_CRIT, focal = form == HEAD_FOCAL;
+  r.crit = crit; r.focal = focal;                                      // the criterion / focal instantiations: touch lengths of their own
   // the kernel's own predicate (k_head_rows: `const bool emb_lds = ...`), restated: the kernel bodies are not touched by the route
   r.emb_lds = Fe > 0 && Fe * d_static <= HR_EMBW && d_static <= HR_DS;
-  r.touch_bytes = !touch ? 0 : crit ? (r.narrow ? RD_TL_HEAD_P19_C : RD_TL_HEAD_C) : (r.narrow ? RD_TL_HEAD_P19 : RD_TL_HEAD);
+  r.touch_bytes = !touch ? 0 : focal ? (r.narrow ? RD_TL_HEAD_P19_F : RD_TL_HEAD_F) : crit ? (r.narrow ? RD_TL_HEAD_P19_C : RD_TL_HEAD_C) : (r.narrow ? RD_TL_HEAD_P19 : RD_TL_HEAD);
   r.grid = B;
   r.name = head_name(r);
   if (mode == 1) return r;                                             // rd_head_forward: the logits are the result
@@ -533,7 +579,7 @@ extern "C" int rd_head_train(const rd_shape* s, int32_t D, int32_t d_static, int
                              float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace, size_t workspace_bytes,
                              void* stream) {
   RD_REQUIRE(y && loss && logits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
-  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, nullptr, nullptr, loss, logits,
+  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, nullptr, HEAD_PLAIN, nullptr, loss, logits,
                      g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
 }
 
@@ -547,8 +593,22 @@ extern "C" int rd_head_train_crit(const rd_shape* s, int32_t D, int32_t d_static
                                   size_t workspace_bytes, void* stream) {
   RD_REQUIRE(y && crit && loss && logits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
   RD_REQUIRE(s && s->B < (1 << 24), "head_train_crit: B must be below 2^24 (per-class label counts are carried as floats)");
-  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, crit, nullptr, loss, logits,
+  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, crit, HEAD_CRIT, nullptr, loss, logits,
                      g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
+}
+
+// rd_head_train with the focal loss (rd_softmax_xent_focal's formulas) as the loss: crit = [gamma, w_0 .. w_{C-1}] on the device,
+// read when the kernel RUNS.  gamma = 0: every output is rd_head_train_crit's at eps = 0.
+extern "C" int rd_head_train_focal(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
+                                   const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w,
+                                   const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
+                                   const int64_t* y, const float* crit, float* loss, float* logits, float* g_emb_w, float* g_emb_b,
+                                   float* g_w0, float* g_b0, float* g_w2, float* g_b2, float* dr, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  RD_REQUIRE(y && crit && loss && logits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
+  RD_REQUIRE(s && s->B < (1 << 24), "head_train_focal: B must be below 2^24 (per-class label counts are carried as floats)");
+  return head_launch(0, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, y, crit, HEAD_FOCAL, nullptr, loss,
+                     logits, g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
 }
 
 // The same head as two calls around a loss the CALLER evaluates (the reference's training loop: `criterion(outputs, y)` in
@@ -560,7 +620,7 @@ extern "C" int rd_head_forward(const rd_shape* s, int32_t D, int32_t d_static, i
                                const float* emb_b, const float* w0, const float* b0, const float* w2, const float* b2,
                                float* logits, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(logits, "NULL tensor");
-  return head_launch(1, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, nullptr, nullptr, logits,
+  return head_launch(1, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, HEAD_PLAIN, nullptr, nullptr, logits,
                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 extern "C" int rd_head_backward(const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
@@ -569,14 +629,14 @@ extern "C" int rd_head_backward(const rd_shape* s, int32_t D, int32_t d_static, 
                                 const float* dlogits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                                 float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(dlogits && g_w0 && g_b0 && g_w2 && g_b2 && dr, "NULL tensor");
-  return head_launch(2, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, dlogits, nullptr, nullptr,
+  return head_launch(2, s, D, d_static, Fe, C, r, mask, lengths, stat, emb_w, emb_b, w0, b0, w2, b2, nullptr, nullptr, HEAD_PLAIN, dlogits, nullptr, nullptr,
                      g_emb_w, g_emb_b, g_w0, g_b0, g_w2, g_b2, dr, workspace, workspace_bytes, stream);
 }
 
 static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static, int32_t Fe, int32_t C, const float* r,
                        const uint8_t* mask, const int64_t* lengths, const float* stat, const float* emb_w, const float* emb_b,
                        const float* w0, const float* b0, const float* w2, const float* b2, const int64_t* y, const float* crit,
-                       const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
+                       int form, const float* dlog_in, float* loss, float* logits, float* g_emb_w, float* g_emb_b, float* g_w0, float* g_b0, float* g_w2,
                        float* g_b2, float* dr, void* workspace, size_t workspace_bytes, void* stream) {
   RD_REQUIRE(s && s->T > 0 && s->B > 0, "bad shape");
   RD_REQUIRE(rd_head_train_supported(D, Fe, C), "head_train: unsupported sizes D=%d Fe=%d C=%d", D, Fe, C);
@@ -594,9 +654,12 @@ static int head_launch(int mode, const rd_shape* s, int32_t D, int32_t d_static,
   a.dlog = a.demb + (size_t)B * dh; a.lossr = a.dlog + (size_t)B * C;
   a.T = s->T; a.B = B; a.D = D; a.ds = d_static; a.Fe = Fe; a.dh = dh; a.C = C;
   a.plan = token_plan(); a.stamps = g_head_stamps;
-  const HeadRoute rt = head_route(mode, B, D, d_static, Fe, C, crit != nullptr);
+  const HeadRoute rt = head_route(mode, B, D, d_static, Fe, C, form);
   a.touch_bytes = rt.touch_bytes;
-  if (rt.crit) {
+  if (rt.focal) {
+    if (rt.narrow) hipLaunchKernelGGL((k_head_rows_focal<1, 12, 3>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+    else hipLaunchKernelGGL((k_head_rows_focal<1, HR_RJ, HR_KI>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
+  } else if (rt.crit) {
     if (rt.narrow) hipLaunchKernelGGL((k_head_rows<1, 12, 3, true>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
     else hipLaunchKernelGGL((k_head_rows<1, HR_RJ, HR_KI, true>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
   } else if (rt.narrow) hipLaunchKernelGGL((k_head_rows<1, 12, 3, false>), dim3(rt.grid), dim3(HR_THR), 0, st, a);
@@ -633,11 +696,11 @@ extern "C" int rd_debug_head_route(int32_t mode, int32_t B, int32_t D, int32_t d
   RD_REQUIRE(words && name && cap > 0, "NULL output");
   for (int i = 0; i < 11; ++i) words[i] = 0;
   name[0] = 0;
-  RD_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && (!with_crit || mode == 0), "bad mode / shape");
+  RD_REQUIRE(mode >= 0 && mode <= 2 && B > 0 && with_crit >= 0 && with_crit <= 2 && (!with_crit || mode == 0), "bad mode / shape");
   RD_REQUIRE(rd_head_train_supported(D, Fe, C), "head_train: unsupported sizes D=%d Fe=%d C=%d", D, Fe, C);
   RD_REQUIRE(Fe == 0 || d_static > 0, "static embedding tensors missing");
-  const HeadRoute r = head_route(mode, B, D, d_static, Fe, C, with_crit != 0);
-  words[0] = (r.narrow ? 1u : 0u) | (r.crit ? 2u : 0u) | (r.emb_lds ? 4u : 0u) | ((unsigned)r.njobs << 8);
+  const HeadRoute r = head_route(mode, B, D, d_static, Fe, C, with_crit == 2 ? HEAD_FOCAL : with_crit ? HEAD_CRIT : HEAD_PLAIN);
+  words[0] = (r.narrow ? 1u : 0u) | (r.crit ? 2u : 0u) | (r.emb_lds ? 4u : 0u) | (r.focal ? 8u : 0u) | ((unsigned)r.njobs << 8);
   words[1] = (uint32_t)r.touch_bytes; words[2] = (uint32_t)r.grid; words[3] = (uint32_t)r.ntiles; words[4] = (uint32_t)r.rider_blocks;
   for (int i = 0; i < r.njobs; ++i) {
     words[5 + i] = (uint32_t)r.job[i].blk0;

@@ -397,7 +397,8 @@ def evaluate_captured(model, ds, chunk=2048, group=None, save_free=True):
 
 
 @torch.no_grad()
-def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True, class_weight=None, label_smoothing=0.0):
+def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True, class_weight=None, label_smoothing=0.0,
+             focal_gamma=None):
     """The validation / test block of the reference's loop (`code/Raindrop.py:345-370,385-401`) without leaving the device until
     the end: `evaluate_captured` -> `transform` of the logits with torch ("sigmoid": validation, :349; "softmax": test, :388-389;
     None: the logits) -> `metrics.rank_metrics`, `metrics.confusion` and `rd_softmax_xent` on the TRANSFORMED scores (the
@@ -408,16 +409,21 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     numpy arrays `auroc_per_class`, `auprc_per_class`, `confusion` [C, C] (rows = true class).  `ds.y` is required.
     class_weight / label_smoothing (raindrop_amd.step.criterion_values): `loss` is CrossEntropyLoss(weight=class_weight,
     label_smoothing=label_smoothing) of the same scores (`rd_softmax_xent_crit`), the training steps' criterion; no other field
-    changes."""
+    changes.  focal_gamma (raindrop_amd.step.focal_values; label_smoothing must be 0): `loss` is the focal loss of the same scores
+    with these class weights (`rd_softmax_xent_focal`); no other field changes."""
     from . import metrics
-    from .step import criterion_values
+    from .step import check_focal, criterion_values, focal_values
     if ds.y is None:
         raise _lib.RaindropHipError("validate needs the dataset's labels (DeviceDataset(..., y=...))")
     if transform not in ("sigmoid", "softmax", None):
         raise ValueError("transform must be 'sigmoid', 'softmax' or None")
+    if focal_gamma is not None:                                           # refused before the evaluation runs, as the constructors do
+        check_focal(label_smoothing, focal_gamma)
+        focal_values(class_weight, focal_gamma, model.n_classes)
     logits = evaluate_captured(model, ds, chunk, group, save_free=save_free)
     N, C = logits.shape
     crit = criterion_values(class_weight, label_smoothing, C)
+    focal = None if focal_gamma is None else focal_values(class_weight, focal_gamma, C)
     scores = torch.sigmoid(logits) if transform == "sigmoid" else torch.softmax(logits, dim=1) if transform == "softmax" else logits
     scores = scores.contiguous()
     r = metrics.rank_metrics(scores, ds.y)
@@ -425,7 +431,10 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     loss = torch.empty(1, dtype=torch.float32, device=ds.dev)
     dscores = torch.empty_like(scores)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if crit is not None:
+    if focal is not None:
+        focald = torch.tensor(focal, dtype=torch.float32, device=ds.dev)
+        _lib.call("rd_softmax_xent_focal", int(N), int(C), _p(scores), _p(ds.y), _p(focald), _p(loss), _p(dscores), st)
+    elif crit is not None:
         critd = torch.tensor(crit, dtype=torch.float32, device=ds.dev)
         _lib.call("rd_softmax_xent_crit", int(N), int(C), _p(scores), _p(ds.y), _p(critd), _p(loss), _p(dscores), st)
     else:

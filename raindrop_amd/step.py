@@ -158,6 +158,33 @@ def criterion_values(class_weight, label_smoothing, n_classes):
     return [eps] + [float(v) for v in w32.tolist()]
 
 
+FOCAL_GAMMA_MAX = 16.0
+
+
+def focal_values(class_weight, focal_gamma, n_classes):
+    """The device buffer `[gamma, w_0 .. w_{C-1}]` of the focal loss (include/raindrop_hip.h rd_softmax_xent_focal):
+    loss = sum_b w[y_b] q_b^gamma (-log p[b,y_b]) / sum_b w[y_b], q_b the summed probability of the other classes.  `focal_gamma`: a
+    finite number in [0, 16] (0: CrossEntropyLoss(weight=class_weight) through the focal kernels); `class_weight` as in
+    `criterion_values` (None: all 1).  Anything else: ValueError."""
+    if focal_gamma is None or isinstance(focal_gamma, (bool, str, bytes)):
+        raise ValueError("focal_gamma must be a finite number in [0, %g], got %r" % (FOCAL_GAMMA_MAX, focal_gamma))
+    try:
+        gamma = float(focal_gamma)
+    except (TypeError, ValueError):
+        raise ValueError("focal_gamma must be a finite number in [0, %g], got %r" % (FOCAL_GAMMA_MAX, focal_gamma)) from None
+    if not 0.0 <= gamma <= FOCAL_GAMMA_MAX:                        # NaN and the infinities fail
+        raise ValueError("focal_gamma must be a finite number in [0, %g], got %r" % (FOCAL_GAMMA_MAX, focal_gamma))
+    w = criterion_values(class_weight, 0.0, n_classes)
+    return [gamma] + ([1.0] * int(n_classes) if w is None else w[1:])
+
+
+def check_focal(label_smoothing, focal_gamma):
+    """focal_gamma together with label smoothing has no agreed meaning: refused (ValueError)."""
+    if focal_gamma is not None and float(label_smoothing) != 0.0:
+        raise ValueError("label_smoothing=%r together with focal_gamma=%r is refused: smoothed targets have no agreed meaning under "
+                         "a focal factor" % (label_smoothing, focal_gamma))
+
+
 class SensorStage:
     """The sensor stage of the DEFAULT branch (rd_sensor_stage_fwd / rd_msgpass_bwd: code/models_rd.py:317's `use_beta = False`,
     distance exactly 0), and the interface a step asks its sensor stage through.
@@ -292,7 +319,7 @@ class Step:
     }
 
     def __init__(self, model, batch, sensor, flat=None, has_backward=True, labels=True, p_drop=None, seed=1234, token_plan=None,
-                 save_free=True, class_weight=None, label_smoothing=0.0):
+                 save_free=True, class_weight=None, label_smoothing=0.0, focal_gamma=None):
         """sensor: the sensor-stage object of the model's branch.  has_backward=False: a forward-only step -- no gradient tables,
         no dx / dfeat / dhid / dlogits / loss / weight-gradient workspace, no backward workspaces, seed cell or trailing riders,
         dropout off whatever model.training says, the eager surface's head operator by operator, and (save_free, the default) the
@@ -303,10 +330,18 @@ class Step:
         rd_softmax_xent_crit), which read that buffer when they RUN: `set_criterion` changes both between replays.  The mean's
         denominator is the sum of w[y_b] over THIS step's batch: under data parallelism every rank normalises by its own shard
         and the gradient all-reduce averages the ranks, which is what DistributedDataParallel with torch's criterion computes.
-        Both at their defaults: the plain mean cross entropy, no buffer, the launches the step always enqueued."""
+        Both at their defaults: the plain mean cross entropy, no buffer, the launches the step always enqueued.
+        focal_gamma: a number in [0, 16] (0.0 included) makes the loss the focal loss with these class weights (`focal_values`;
+        label_smoothing must be 0): the step owns `focal` = [gamma, w_0 ..] instead of `crit` and its head runs the `_focal` entry
+        points (rd_head_train_focal / rd_softmax_xent_focal) on it; `set_criterion(class_weight=, focal_gamma=)` changes both
+        between replays.  The denominator and the data-parallel rule are the weighted criterion's.  None: as without it."""
         self._crit_vals = criterion_values(class_weight, label_smoothing, model.n_classes)
-        if self._crit_vals is not None and not (has_backward and labels):
-            raise ValueError("class_weight / label_smoothing belong to a step that evaluates the loss itself (a training step with labels)")
+        check_focal(label_smoothing, focal_gamma)
+        self._focal_vals = None
+        if focal_gamma is not None:
+            self._focal_vals, self._crit_vals = focal_values(class_weight, focal_gamma, model.n_classes), None
+        if (self._crit_vals is not None or self._focal_vals is not None) and not (has_backward and labels):
+            raise ValueError("class_weight / label_smoothing / focal_gamma belong to a step that evaluates the loss itself (a training step with labels)")
         self.model, self.flat, self.batch, self.sensor, self.has_backward = model, flat, batch, sensor, bool(has_backward)
         self.infer = bool(save_free) and not self.has_backward
         self.dev = batch["src"].device
@@ -408,6 +443,11 @@ class Step:
         if getattr(self, "_crit_vals", None) is not None:
             self.crit = a.zeros((m.n_classes + 1,))
             self.crit.copy_(torch.tensor(self._crit_vals, dtype=torch.float32))
+        # the focal loss's [gamma, w_0 .. w_{C-1}] of a step built with focal_gamma (then crit is None: one criterion per step)
+        self.focal = None
+        if getattr(self, "_focal_vals", None) is not None:
+            self.focal = a.zeros((m.n_classes + 1,))
+            self.focal.copy_(torch.tensor(self._focal_vals, dtype=torch.float32))
         tables = lambda T_: [_lib.RdEncoderPtrs(*[T_["transformer_encoder.layers.%d.%s" % (i, n)].data_ptr() for n in ops.ENC_PARAM_NAMES])
                              for i in range(self.nl)]
         self.enc_w, self.enc_g = tables(self.P), tables(self.G) if bwd else []
@@ -485,15 +525,33 @@ class Step:
         if not self.head_fused:
             return self._head_by_operator()
         common, tail = self._fused_head_args()
+        if getattr(self, "focal", None) is not None:                       # the focal loss: the focal instantiation
+            return self._call("rd_head_train_focal", *common, _p(self.batch["y"]), _p(self.focal), _p(self.loss), _p(self.logits), *tail)
         if self.crit is not None:                                          # class weights / label smoothing: the criterion instantiation
             return self._call("rd_head_train_crit", *common, _p(self.batch["y"]), _p(self.crit), _p(self.loss), _p(self.logits), *tail)
         self._call("rd_head_train", *common, _p(self.batch["y"]), _p(self.loss), _p(self.logits), *tail)
 
-    def set_criterion(self, class_weight=None, label_smoothing=0.0):
+    def set_criterion(self, class_weight=None, label_smoothing=0.0, focal_gamma=None):
         """Change the step's loss to CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing) between steps: a copy of
         C + 1 floats into the device buffer the head kernels read when they run, like `lr` -- never a new capture.  None / 0 mean
         what they mean to the constructor (all weights 1 / no smoothing).  Only a step BUILT with a criterion has that buffer and
-        the kernels that read it; any other refuses (build a new step)."""
+        the kernels that read it; any other refuses (build a new step).
+        A step built with focal_gamma takes `class_weight` and `focal_gamma` the same way (its buffer is [gamma, w_0 ..]); it
+        refuses label_smoothing, and a call without focal_gamma; a step not built focal refuses focal_gamma."""
+        focal = getattr(self, "focal", None)
+        if focal is not None:
+            check_focal(label_smoothing, 0.0 if focal_gamma is None else focal_gamma)
+            if focal_gamma is None:
+                raise _lib.RaindropHipError("set_criterion: this step was built for the focal loss (focal_gamma=...) and its captured "
+                                            "head runs the focal kernels; pass focal_gamma=... (0.0 is the weighted cross entropy), "
+                                            "or build a new step for another criterion")
+            vals = focal_values(class_weight, focal_gamma, self.model.n_classes)
+            self._focal_vals = vals
+            focal.copy_(torch.tensor(vals, dtype=torch.float32))
+            return
+        if focal_gamma is not None:
+            raise _lib.RaindropHipError("set_criterion: this step was not built for the focal loss (focal_gamma=None) and its captured "
+                                        "head reads no gamma; build the step with focal_gamma=... to change it between steps")
         if self.crit is None:
             raise _lib.RaindropHipError("set_criterion: this step was built for the plain mean cross entropy (class_weight=None, "
                                         "label_smoothing=0) and its captured head reads no criterion buffer; build the step with "
@@ -526,7 +584,9 @@ class Step:
         c = self._call
         self._head_forward_by_operator()
         # ---------------- loss: mean cross entropy (code/Raindrop.py:255,322) and its gradient ----------
-        if self.crit is not None:
+        if getattr(self, "focal", None) is not None:
+            c("rd_softmax_xent_focal", B, C, _p(self.logits), _p(b["y"]), _p(self.focal), _p(self.loss), _p(self.dlogits), st)
+        elif self.crit is not None:
             c("rd_softmax_xent_crit", B, C, _p(self.logits), _p(b["y"]), _p(self.crit), _p(self.loss), _p(self.dlogits), st)
         else:
             c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
@@ -598,7 +658,7 @@ class TrainStep(Step):
     TUNE_WAVES = (12, 15)
 
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0, feed=None, accumulate=1):
+                 module_mode=False, sensor=None, class_weight=None, label_smoothing=0.0, feed=None, accumulate=1, focal_gamma=None):
         """model: raindrop_amd.models_rd.Raindrop_v2 on a ROCm device; flat: FlatGradAllReduce over the
         live parameters (its buffer receives the gradients); batch: dict(src, static, times, lengths, y)
         of device tensors that are REUSED every step (copy new data into them).
@@ -615,6 +675,9 @@ class TrainStep(Step):
         two-graph data-parallel form); `set_criterion` changes both between replays without a new capture.  Each rank normalises by
         the weights of its OWN shard's labels and the gradient all-reduce averages the ranks -- DistributedDataParallel's result
         with torch's criterion, not the single-process result on the global batch (`Step.__init__`).
+        focal_gamma: the focal loss with these class weights in every form of the step (`Step.__init__`, `focal_values`); needs
+        label_smoothing == 0; `set_criterion(class_weight=, focal_gamma=)` changes it between replays.  Under accumulate=k each
+        micro-batch is normalised by its own weight sum, and each rank by its own shard's, as with class weights.
         token_plan: store and process only the live (sample, step) rows (include/raindrop_hip.h "token plan": the padding mask of
         code/models_rd.py:298-299 applied as a layout; same logits, loss and gradients).  None = environment RD_TOKEN_PLAN
         (default on) where the shape supports it.
@@ -655,7 +718,7 @@ class TrainStep(Step):
         self.split = bool(split) and len(model.transformer_encoder.layers) >= 2
         self.autotune, self.tuned_rows32, self.tuned_waves16 = bool(autotune), None, None
         super().__init__(model, batch, sensor or SensorStage(), flat=flat, labels=not self.module_mode, p_drop=p_drop, seed=seed,
-                         token_plan=token_plan, class_weight=class_weight, label_smoothing=label_smoothing)
+                         token_plan=token_plan, class_weight=class_weight, label_smoothing=label_smoothing, focal_gamma=focal_gamma)
         if self.split:
             self._check_split_order()
         self.feed = feed
@@ -1082,13 +1145,18 @@ class AutogradStep:
     rd_structure_distance_bwd -> rd_graph_beta_bwd_alpha).  Any other model would add lambda * 0 and is refused.  0: CE alone,
     the same capture as without the argument."""
 
-    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234, distance_weight=0.0, class_weight=None, label_smoothing=0.0):
+    def __init__(self, model, batch, lr=1e-4, optimizer=True, seed=1234, distance_weight=0.0, class_weight=None, label_smoothing=0.0,
+                 focal_gamma=None):
         """class_weight / label_smoothing (`criterion_values`): the captured loss is torch.nn.functional.cross_entropy(logits, y,
-        weight=class_weight, label_smoothing=label_smoothing) (`_criterion`)."""
+        weight=class_weight, label_smoothing=label_smoothing) (`_criterion`).  focal_gamma (`focal_values`; label_smoothing must be
+        0): the focal loss with these class weights, written in torch operations."""
         crit = criterion_values(class_weight, label_smoothing, model.n_classes)
+        check_focal(label_smoothing, focal_gamma)
+        focal = None if focal_gamma is None else focal_values(class_weight, focal_gamma, model.n_classes)
         self.model, self.batch = model, batch
         self.dev = batch["src"].device
         self._crit = None if crit is None else (crit[0], torch.tensor(crit[1:], dtype=torch.float32, device=self.dev))
+        self._focal = None if focal is None else (focal[0], torch.tensor(focal[1:], dtype=torch.float32, device=self.dev))
         self.distance_weight = float(distance_weight)
         if self.distance_weight != 0.0 and not (getattr(model, "use_beta", False) and getattr(model, "compute_distance", False)):
             raise _lib.RaindropHipError("AutogradStep(distance_weight=%g): the structure distance is the constant 0 unless the model "
@@ -1112,6 +1180,17 @@ class AutogradStep:
         output size is read back on the host ("operation not permitted when stream is capturing").  The same value -- mean
         reduction, no ignore_index -- written out in operations of static shape:
             (1 - eps) sum_b w[y_b] (-logp[b,y_b]) / W + (eps / C) sum_b sum_c w_c (-logp[b,c]) / W,   W = sum_b w[y_b]."""
+        focal = getattr(self, "_focal", None)
+        if focal is not None:
+            # sum_b w[y_b] q_b^gamma (-logp[b,y_b]) / W with q_b the summed probability of the other classes (rd_softmax_xent_focal)
+            gamma, w = focal
+            if gamma == 0.0:
+                return torch.nn.functional.cross_entropy(logits, y, weight=w)
+            logp = torch.log_softmax(logits, 1)
+            hot = torch.nn.functional.one_hot(y, logits.shape[1]).to(logp.dtype)
+            q = (logp.exp() * (1.0 - hot)).sum(1)
+            wy = w[y]
+            return -(wy * q.pow(gamma) * (logp * hot).sum(1)).sum() / wy.sum()
         if self._crit is None:
             return torch.nn.functional.cross_entropy(logits, y)
         eps, w = self._crit

@@ -110,7 +110,7 @@ class BetaSensorStage(SensorStage):
 
 class BetaTrainStep(TrainStep):
     def __init__(self, model, flat, batch, p_drop=None, use_graph=True, seed=1234, autotune=True, token_plan=None, split=None,
-                 distance_weight=0.0, class_weight=None, label_smoothing=0.0, feed=None, accumulate=1):
+                 distance_weight=0.0, class_weight=None, label_smoothing=0.0, feed=None, accumulate=1, focal_gamma=None):
         """As `TrainStep`, for `Raindrop_v2(use_beta=True)` (with or without `compute_distance`) only.  `flat` must cover the
         branch's live parameters (raindrop_amd.synth.live_parameter_names_beta).
         accumulate: as in `TrainStep` (k micro-batches per optimizer step; the window's gradient is the mean of the k gradients of
@@ -118,6 +118,7 @@ class BetaTrainStep(TrainStep):
         feed: as in `TrainStep` (raindrop_amd.feed.EpochFeed: the step gathers its own batch and records loss and accuracy).
         class_weight, label_smoothing: as in `TrainStep` -- the CE term becomes torch's weighted, smoothed criterion (per rank: its
         own shard's weight sum), the objective CE_crit + lambda * distance; the distance term is untouched.
+        focal_gamma: as in `TrainStep` -- the CE term becomes the focal loss with these class weights; the distance term is untouched.
         distance_weight (lambda, `compute_distance=True` only): the step minimises CE + lambda * distance, the paper's objective
         (code/models_rd.py:345-346, code/Raindrop.py:319).  `self.loss` stays the CE term, `self.distance` holds the distance, both
         device tensors.  lambda lives in a device cell (`set_distance_weight`): changing it needs no new capture.  0: CE alone --
@@ -135,7 +136,7 @@ class BetaTrainStep(TrainStep):
                                         "raindrop_amd.synth.live_parameter_names_beta(cfg)" % ", ".join(missing))
         super().__init__(model, flat, batch, p_drop=p_drop, use_graph=use_graph, seed=seed, autotune=autotune, token_plan=token_plan,
                          split=split, sensor=stage, class_weight=class_weight, label_smoothing=label_smoothing, feed=feed,
-                         accumulate=accumulate)
+                         accumulate=accumulate, focal_gamma=focal_gamma)
         self.alpha, self.ei2, self.distance, self.beta_saved, self.beta_ws = stage.alpha, stage.ei2, stage.distance, self.k1_saved, self.k1_ws
 
     def set_distance_weight(self, lam):

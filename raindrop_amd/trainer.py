@@ -62,8 +62,12 @@ class ReduceOnPlateau:
 
 
 def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
-                    warmup_steps=0, accumulate=1):
+                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0):
     """what can be refused without a device"""
+    if focal_gamma is not None:
+        from .step import check_focal, focal_values
+        focal_values(None, focal_gamma, 1)                                 # the range of gamma (the weights need the model's class count)
+        check_focal(label_smoothing, focal_gamma)
     if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
         raise ValueError("accumulate must be an integer >= 1, got %r" % (accumulate,))
     if isinstance(lr_schedule, str):
@@ -138,7 +142,8 @@ def _live_names(model):
 
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
-        param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1):
+        param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1,
+        focal_gamma=None):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -173,10 +178,13 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     `optimizer_steps` (the run's total), and `lr_step` then holds one entry per optimizer step: the rate that step applied (the
     double product the device forms), not one per epoch.  The plateau scheduler, validation and EMA validation are untouched.
 
+    focal_gamma: a number in [0, 16] makes the criterion of the step AND of the validation loss the focal loss with `class_weight`
+    (`TrainStep(focal_gamma=)`, `feed.validate(focal_gamma=)`); `label_smoothing` must then be 0.  None: as without it.
+
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
     _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps,
-                    accumulate)
+                    accumulate, focal_gamma, label_smoothing)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -204,6 +212,8 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         kw["seed"] = int(seed)
     if accumulate > 1:                                                     # (1: the step as it was built before the keyword)
         kw["accumulate"] = accumulate
+    if focal_gamma is not None:
+        kw["focal_gamma"] = focal_gamma
     optimizer_steps = 0
     step = BetaTrainStep(model, flat, batch, distance_weight=distance_weight, **kw) if beta else TrainStep(model, flat, batch, **kw)
     sched = ReduceOnPlateau() if scheduler is True else (scheduler or None)
@@ -214,6 +224,8 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         out["lr_step"] = []
     best, best_auroc, best_epoch = None, 0.0, None
     vkw = dict(transform=transform, class_weight=class_weight, label_smoothing=label_smoothing)
+    if focal_gamma is not None:
+        vkw["focal_gamma"] = focal_gamma
     try:
         step.capture_full(opt)
         for epoch in range(int(epochs)):
