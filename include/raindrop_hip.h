@@ -652,6 +652,30 @@ int rd_feed_gather(int32_t T, int32_t B, int32_t W, int32_t d_static, int64_t N,
                    const float* time_all, const float* static_all, const int64_t* y_all, const int64_t* plan,
                    const int64_t* cell, float* src, float* times, float* static_out, int64_t* y_out, int64_t* lengths,
                    int32_t* bad_index_count, void* stream);
+/* rd_batch_gather / rd_feed_gather with TRAIN-TIME INPUT AUGMENTATION in the same launch (raindrop_amd.feed.Augment; DESIGN 3e').
+ * W must be even: W = 2F, columns [0,F) values, [F,2F) observed-indicators (odd W: RD_EINVAL).  aug_cell: 32 bytes on the device,
+ * 8-byte aligned, {u64 seed, u64 epoch, f32 p_time, f32 p_sensor, f32 p_obs, f32 noise_c}, read when the kernel RUNS (new rates, a
+ * new epoch: a copy, never a new capture).  Every decision is a pure function of key = seed + draw (uint64, wrapping) and SOURCE
+ * coordinates: the uniform of element idx at site s is component idx & 3 of the generator's quad idx >> 2, keep iff u >= p.
+ * draw = epoch * capacity + cursor (the plan row actually read) in the feed form; the explicit-index form takes `draw` by value and
+ * ignores the cell's epoch.  With b the batch slot and t the row of the source sample, in this order:
+ *   1. time-step drop, site 80, element b*T + t: candidates are the rows t < L, L = #{t : time[t] > 0}; a sample whose candidates
+ *      would all be dropped keeps all of them.  Rows written: the kept candidates in order, the source rows [L,T) unchanged, then
+ *      rows of +0.0 -- src and times alike; lengths[b] = #{written times > 0};
+ *   2. sensor drop, site 81, element b*F + f: value and indicator +0.0 in every row of the sample;
+ *   3. observation drop, site 82, element (t*B + b)*F + f: value and indicator +0.0;
+ *   4. jitter, site 83, the four uniforms u of the WHOLE quad (t*B + b)*F + f, where the indicator is still non-zero:
+ *      v' = fmaf(((u.x + u.y) + (u.z + u.w)) - 2, noise_c, v), noise_c = float(sqrt(3) * sigma): zero mean, deviation sigma.
+ * A rate of exactly 0 draws nothing for its transform; all four at 0 write the plain twin's bytes.  Index clamping, the `bad`
+ * counter, the cursor rules, labels and statics are the plain twins'.  One launch; asynchronous, capturable; B == 0 is a no-op. */
+int rd_batch_gather_aug(int32_t T, int32_t B, int32_t W, int32_t d_static, int64_t N, const float* P_all,
+                        const float* time_all, const float* static_all, const int64_t* y_all, const int64_t* idx,
+                        float* src, float* times, float* static_out, int64_t* y_out, int64_t* lengths,
+                        int32_t* bad_index_count, const void* aug_cell, uint64_t draw, void* stream);
+int rd_feed_gather_aug(int32_t T, int32_t B, int32_t W, int32_t d_static, int64_t N, int64_t capacity, const float* P_all,
+                       const float* time_all, const float* static_all, const int64_t* y_all, const int64_t* plan,
+                       const int64_t* cell, float* src, float* times, float* static_out, int64_t* y_out, int64_t* lengths,
+                       int32_t* bad_index_count, const void* aug_cell, void* stream);
 /* The LAST launch of a fed step (one workgroup), k = cursor: loss_hist[k] = *loss; correct_hist[k] = the number of samples b
  * with argmax_c logits[b, c] == y[b] (logits [B,C] row-major; ties go to the lowest class, a NaN is the maximum: torch.argmax;
  * int32, integer partial sums in a fixed order, no atomics); then cursor = k + 1.  loss_hist / correct_hist hold `capacity`

@@ -159,6 +159,9 @@ SIGNATURES = {
     # the batch of a captured step from a device-resident epoch plan (raindrop_amd.feed.EpochFeed)
     "rd_feed_gather": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64, ctypes.c_int64] + [_P] * 13),
     "rd_feed_record": (c_int32, [c_int32, c_int32, ctypes.c_int64] + [_P] * 7),
+    # the two gathers with input augmentation (raindrop_amd.feed.Augment): the plain twins' arguments, then aug_cell [, draw], stream
+    "rd_batch_gather_aug": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64] + [_P] * 12 + [ctypes.c_uint64, _P]),
+    "rd_feed_gather_aug": (c_int32, [c_int32, c_int32, c_int32, c_int32, ctypes.c_int64, ctypes.c_int64] + [_P] * 14),
     "rd_graph_beta_kept": (c_int32, [c_int32]),
     "rd_graph_beta_workspace_bytes": (c_size_t, [c_int32] * 5),
     "rd_graph_beta_fwd": (c_int32, [c_int32] * 6 + [_P, _P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64]

@@ -77,6 +77,9 @@ __device__ __forceinline__ uint64_t eff_seed(uint64_t seed, const uint64_t* cell
 }
 
 enum DropSite : uint32_t { SITE_OBS_EMBED = 1, SITE_EDGE_COEFF = 2, SITE_ATTN_PROB = 16, SITE_ATTN_OUT = 32, SITE_FFN_HID = 48,
-                           SITE_FFN_OUT = 64 };   // + layer index for the encoder sites
+                           SITE_FFN_OUT = 64,     // + layer index for the encoder sites
+                           // input augmentation of the batch feed (rd_feed_aug.hip): time step b*T + t, sensor b*F + f, observation
+                           // (t*B + b)*F + f and the jitter's whole quad (t*B + b)*F + f, t the row of the SOURCE sample
+                           SITE_FEED_TIME = 80, SITE_FEED_SENSOR = 81, SITE_FEED_OBS = 82, SITE_FEED_NOISE = 83 };
 
 }  // namespace rd

@@ -27,6 +27,55 @@ def _p(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+class Augment:
+    """Train-time input augmentation inside the batch gather (rd_feed_gather_aug / rd_batch_gather_aug; DESIGN §3e'): `p_time` drops
+    time steps (the kept ones are compacted, `lengths` follows), `p_sensor` whole sensors of a sample, `p_obs` single observations
+    -- value and observed-indicator both become 0 --, `value_noise` = sigma jitters the values still observed by a zero-mean
+    Irwin-Hall(4) variate of deviation sigma (bounded at 2 sqrt(3) sigma).  Rates in [0, 1), sigma >= 0; a rate of 0 turns its
+    transform off.  Every decision is a pure function of (seed, epoch, cursor) and the element's place in the SOURCE sample, so a
+    replay reproduces it and tests/feed_aug_ref.py restates it on the host.  Training input only: no evaluation path augments.
+    Under data parallelism each rank owns its feed: give each rank its own `seed`, or all ranks draw the same masks."""
+    RATES = ("p_time", "p_sensor", "p_obs")
+
+    def __init__(self, p_time=0.0, p_sensor=0.0, p_obs=0.0, value_noise=0.0, seed=0):
+        self.p_time, self.p_sensor, self.p_obs, self.value_noise, self.seed = p_time, p_sensor, p_obs, value_noise, seed
+        self.check()
+
+    def check(self):
+        for name in self.RATES:
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not 0.0 <= float(v) < 1.0:
+                raise ValueError("Augment: %s must be a number in [0, 1), got %r" % (name, v))
+            if float(v) > 0.0 and float(np.float32(v)) >= 1.0:
+                raise ValueError("Augment: %s = %r rounds to 1 in float32" % (name, v))
+            setattr(self, name, float(v))
+        s = self.value_noise
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.floating, np.integer)) or not 0.0 <= float(s) < float("inf"):
+            raise ValueError("Augment: value_noise (sigma) must be a finite number >= 0, got %r" % (s,))
+        self.value_noise = float(s)
+        if isinstance(self.seed, bool) or not isinstance(self.seed, (int, np.integer)):
+            raise ValueError("Augment: seed must be an integer, got %r" % (self.seed,))
+        self.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+
+    @property
+    def noise_c(self):
+        """float32(sqrt(3) * sigma): formed in double, rounded once -- the factor the kernel multiplies (s - 2) by"""
+        return np.float32(np.sqrt(np.float64(3.0)) * np.float64(self.value_noise))
+
+    def cell(self, epoch=0):
+        """the 32-byte device cell {u64 seed, u64 epoch, f32 p_time, f32 p_sensor, f32 p_obs, f32 noise_c} as int64[4] (host)"""
+        host = np.zeros(4, dtype=np.int64)
+        host.view(np.uint64)[:2] = (self.seed, int(epoch) & 0xFFFFFFFFFFFFFFFF)
+        host.view(np.float32)[4:] = (self.p_time, self.p_sensor, self.p_obs, self.noise_c)
+        return host
+
+    def state(self):
+        return dict(p_time=self.p_time, p_sensor=self.p_sensor, p_obs=self.p_obs, value_noise=self.value_noise, seed=self.seed)
+
+    def __repr__(self):
+        return "Augment(%s)" % ", ".join("%s=%r" % kv for kv in self.state().items())
+
+
 class DeviceDataset:
     """P [T,N,2F] f32, Ptime [T,N] f32, Pstatic [N,d_static] f32 or None, y [N] int64 or None -- moved to
     `device` once.  `batch(idx)` returns freshly allocated (P, Pstatic, Ptime, y, lengths) for the index
@@ -61,7 +110,11 @@ class DeviceDataset:
                 "y": None if self.y is None else torch.empty((B,), dtype=torch.int64, device=self.dev),
                 "lengths": torch.empty((B,), dtype=torch.int64, device=self.dev)}
 
-    def batch(self, idx, out=None, check=True):
+    def batch(self, idx, out=None, check=True, augment=None, draw=0):
+        """augment: an `Augment` -- the batch is gathered by rd_batch_gather_aug under the key `augment.seed + draw` (the eager,
+        explicit-index form of what a feed with `augment=` does at draw = epoch * capacity + cursor).  None: the plain gather."""
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError("augment must be None or a feed.Augment, got %r" % (augment,))
         idx_t = torch.as_tensor(np.asarray(idx) if not torch.is_tensor(idx) else idx).reshape(-1).to(torch.int64)
         if check and idx_t.device.type == "cpu" and idx_t.numel():      # host indices: validate for free
             lo, hi = int(idx_t.min()), int(idx_t.max())
@@ -72,6 +125,13 @@ class DeviceDataset:
         o = out if out is not None else self.alloc(B)
         if o["P"].shape[1] != B:
             raise ValueError("out buffers hold %d samples, idx has %d" % (o["P"].shape[1], B))
+        if augment is not None:
+            cell = torch.from_numpy(augment.cell()).to(self.dev)
+            _lib.call("rd_batch_gather_aug", self.T, B, self.W, self.ds, self.N, _p(self.P), _p(self.Ptime), _p(self.Pstatic),
+                      _p(self.y), _p(idx_t), _p(o["P"]), _p(o["Ptime"]), _p(o["Pstatic"]), _p(o["y"]), _p(o["lengths"]),
+                      _p(self._bad), _p(cell), ctypes.c_uint64(int(draw) & 0xFFFFFFFFFFFFFFFF),
+                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            return o["P"], o["Pstatic"], o["Ptime"], o["y"], o["lengths"]
         _lib.call("rd_batch_gather", self.T, B, self.W, self.ds, self.N, _p(self.P), _p(self.Ptime), _p(self.Pstatic),
                   _p(self.y), _p(idx_t), _p(o["P"]), _p(o["Ptime"]), _p(o["Pstatic"]), _p(o["y"]), _p(o["lengths"]),
                   _p(self._bad), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -99,9 +159,16 @@ class EpochFeed:
         loss, correct = fd.history()
 
     Owns one int64 buffer {cursor, n_batches | plan [capacity, batch_size]}, the history [2, capacity] (fp32 losses, int32 counts) and the
-    bad-index counter.  `ds` must carry labels.  Under data parallelism every rank has its own feed and loads its own plan rows."""
+    bad-index counter.  `ds` must carry labels.  Under data parallelism every rank has its own feed and loads its own plan rows.
 
-    def __init__(self, ds, batch_size, capacity):
+    augment: an `Augment` -- the gather is rd_feed_gather_aug, which augments the batch while it forms it under the key
+    `seed + epoch * capacity + cursor`.  The feed then owns the 32-byte cell {seed, epoch, rates}: `load_epoch` writes the next epoch
+    number into it (0 for the first), `set_augment` / `set_epoch` rewrite it, all as small copies in stream order -- the captured
+    step reads the cell when it runs, so none of them needs a new capture.  A micro-batch of an accumulating step is one cursor
+    position and so one draw.  Each rank of a data-parallel run passes its own `seed`.  None (the default): nothing is allocated
+    and the launches are the plain feed's."""
+
+    def __init__(self, ds, batch_size, capacity, augment=None):
         if torch.device(ds.dev).type != "cuda":
             raise _lib.RaindropHipError("EpochFeed needs a ROCm device (there is no CPU fallback)")
         if ds.y is None:
@@ -115,6 +182,42 @@ class EpochFeed:
         self.loss_hist, self.correct_hist = self._hist[0].view(torch.float32), self._hist[1]
         self._bad = torch.zeros(1, dtype=torch.int32, device=self.dev)
         self._n = self._left = 0
+        if augment is not None and not isinstance(augment, Augment):
+            raise ValueError("augment must be None or a feed.Augment, got %r" % (augment,))
+        self.augment, self._aug, self._epoch = None, None, 0
+        if augment is not None:
+            if ds.W % 2:
+                raise ValueError("augmentation needs W = 2F columns (values | indicators), the dataset has W = %d" % ds.W)
+            self.augment = Augment(**augment.state())                  # the feed's own copy: set_augment changes it
+            self._aug = torch.from_numpy(self.augment.cell(0)).to(self.dev)
+            self._epoch = -1                                           # the first load_epoch is epoch 0
+
+    def _write_aug(self):
+        self._aug.copy_(torch.from_numpy(self.augment.cell(max(self._epoch, 0))))
+
+    def set_augment(self, **rates):
+        """new rates / sigma / seed (Augment's keywords; the others stay) from the next enqueued step on: one 32-byte copy in
+        stream order, no new capture"""
+        if self.augment is None:
+            raise _lib.RaindropHipError("set_augment: this feed was built without augment=")
+        unknown = set(rates) - set(self.augment.state())
+        if unknown:
+            raise ValueError("set_augment: unknown keywords %s" % sorted(unknown))
+        self.augment = Augment(**dict(self.augment.state(), **rates))
+        self._write_aug()
+
+    def set_epoch(self, e):
+        """the epoch number of the batch key from the next enqueued step on (the next `load_epoch` continues with e + 1)"""
+        if self.augment is None:
+            raise _lib.RaindropHipError("set_epoch: this feed was built without augment=")
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < 0:
+            raise ValueError("set_epoch: a non-negative integer, got %r" % (e,))
+        self._epoch = int(e)
+        self._write_aug()
+
+    def augment_state(self):
+        """rates, sigma, seed and the epoch number the device cell holds (host mirror, no synchronisation); None without augment="""
+        return None if self.augment is None else dict(self.augment.state(), epoch=max(self._epoch, 0))
 
     def load_epoch(self, batches):
         """`batches`: index vectors of `batch_size` samples each (EpochPlanner.next_epoch()), at most `capacity` of them, checked
@@ -138,6 +241,9 @@ class EpochFeed:
         if n:
             self._hist[:, :n].zero_()
         self._n = self._left = n
+        if self.augment is not None:                                   # a refused plan (above) leaves the epoch where it was
+            self._epoch += 1
+            self._write_aug()
 
     def remaining(self):
         """batches of the loaded epoch no step has taken yet: the host's mirror of the device cursor, no synchronisation"""
@@ -179,6 +285,12 @@ class EpochFeed:
 
     def enqueue_gather(self, batch, call=_lib.call):
         ds, st = self.ds, batch.get("static")
+        if self._aug is not None:
+            call("rd_feed_gather_aug", ds.T, self.B, ds.W, ds.ds if st is not None else 0, ds.N, self.capacity, _p(ds.P), _p(ds.Ptime),
+                 _p(ds.Pstatic) if st is not None else None, _p(ds.y), _p(self.plan), _p(self.cell), _p(batch["src"]), _p(batch["times"]),
+                 _p(st), _p(batch["y"]), _p(batch["lengths"]), _p(self._bad), _p(self._aug),
+                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            return
         call("rd_feed_gather", ds.T, self.B, ds.W, ds.ds if st is not None else 0, ds.N, self.capacity, _p(ds.P), _p(ds.Ptime),
              _p(ds.Pstatic) if st is not None else None, _p(ds.y), _p(self.plan), _p(self.cell), _p(batch["src"]), _p(batch["times"]),
              _p(st), _p(batch["y"]), _p(batch["lengths"]), _p(self._bad), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -189,7 +301,8 @@ class EpochFeed:
 
     def snapshot(self):
         """cursor, history and counter as they are now (device clones, stream-ordered): a capture's warm-up passes run the step
-        for real, `restore` puts back what they moved"""
+        for real, `restore` puts back what they moved.  (The augmentation cell is not part of it: no step writes it, and a batch's
+        masks depend on (seed, epoch, cursor) alone, so a restored cursor draws what it would have drawn.)"""
         return self.cell.clone(), self._hist.clone(), self._bad.clone()
 
     def restore(self, snap):

@@ -62,8 +62,9 @@ class ReduceOnPlateau:
 
 
 def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
-                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0):
+                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0, augment=None):
     """what can be refused without a device"""
+    _resolve_augment(augment)
     if focal_gamma is not None:
         from .step import check_focal, focal_values
         focal_values(None, focal_gamma, 1)                                 # the range of gamma (the weights need the model's class count)
@@ -110,6 +111,18 @@ def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups
             raise _lib.RaindropHipError("fit: %s carries no labels (DeviceDataset(..., y=...))" % name)
 
 
+def _resolve_augment(augment):
+    """fit's `augment` as a feed.Augment (None: none); a dict holds Augment's keywords"""
+    if augment is None or isinstance(augment, feed_mod.Augment):
+        return augment
+    if isinstance(augment, dict):
+        unknown = set(augment) - {"p_time", "p_sensor", "p_obs", "value_noise", "seed"}
+        if unknown:
+            raise ValueError("augment: dict(p_time=0.0, p_sensor=0.0, p_obs=0.0, value_noise=0.0, seed=0), got keys %s" % sorted(augment))
+        return feed_mod.Augment(**augment)
+    raise ValueError("augment must be None, a feed.Augment or a dict of its keywords, got %r" % (augment,))
+
+
 def _resolve_schedule(lr_schedule, warmup_steps, total_steps):
     """fit's `lr_schedule` as an LRSchedule for `total_steps` steps (None: none, also for a run of no steps)"""
     if lr_schedule is None or total_steps <= 0:
@@ -143,7 +156,7 @@ def _live_names(model):
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
         param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1,
-        focal_gamma=None):
+        focal_gamma=None, augment=None):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -181,10 +194,14 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     focal_gamma: a number in [0, 16] makes the criterion of the step AND of the validation loss the focal loss with `class_weight`
     (`TrainStep(focal_gamma=)`, `feed.validate(focal_gamma=)`); `label_smoothing` must then be 0.  None: as without it.
 
+    augment: a `feed.Augment` (or a dict of its keywords) -- train-time input augmentation inside the TRAINING feed's gather
+    (`EpochFeed(augment=)`: time-step, sensor and observation drop, value jitter; fresh masks every batch and epoch from
+    (seed, epoch, cursor)).  Validation, the best-weights logic and every other path are untouched.  None: as without it.
+
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
     _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps,
-                    accumulate, focal_gamma, label_smoothing)
+                    accumulate, focal_gamma, label_smoothing, augment)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -204,7 +221,8 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     schedule = _resolve_schedule(lr_schedule, warmup_steps, int(epochs) * _window_plan(planner.n_batches, accumulate)[0])
     opt = FlatAdam(flat.flatten_parameters(), lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ema_decay=ema_decay,
                    groups=groups, decoupled=decoupled_weight_decay, schedule=schedule)
-    fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1))
+    aug = _resolve_augment(augment)
+    fd = feed_mod.EpochFeed(train_ds, B, max(int(planner.n_batches), 1), **({} if aug is None else dict(augment=aug)))
     P, Pstatic, Ptime, y, lengths = train_ds.batch(np.arange(B) % train_ds.N)          # valid contents for the step's checks
     batch = dict(src=P, static=Pstatic if model.static else None, times=Ptime, y=y, lengths=lengths)
     kw = dict(autotune=autotune, class_weight=class_weight, label_smoothing=label_smoothing, feed=fd)
