@@ -932,6 +932,48 @@ int rd_rank_metrics(int64_t N, int32_t C, const float* scores, int64_t ld, const
  * integers on the host.  C <= 4096. */
 int rd_confusion(int64_t N, int32_t C, const float* logits, int64_t ld, const int64_t* y, int64_t* counts, void* stream);
 
+/* Bootstrap of the ranking statistics (raindrop_amd/csrc/rd_metrics_boot.hip): R resamples of the N rows, every column's
+ * statistics on each, and a percentile summary -- how far one AUROC / AUPRC of a small split can be trusted.  A resample changes
+ * the MULTIPLICITY of a sample, never the order of the scores: every column is sorted once, the R resamples are R weighted scans.
+ * Asynchronous, capturable, caller-owned memory only, no floating-point atomics: two calls give the same bits.
+ *
+ * Resample rule.  Resample r in [0, R) draws N row indices with replacement over the ORIGINAL rows, the same draw for every column.
+ * Draw k in [0, N) reads raw 32-bit word k & 3 of generator quad q = r * ceil(N / 4) + (k >> 2) of site 84 (SITE_BOOTSTRAP)
+ * under the key `seed` alone (no seed cell).  One Threefry-2x32-13 call gives two words, so a quad is two calls: words 0, 1 are
+ * (x0, x1) of the call with counter 2 q, words 2, 3 those of counter 2 q + 1 -- counter (low word, high word | 84 << 16), key (seed
+ * low word, seed high word), as for the dropout sites.  The index is j = floor(word * N / 2^32) (the high half of the 32 x 32
+ * product): row j is drawn with probability floor or ceil(2^32 / N) / 2^32, a relative bias of at most N / 2^32 (< 4e-6).
+ * m_r[j] = number of draws that hit j; every row of m sums to N.
+ *
+ * Statistics.  For column c and resample r: rd_rank_metrics' statistics with sample j counted m_r[j] times -- tp / fp are the
+ * cumulative WEIGHTED counts at the end of each tie group in descending score order (a group whose members all have multiplicity
+ * 0 contributes nothing), the float32 key order, the tie rule, the NaN order and "a label outside [0, C) is a negative" as above;
+ *   pos_b[r][c]       = P_r = sum_j m_r[j] (y_j == c),  Q_r = N - P_r
+ *   auroc_num_b[r][c] = sum (fp - fp_prev)(tp + tp_prev)               exact int64
+ *   auroc_b[r][c]     = auroc_num_b / (2 P_r Q_r)                      float64; NaN when P_r = 0 or Q_r = 0
+ *   auprc_b[r][c]     = sum (tp - tp_prev) / P_r * tp / (tp + fp)      float64, summed in an order that is a function of N alone;
+ *                                                                      0 when P_r = 0
+ *   mean_b[r][0 .. 1] = plain means of auroc_b[r] / auprc_b[r] over the columns (NaN when a column is NaN)
+ * = roc_auc_score / average_precision_score on the expanded resample scores[idx_r], y[idx_r].
+ * Envelope: 1 <= N <= 16384 (one LDS sort per column; larger N is deliberately out of scope: the chunked sort of rd_rank_metrics
+ * has no index-carrying form), 1 <= C <= 65535, 1 <= R <= 4096; outside it RD_EUNSUPPORTED.  `workspace`:
+ * rd_rank_bootstrap_workspace_bytes (0 outside the envelope), 2-byte aligned: per column the N sorted samples as 16-bit codes.
+ *
+ * rd_rank_bootstrap_summary: summary f64 [2][C + 1][5]: metric (0 AUROC, 1 AUPRC) x (column 0 .. C - 1, then the macro mean from
+ * mean_b) x {n_valid, mean, standard deviation (ddof = 1), lower, upper} over the n_valid non-NaN resamples; lower / upper =
+ * numpy.percentile(valid, [100 alpha / 2, 100 (1 - alpha / 2)]) (linear interpolation on the ascending values, sorted in LDS).
+ * Sums are float64 in a fixed order.  n_valid < 2: deviation and interval NaN; n_valid = 0: the mean too.  0 < alpha < 1.
+ *
+ * rd_rank_bootstrap_counts: the multiplicities themselves, counts u32 [nr][N] = m_r for r = r0 .. r0 + nr - 1 (0 <= r0,
+ * r0 + nr <= R), by the device function the statistics use: the tests' handle on the resample rule. */
+size_t rd_rank_bootstrap_workspace_bytes(int64_t N, int32_t C, int32_t R);
+int rd_rank_bootstrap(int64_t N, int32_t C, const float* scores, int64_t ld, const int64_t* y, int32_t R, uint64_t seed,
+                      double* auroc_b, double* auprc_b, int64_t* auroc_num_b, int64_t* pos_b, double* mean_b, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int rd_rank_bootstrap_summary(int32_t R, int32_t C, const double* auroc_b, const double* auprc_b, const double* mean_b, double alpha,
+                              double* summary, void* stream);
+int rd_rank_bootstrap_counts(int64_t N, int32_t R, uint64_t seed, int32_t r0, int32_t nr, uint32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

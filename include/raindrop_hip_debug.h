@@ -25,7 +25,9 @@ void rd_debug_set_splitk_want(int workgroups);       /* target workgroup count o
 /* Launch log (tests/switch_child.py): host memory only, no kernel sees it.  While it is on, every launch site records the name it
  * reports to the error check (the kernel, with the tile / prefetch / column-group variant where one name would cover two paths).
  * Switching it (either way) clears the set; off, the default, costs a launch one load and one branch.  The read copies the distinct
- * names so far, joined by '\n' and NUL-terminated, into out[cap] (whole names only) and returns the length all of them need. */
+ * names so far, joined by '\n' and NUL-terminated, into out[cap] (whole names only) and returns the length all of them need.
+ * The bootstrap of the validation metrics (rd_metrics_boot.hip) reports "k_boot_sort", "k_boot_stats", "k_boot_means"
+ * (rd_rank_bootstrap), "k_boot_summary" (rd_rank_bootstrap_summary) and "k_boot_counts" (rd_rank_bootstrap_counts). */
 void rd_debug_launch_log(int on);
 size_t rd_debug_launch_log_read(char* out, size_t cap);
 /* The route one encoder layer of this shape takes (rd_temporal.hip enc_route) in the current arithmetic mode and switches, with or

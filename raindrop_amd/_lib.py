@@ -211,6 +211,12 @@ SIGNATURES = {
     "rd_rank_metrics_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32]),
     "rd_rank_metrics": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "rd_confusion": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P]),
+    # bootstrap of the ranking statistics (raindrop_amd.metrics.rank_bootstrap): N, C, scores, ld, y, R, seed, five outputs, workspace
+    "rd_rank_bootstrap_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32, c_int32]),
+    "rd_rank_bootstrap": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, c_int32, ctypes.c_uint64] + [_P] * 5
+                          + [_P, c_size_t, _P]),
+    "rd_rank_bootstrap_summary": (c_int32, [c_int32, c_int32, _P, _P, _P, ctypes.c_double, _P, _P]),
+    "rd_rank_bootstrap_counts": (c_int32, [ctypes.c_int64, c_int32, ctypes.c_uint64, c_int32, c_int32, _P, _P]),
 }
 # hooks of include/raindrop_hip_debug.h that tests call through this binding (not part of the ABI)
 DEBUG_SIGNATURES = {

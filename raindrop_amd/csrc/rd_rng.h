@@ -80,6 +80,8 @@ enum DropSite : uint32_t { SITE_OBS_EMBED = 1, SITE_EDGE_COEFF = 2, SITE_ATTN_PR
                            SITE_FFN_OUT = 64,     // + layer index for the encoder sites
                            // input augmentation of the batch feed (rd_feed_aug.hip): time step b*T + t, sensor b*F + f, observation
                            // (t*B + b)*F + f and the jitter's whole quad (t*B + b)*F + f, t the row of the SOURCE sample
-                           SITE_FEED_TIME = 80, SITE_FEED_SENSOR = 81, SITE_FEED_OBS = 82, SITE_FEED_NOISE = 83 };
+                           SITE_FEED_TIME = 80, SITE_FEED_SENSOR = 81, SITE_FEED_OBS = 82, SITE_FEED_NOISE = 83,
+                           // bootstrap resampling of the validation metrics (rd_metrics_boot.hip): raw 32-bit words, not uniforms
+                           SITE_BOOTSTRAP = 84 };
 
 }  // namespace rd

@@ -509,9 +509,22 @@ def evaluate_captured(model, ds, chunk=2048, group=None, save_free=True):
     return torch.cat(parts, 0)[: ds.N].to(ds.dev)
 
 
+def check_bootstrap(bootstrap, bootstrap_seed=0, ci=0.95):
+    """`validate`'s / `fit`'s bootstrap keywords, refused without a device: bootstrap None or an integer in [1, 4096]
+    (metrics.BOOT_R_MAX), bootstrap_seed an integer in [0, 2^64), 0 < ci < 1"""
+    from .metrics import BOOT_R_MAX
+    if bootstrap is not None and (isinstance(bootstrap, bool) or not isinstance(bootstrap, (int, np.integer))
+                                  or not 1 <= bootstrap <= BOOT_R_MAX):
+        raise ValueError("bootstrap must be None or an integer in [1, %d] (resamples), got %r" % (BOOT_R_MAX, bootstrap))
+    if isinstance(bootstrap_seed, bool) or not isinstance(bootstrap_seed, (int, np.integer)) or not 0 <= bootstrap_seed < 2 ** 64:
+        raise ValueError("bootstrap_seed must be an integer in [0, 2^64), got %r" % (bootstrap_seed,))
+    if isinstance(ci, bool) or not isinstance(ci, (int, float)) or not 0.0 < ci < 1.0:
+        raise ValueError("ci must lie in (0, 1) (0.95: the 2.5th and 97.5th percentiles), got %r" % (ci,))
+
+
 @torch.no_grad()
 def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True, class_weight=None, label_smoothing=0.0,
-             focal_gamma=None):
+             focal_gamma=None, bootstrap=None, bootstrap_seed=0, ci=0.95):
     """The validation / test block of the reference's loop (`code/Raindrop.py:345-370,385-401`) without leaving the device until
     the end: `evaluate_captured` -> `transform` of the logits with torch ("sigmoid": validation, :349; "softmax": test, :388-389;
     None: the logits) -> `metrics.rank_metrics`, `metrics.confusion` and `rd_softmax_xent` on the TRANSFORMED scores (the
@@ -523,9 +536,17 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     class_weight / label_smoothing (raindrop_amd.step.criterion_values): `loss` is CrossEntropyLoss(weight=class_weight,
     label_smoothing=label_smoothing) of the same scores (`rd_softmax_xent_crit`), the training steps' criterion; no other field
     changes.  focal_gamma (raindrop_amd.step.focal_values; label_smoothing must be 0): `loss` is the focal loss of the same scores
-    with these class weights (`rd_softmax_xent_focal`); no other field changes."""
+    with these class weights (`rd_softmax_xent_focal`); no other field changes.
+    bootstrap=R (1 .. 4096; the split must have at most 16384 samples): `metrics.rank_bootstrap(scores, y, n_boot=R, seed=bootstrap_seed,
+    alpha=1 - ci)` on the same scores -- with a `group`, on the gathered scores of every rank, the same seed and so the same
+    resamples everywhere -- and the result gains, for the column `auroc` / `auprc` describe (binary: column 1; more classes: the
+    macro mean), `auroc_ci`, `auprc_ci` ((lower, upper): the two-sided percentile interval at level `ci`), `auroc_se`, `auprc_se` (the
+    bootstrap standard error) and `bootstrap_valid` (the resamples whose AUROC is defined: one without a positive or a negative of
+    a column is left out of its interval; the AUPRC is defined on all R), in the same device-to-host copy.  None: the launches and
+    the keys as without it."""
     from . import metrics
     from .step import check_focal, criterion_values, focal_values
+    check_bootstrap(bootstrap, bootstrap_seed, ci)
     if ds.y is None:
         raise _lib.RaindropHipError("validate needs the dataset's labels (DeviceDataset(..., y=...))")
     if transform not in ("sigmoid", "softmax", None):
@@ -552,20 +573,30 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
         _lib.call("rd_softmax_xent_crit", int(N), int(C), _p(scores), _p(ds.y), _p(critd), _p(loss), _p(dscores), st)
     else:
         _lib.call("rd_softmax_xent", int(N), int(C), _p(scores), _p(ds.y), _p(loss), _p(dscores), st)
-    packed = torch.cat([r["mean"], loss.double(), r["auroc_per_class"], r["auprc_per_class"], cm.reshape(-1).double()]).cpu().numpy()
-    auroc_pc, auprc_pc = packed[3:3 + C].copy(), packed[3 + C:3 + 2 * C].copy()
-    cmh = np.rint(packed[3 + 2 * C:]).astype(np.int64).reshape(C, C)             # counts < 2^53: exact in float64
-    acc, prec, rec, f1 = metrics.summary_from_confusion(cmh)
     binary = C == 2
-    return {"auroc": float(auroc_pc[1] if binary else packed[0]), "auprc": float(auprc_pc[1] if binary else packed[1]),
-            "loss": float(packed[2]), "accuracy": acc, "precision": prec, "recall": rec, "f1": f1,
-            "auroc_per_class": auroc_pc, "auprc_per_class": auprc_pc, "confusion": cmh}
+    parts = [r["mean"], loss.double(), r["auroc_per_class"], r["auprc_per_class"], cm.reshape(-1).double()]
+    if bootstrap is not None:                              # the (n_valid, mean, deviation, lower, upper) rows of the reported column
+        boot = metrics.rank_bootstrap(scores, ds.y, n_boot=int(bootstrap), seed=int(bootstrap_seed), alpha=1.0 - float(ci))
+        parts.append(boot["summary"][:, 1 if binary else C, :].reshape(-1))
+    packed = torch.cat(parts).cpu().numpy()
+    auroc_pc, auprc_pc = packed[3:3 + C].copy(), packed[3 + C:3 + 2 * C].copy()
+    cmh = np.rint(packed[3 + 2 * C:3 + 2 * C + C * C]).astype(np.int64).reshape(C, C)             # counts < 2^53: exact in float64
+    acc, prec, rec, f1 = metrics.summary_from_confusion(cmh)
+    out = {"auroc": float(auroc_pc[1] if binary else packed[0]), "auprc": float(auprc_pc[1] if binary else packed[1]),
+           "loss": float(packed[2]), "accuracy": acc, "precision": prec, "recall": rec, "f1": f1,
+           "auroc_per_class": auroc_pc, "auprc_per_class": auprc_pc, "confusion": cmh}
+    if bootstrap is not None:
+        sa, sp = packed[-10:-5], packed[-5:]
+        out.update(auroc_ci=(float(sa[3]), float(sa[4])), auprc_ci=(float(sp[3]), float(sp[4])), auroc_se=float(sa[2]),
+                   auprc_se=float(sp[2]), bootstrap_valid=int(sa[0]))
+    return out
 
 
 def validate_ema(model, ds, opt, **kw):
     """`validate(model, ds, **kw)` on the AVERAGED weights of `opt` (raindrop_amd.optim.FlatAdam(ema_decay=...)): the flat
     parameters and their average change places for the duration (`opt.ema_weights()`: two in-place exchanges, rd_swap_f32), and the
     cached captured forwards, which read the parameters by address, are replayed as they are -- no new capture, no copy of the
-    model.  The training weights are back, bit for bit, when it returns."""
+    model.  The training weights are back, bit for bit, when it returns.  Every keyword of `validate` passes through, `bootstrap`,
+    `bootstrap_seed` and `ci` among them: the interval then belongs to the averaged weights."""
     with opt.ema_weights():
         return validate(model, ds, **kw)

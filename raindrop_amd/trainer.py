@@ -62,9 +62,10 @@ class ReduceOnPlateau:
 
 
 def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
-                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0, augment=None):
+                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0, augment=None, bootstrap=None, bootstrap_seed=0):
     """what can be refused without a device"""
     _resolve_augment(augment)
+    feed_mod.check_bootstrap(bootstrap, bootstrap_seed)
     if focal_gamma is not None:
         from .step import check_focal, focal_values
         focal_values(None, focal_gamma, 1)                                 # the range of gamma (the weights need the model's class count)
@@ -156,7 +157,7 @@ def _live_names(model):
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
         param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1,
-        focal_gamma=None, augment=None):
+        focal_gamma=None, augment=None, bootstrap=None, bootstrap_seed=0):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -198,10 +199,15 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     (`EpochFeed(augment=)`: time-step, sensor and observation drop, value jitter; fresh masks every batch and epoch from
     (seed, epoch, cursor)).  Validation, the best-weights logic and every other path are untouched.  None: as without it.
 
+    bootstrap=R (1 .. 4096; `val_ds` of at most 16384 samples): once, at the end, on the restored best weights (never per epoch),
+    `feed.validate(model, val_ds, bootstrap=R, bootstrap_seed=bootstrap_seed)` with the run's transform and criterion, and the result
+    gains `val_ci`: a dict of that validation's `auroc`, `auprc`, `auroc_ci`, `auprc_ci` (95 % percentile intervals), `auroc_se`,
+    `auprc_se` and `bootstrap_valid`.  None: as without it.
+
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
     _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps,
-                    accumulate, focal_gamma, label_smoothing, augment)
+                    accumulate, focal_gamma, label_smoothing, augment, bootstrap, bootstrap_seed)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -274,10 +280,16 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
                 best = src.clone() if best is None else best.copy_(src)
         if best is not None:
             opt.param.data.copy_(best)
+        val_ci = None
+        if bootstrap is not None:                                          # the parameters now hold what `best_auroc` was measured on
+            v = feed_mod.validate(model, val_ds, bootstrap=int(bootstrap), bootstrap_seed=int(bootstrap_seed), **vkw)
+            val_ci = {k: v[k] for k in ("auroc", "auprc", "auroc_ci", "auprc_ci", "auroc_se", "auprc_se", "bootstrap_valid")}
     finally:
         step.close()
         model.train(was_training)
     out["best_epoch"], out["best_auroc"] = best_epoch, best_auroc
     if accumulate > 1:
         out["optimizer_steps"] = optimizer_steps
+    if bootstrap is not None:
+        out["val_ci"] = val_ci
     return out
