@@ -104,7 +104,7 @@ LSETS = ("full", "ones", "zero", "ties", "l89")
 PLAN_CASES = [(s, l) for s in PLAN_INSIDE for l in LSETS] + [(s, "ties") for s in PLAN_OUTSIDE]
 
 # A case whose gap-placed biases miss GATE_MARGIN (or the open share) gets another seed here -- never another margin.
-SEED_BUMP = {}
+SEED_BUMP = {("panel/M1", 1, 17, 1): 10}      # tests/panel_ref.py M1: the first seed at which the one row's last reduction index shows in z
 
 VARIANTS = {"leftover_row": ("padded", "F34_B17"),       # the last leftover row of one sample dropped from dW1 and dW2
             "gate_neighbour": ("padded", "F34_B17"),     # one layer-1 gate taken from the neighbouring row
@@ -347,6 +347,9 @@ def evaluate(c, variant=None):
         assert K % 32 == 16
         Xin = X.copy()
         Xin[:, :, 32 * (K // 32):] = 0.0
+    if variant == "drop_last_k":                           # tests/panel_ref.py: the last reduction index of both products never runs
+        Xin = X.copy()
+        Xin[:, :, K - 1] = 0.0
     pre1 = Xin @ W1.T + b1
     g1 = pre1 > 0
     if variant == "gate_neighbour":                        # row (b, f) of one column gated by row (b, f + 1)'s bit
@@ -356,7 +359,11 @@ def evaluate(c, variant=None):
         g1 = g1.copy()
         g1[b_, f_, n_] = g1[b_, f_ + 1, n_]
     Y1 = np.where(g1, pre1, 0.0) * s1[:, :, None]
-    pre2 = Y1 @ W2.T + b2
+    Y1in = Y1
+    if variant == "drop_last_k":
+        Y1in = Y1.copy()
+        Y1in[:, :, K - 1] = 0.0
+    pre2 = Y1in @ W2.T + b2
     g2 = pre2 > 0
     Y2 = np.where(g2, pre2, 0.0) * s2[:, :, None]
     z = Y2.reshape(B, F, T, D_OB).transpose(2, 0, 1, 3).reshape(T, B, F * D_OB)

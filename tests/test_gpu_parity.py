@@ -156,7 +156,8 @@ def test_sensor_stage_vs_oracle(cfg_name, B, kind, panel, monkeypatch):
     the d_ob = 4 scatter and the gate-mask epilogues -- `panel`: "0" the 64 x 128 workgroup tile, "1" round 6's 128 x 256 one, "pc" its
     128 x 128 producer / consumer one (ragged in both halves of their rows at 180 / 324 / 153 rows, in the last column block at 860
     and 2400 columns);
-    P19 the fused kernels; TINY the tiled GEMM."""
+    P19 the fused kernels; TINY the tiled GEMM.  The places of the three panel kernels these shapes never enter (one chunk, odd chunk
+    counts, K tails, M around 64 and 128, few tiles) are held to float64 in every forced form by tests/test_panel_float64_gpu.py."""
     from raindrop_amd import _lib, ops
     if panel == "pc":                                     # the 128 x 128 producer / consumer form (waves 4-7 convert, waves 0-3 multiply)
         monkeypatch.setenv("RD_PANEL_PC", "1")
