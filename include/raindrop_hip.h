@@ -974,6 +974,50 @@ int rd_rank_bootstrap_summary(int32_t R, int32_t C, const double* auroc_b, const
                               double* summary, void* stream);
 int rd_rank_bootstrap_counts(int64_t N, int32_t R, uint64_t seed, int32_t r0, int32_t nr, uint32_t* counts, void* stream);
 
+/* Calibration (raindrop_amd/csrc/rd_metrics_calib.hip): whether a predicted 0.8 means 80 % -- the reliability table and its
+ * summaries, and the temperature (Guo et al., 2017) that minimises the NLL of softmax(logits / T).  Asynchronous, capturable,
+ * caller-owned memory only, no floating-point atomics, every sum float64 in an order that is a function of the shapes alone: two
+ * calls give the same bits.  Argument errors RD_EINVAL before any launch; outside the envelope RD_EUNSUPPORTED, no CPU fallback.
+ *
+ * rd_calibration: logits f32 [N, C] with row stride ld (floats), y int64 [N]; `temperature` a DEVICE float64 (so a fit's result
+ * feeds it without a sync; its element 0 is read; NULL: T = 1; T > 0 is the caller's business).  p = softmax(logits / T) in
+ * float64, max-subtracted.  column = -1, top-label mode: confidence = max_c p, hit = (argmax == y), the argmax the FIRST maximum of
+ * the row's logits (np.argmax).  column = c, one-vs-rest mode: confidence = p[:, c], hit = (y == c).
+ * Bin rule.  M equal-width bins with the edges e_i = (double)i / (double)M; a confidence falls in bin i iff e_i < conf <= e_{i+1}
+ * (closed on the right: 0.5 with M = 10 is bin 4, 1.0 the last bin), and a confidence of exactly 0 goes to bin 0.  A NaN
+ * confidence (a NaN logit) enters no bin.
+ *   counts  int64 [M][2]   {n_b, hits_b}, exact
+ *   table   f64 [M][3]     {n_b, mean confidence, hit rate}; the last two NaN for an empty bin
+ *   summary f64 [6]        0 ECE = sum_b (n_b / N) |hit rate_b - mean confidence_b|     1 MCE = the maximum of that gap over the
+ *                          NON-EMPTY bins (0 when all are empty)     2 Brier     3 NLL = -mean log p[n, y_n], always of the full
+ *                          softmax, whatever the column     4 hit rate = sum hits_b / N     5 mean confidence = sum of the binned
+ *                          confidences / N
+ * Brier.  Top-label mode: mean_n sum_c (p_nc - [y_n = c])^2.  Column mode: mean_n (p_nc - [y_n = c])^2 of that column alone
+ * (sklearn's brier_score_loss).  A label outside [0, C) makes its row a miss whose NLL and Brier terms are NaN (not refused: that
+ * would cost a sync, the NaN-scores rule of rd_rank_metrics).
+ * Envelope: 1 <= N < 2^24, 2 <= C <= 64, 1 <= M <= 256.  ceil(N / rows per workgroup) <= 1024 workgroups of 256 threads leave
+ * per-bin partials in `workspace` (rd_calibration_workspace_bytes, 0 outside the envelope; 8-byte aligned; the layout depends on N
+ * and M alone), one finishing workgroup sums them in workgroup order.
+ *
+ * rd_fit_temperature: the scalar T that minimises NLL(T) = mean_n [logsumexp(z_n / T) - z_{n,y} / T], found in beta = 1 / T, where
+ * the objective is convex: g(beta) = mean(E_p[z] - z_y) and h(beta) = mean(Var_p[z]) = g' >= 0, p = softmax(beta z).  Bracket
+ * [1e-2, 1e2]; the start is beta = 1, whose sign of g says on which side the minimum lies; g at the bracket's end on that side
+ * decides between an interior minimum and a stop at the end; then a safeguarded Newton iteration from beta = 1 -- a step that
+ * leaves the bracket, has h <= 0 or does not halve the previous step is replaced by the bracket's midpoint, and the sign of g at
+ * every new beta moves one end of the bracket there.  It stops when the step or the bracket is <= 1e-12 beta, when g is exactly 0,
+ * or after 100 evaluations of (g, h), the two above included.
+ *   result f64 [8]   0 T     1 beta     2 NLL at T = 1     3 NLL at T     4 evaluations of (g, h)     5 status     6 g at the end     7 0
+ * Status.  0 interior minimum (constant rows, g = 0 at beta = 1: T = 1)     1 stopped at T = 1e-2: the rows are separable and the
+ * NLL still falls     2 stopped at T = 1e2 (labels worse than chance)     3 the evaluation cap was reached     4 a non-finite
+ * gradient was met (a NaN or infinite logit, a label outside [0, C)): T = 1, beta = 1 and NLL at T = NLL at 1 are written, so
+ * nothing downstream is poisoned.
+ * Envelope: 1 <= N <= 16384 (the bootstrap's), 2 <= C <= 64.  One launch of one 1024-thread workgroup; the logits are staged once in
+ * LDS when N C 4 <= 159 KiB, else re-read from global memory every evaluation: the same bits either way. */
+size_t rd_calibration_workspace_bytes(int64_t N, int32_t C, int32_t M);
+int rd_calibration(int64_t N, int32_t C, const float* logits, int64_t ld, const int64_t* y, const double* temperature, int32_t column,
+                   int32_t M, int64_t* counts, double* table, double* summary, void* workspace, size_t workspace_bytes, void* stream);
+int rd_fit_temperature(int64_t N, int32_t C, const float* logits, int64_t ld, const int64_t* y, double* result, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

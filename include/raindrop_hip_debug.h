@@ -27,7 +27,9 @@ void rd_debug_set_splitk_want(int workgroups);       /* target workgroup count o
  * Switching it (either way) clears the set; off, the default, costs a launch one load and one branch.  The read copies the distinct
  * names so far, joined by '\n' and NUL-terminated, into out[cap] (whole names only) and returns the length all of them need.
  * The bootstrap of the validation metrics (rd_metrics_boot.hip) reports "k_boot_sort", "k_boot_stats", "k_boot_means"
- * (rd_rank_bootstrap), "k_boot_summary" (rd_rank_bootstrap_summary) and "k_boot_counts" (rd_rank_bootstrap_counts). */
+ * (rd_rank_bootstrap), "k_boot_summary" (rd_rank_bootstrap_summary) and "k_boot_counts" (rd_rank_bootstrap_counts).
+ * The calibration (rd_metrics_calib.hip) reports "k_calib_rows", "k_calib_finish" (rd_calibration) and "k_fit_temperature<lds>" or
+ * "k_fit_temperature<global>" (rd_fit_temperature: the logits staged in LDS, or re-read from global memory). */
 void rd_debug_launch_log(int on);
 size_t rd_debug_launch_log_read(char* out, size_t cap);
 /* The route one encoder layer of this shape takes (rd_temporal.hip enc_route) in the current arithmetic mode and switches, with or
@@ -83,6 +85,11 @@ int rd_debug_splitk_plan(int64_t red, int32_t rows, int32_t cols, int32_t* k_per
  *    words[5 + j]  first tile blk0 of job j (d mlp_static[0], d mlp_static[2], d emb)   words[8 + j]  its tiles: n << 16 | k */
 int rd_debug_head_route(int32_t mode, int32_t B, int32_t D, int32_t d_static, int32_t Fe, int32_t C, int32_t with_crit, uint32_t* words,
                         char* name, size_t cap);
+/* The form one rd_fit_temperature call of [N, C] logits takes (rd_metrics_calib.hip fit_route, the function the launch site calls).
+ * Needs no device.  Bit 0 of *bits: stage, the logits are copied into LDS once (else every evaluation re-reads global memory); bits
+ * 8-31: the launch's dynamic LDS bytes (N C 4 when staged, else 0).  Returns RD_OK, or RD_EUNSUPPORTED outside the fit's envelope. */
+int rd_debug_calibration_route(int64_t N, int32_t C, uint32_t* bits);
+void rd_debug_set_calibration_stage(int on);         /* 0: rd_fit_temperature never stages (the route query follows); 1, the default: by the budget */
 
 #ifdef __cplusplus
 }

@@ -217,6 +217,11 @@ SIGNATURES = {
                           + [_P, c_size_t, _P]),
     "rd_rank_bootstrap_summary": (c_int32, [c_int32, c_int32, _P, _P, _P, ctypes.c_double, _P, _P]),
     "rd_rank_bootstrap_counts": (c_int32, [ctypes.c_int64, c_int32, ctypes.c_uint64, c_int32, c_int32, _P, _P]),
+    # calibration (raindrop_amd.metrics.calibration / fit_temperature): N, C, logits, ld, y, temperature, column, M, counts, table,
+    # summary, workspace | N, C, logits, ld, y, result
+    "rd_calibration_workspace_bytes": (c_size_t, [ctypes.c_int64, c_int32, c_int32]),
+    "rd_calibration": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, c_int32, c_int32, _P, _P, _P, _P, c_size_t, _P]),
+    "rd_fit_temperature": (c_int32, [ctypes.c_int64, c_int32, _P, ctypes.c_int64, _P, _P, _P]),
 }
 # hooks of include/raindrop_hip_debug.h that tests call through this binding (not part of the ABI)
 DEBUG_SIGNATURES = {
@@ -228,6 +233,8 @@ DEBUG_SIGNATURES = {
     "rd_debug_splitk_plan": (c_int32, [ctypes.c_int64, c_int32, c_int32, _P]),      # red, rows, cols, *k_per_split -> nsplit
     # mode, B, D, d_static, Fe, C, with_crit (2: the focal form), words[11] (bits of words[0]: HEAD_ROUTE_BITS below), name, cap
     "rd_debug_head_route": (c_int32, [c_int32] * 7 + [_P, _P, c_size_t]),
+    "rd_debug_calibration_route": (c_int32, [ctypes.c_int64, c_int32, _P]),         # N, C; bit 0 of *bits: staged in LDS, bits 8-31 its bytes
+    "rd_debug_set_calibration_stage": (None, [c_int32]),                            # 0: never stage; 1 (default): by the budget
 }
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",

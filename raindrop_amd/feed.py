@@ -522,9 +522,25 @@ def check_bootstrap(bootstrap, bootstrap_seed=0, ci=0.95):
         raise ValueError("ci must lie in (0, 1) (0.95: the 2.5th and 97.5th percentiles), got %r" % (ci,))
 
 
+def check_calibration(calibration, temperature=None):
+    """`validate`'s calibration keywords (and `fit`'s bins), refused without a device: calibration None or an integer number of bins
+    in [1, 256] (metrics.CALIB_M_MAX); temperature None, "fit" or a positive finite float, and only together with `calibration`"""
+    from .metrics import CALIB_M_MAX
+    if calibration is not None and (isinstance(calibration, bool) or not isinstance(calibration, (int, np.integer))
+                                    or not 1 <= calibration <= CALIB_M_MAX):
+        raise ValueError("calibration must be None or an integer in [1, %d] (bins), got %r" % (CALIB_M_MAX, calibration))
+    if temperature is None:
+        return
+    if temperature != "fit" and (isinstance(temperature, (bool, str)) or not isinstance(temperature, (int, float, np.integer, np.floating))
+                                 or not 0.0 < float(temperature) < float("inf")):
+        raise ValueError("temperature must be None, 'fit' or a positive finite float, got %r" % (temperature,))
+    if calibration is None:
+        raise ValueError("temperature=%r needs calibration=<bins>: it scales the calibration statistics only" % (temperature,))
+
+
 @torch.no_grad()
 def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=True, class_weight=None, label_smoothing=0.0,
-             focal_gamma=None, bootstrap=None, bootstrap_seed=0, ci=0.95):
+             focal_gamma=None, bootstrap=None, bootstrap_seed=0, ci=0.95, calibration=None, temperature=None):
     """The validation / test block of the reference's loop (`code/Raindrop.py:345-370,385-401`) without leaving the device until
     the end: `evaluate_captured` -> `transform` of the logits with torch ("sigmoid": validation, :349; "softmax": test, :388-389;
     None: the logits) -> `metrics.rank_metrics`, `metrics.confusion` and `rd_softmax_xent` on the TRANSFORMED scores (the
@@ -543,10 +559,21 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     macro mean), `auroc_ci`, `auprc_ci` ((lower, upper): the two-sided percentile interval at level `ci`), `auroc_se`, `auprc_se` (the
     bootstrap standard error) and `bootstrap_valid` (the resamples whose AUROC is defined: one without a positive or a negative of
     a column is left out of its interval; the AUPRC is defined on all R), in the same device-to-host copy.  None: the launches and
-    the keys as without it."""
+    the keys as without it.
+    calibration=M (1 .. 256 bins; at most 64 classes): `metrics.calibration(logits, y, n_bins=M, temperature=T)` and the result gains
+    `ece`, `mce`, `brier`, `nll` and the numpy arrays `reliability` [M, 3] (rows, mean confidence, hit rate of every bin; NaN, NaN for
+    an empty one) and `reliability_counts` [M, 2] int64 (rows, hits), in the same copy.  They are ALWAYS statistics of
+    softmax(logits / T), whatever `transform` is (the sigmoid of two logits is not a distribution), for the column `auroc` describes:
+    binary, column 1 one-vs-rest; more classes, the top label.  temperature: None (T = 1), a float, or "fit":
+    `metrics.fit_temperature` on this split's logits (at most 16384 samples; with a `group` the gathered logits, so every rank gets
+    the same T), which adds `temperature`, `temperature_status` (0: an interior minimum; include/raindrop_hip.h), `ece_uncalibrated`
+    and `nll_uncalibrated` (both at T = 1).  A T fitted and scored on the same split is optimistic: the intended use is "fit" on the
+    validation split and that float on the test split.  `temperature` without `calibration` is refused.  None, None: the launches
+    and the keys as without them."""
     from . import metrics
     from .step import check_focal, criterion_values, focal_values
     check_bootstrap(bootstrap, bootstrap_seed, ci)
+    check_calibration(calibration, temperature)
     if ds.y is None:
         raise _lib.RaindropHipError("validate needs the dataset's labels (DeviceDataset(..., y=...))")
     if transform not in ("sigmoid", "softmax", None):
@@ -578,6 +605,17 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     if bootstrap is not None:                              # the (n_valid, mean, deviation, lower, upper) rows of the reported column
         boot = metrics.rank_bootstrap(scores, ds.y, n_boot=int(bootstrap), seed=int(bootstrap_seed), alpha=1.0 - float(ci))
         parts.append(boot["summary"][:, 1 if binary else C, :].reshape(-1))
+    at_boot = 3 + 2 * C + C * C                            # where the bootstrap rows start; the calibration follows them
+    at_cal = at_boot + (10 if bootstrap is not None else 0)
+    if calibration is not None:                            # summary[:4], table, counts [, T, status, ECE and NLL at T = 1]
+        M, col = int(calibration), 1 if binary else None
+        fitted = metrics.fit_temperature(logits, ds.y) if temperature == "fit" else None
+        cal = metrics.calibration(logits, ds.y, n_bins=M, column=col,
+                                  temperature=fitted["result"] if fitted is not None else None if temperature is None else float(temperature))
+        parts += [cal["summary"][:4], cal["table"].reshape(-1), cal["counts"].reshape(-1).double()]
+        if fitted is not None:
+            plain = metrics.calibration(logits, ds.y, n_bins=M, column=col)
+            parts += [fitted["result"][0:1], fitted["result"][5:6], plain["summary"][0:1], plain["summary"][3:4]]
     packed = torch.cat(parts).cpu().numpy()
     auroc_pc, auprc_pc = packed[3:3 + C].copy(), packed[3 + C:3 + 2 * C].copy()
     cmh = np.rint(packed[3 + 2 * C:3 + 2 * C + C * C]).astype(np.int64).reshape(C, C)             # counts < 2^53: exact in float64
@@ -586,9 +624,16 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
            "loss": float(packed[2]), "accuracy": acc, "precision": prec, "recall": rec, "f1": f1,
            "auroc_per_class": auroc_pc, "auprc_per_class": auprc_pc, "confusion": cmh}
     if bootstrap is not None:
-        sa, sp = packed[-10:-5], packed[-5:]
+        sa, sp = packed[at_boot:at_boot + 5], packed[at_boot + 5:at_boot + 10]
         out.update(auroc_ci=(float(sa[3]), float(sa[4])), auprc_ci=(float(sp[3]), float(sp[4])), auroc_se=float(sa[2]),
                    auprc_se=float(sp[2]), bootstrap_valid=int(sa[0]))
+    if calibration is not None:
+        k = packed[at_cal:]
+        out.update(ece=float(k[0]), mce=float(k[1]), brier=float(k[2]), nll=float(k[3]), reliability=k[4:4 + 3 * M].reshape(M, 3).copy(),
+                   reliability_counts=np.rint(k[4 + 3 * M:4 + 5 * M]).astype(np.int64).reshape(M, 2))       # counts < 2^53: exact
+        if temperature == "fit":
+            f = k[4 + 5 * M:]
+            out.update(temperature=float(f[0]), temperature_status=int(f[1]), ece_uncalibrated=float(f[2]), nll_uncalibrated=float(f[3]))
     return out
 
 
@@ -597,6 +642,6 @@ def validate_ema(model, ds, opt, **kw):
     parameters and their average change places for the duration (`opt.ema_weights()`: two in-place exchanges, rd_swap_f32), and the
     cached captured forwards, which read the parameters by address, are replayed as they are -- no new capture, no copy of the
     model.  The training weights are back, bit for bit, when it returns.  Every keyword of `validate` passes through, `bootstrap`,
-    `bootstrap_seed` and `ci` among them: the interval then belongs to the averaged weights."""
+    `bootstrap_seed` and `ci` among them: the interval then belongs to the averaged weights; `calibration` and `temperature` likewise."""
     with opt.ema_weights():
         return validate(model, ds, **kw)

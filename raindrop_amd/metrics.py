@@ -10,6 +10,9 @@ distinct scores, ties form one group); results stay device tensors until the cal
                                                     # r["auroc_num"]: [C] int64, the exact numerators  sum (fp - fp')(tp + tp')
     b = rank_bootstrap(scores, y, n_boot=1000)      # b["auroc_ci"], b["auprc_ci"]: [C, 2] percentile intervals over 1000 resamples of
                                                     # the rows (raindrop_amd/csrc/rd_metrics_boot.hip; N <= 16384, n_boot <= 4096)
+    f = fit_temperature(logits, y)                  # f["temperature"]: the T that minimises the NLL of softmax(logits / T)
+    k = calibration(logits, y, n_bins=15, temperature=f["result"])     # k["ece"], k["table"] [15, 3]: the reliability diagram
+                                                    # (raindrop_amd/csrc/rd_metrics_calib.hip; C <= 64, n_bins <= 256)
     cm = confusion(logits, y)                       # [C, C] int64, rows = true class, columns = argmax
     acc, prec, rec, f1 = summary_from_confusion(cm.cpu().numpy())
 
@@ -129,6 +132,81 @@ def bootstrap_counts(N, n_boot, seed, r0=0, nr=None, device="cuda"):
     with torch.cuda.device(counts.device):
         _lib.call("rd_rank_bootstrap_counts", int(N), int(n_boot), int(seed) & 0xFFFFFFFFFFFFFFFF, int(r0), nr, _p(counts), _stream())
     return counts
+
+
+CALIB_C_MAX, CALIB_M_MAX, FIT_N_MAX = 64, 256, 16384       # rd_calibration's / rd_fit_temperature's envelope (include/raindrop_hip.h)
+
+
+def calibration_workspace(N, C, n_bins, device):
+    """Workspace tensor `calibration` needs for [N, C] logits and `n_bins` bins (the workgroups' per-bin partials)."""
+    n = int(_lib.load().rd_calibration_workspace_bytes(int(N), int(C), int(n_bins)))
+    return torch.empty(max(n, 256), dtype=torch.uint8, device=device)
+
+
+def calibration(logits, y, n_bins=15, temperature=None, column=None, out=None, workspace=None):
+    """Reliability statistics of p = softmax(logits / T) (float64 on the device; include/raindrop_hip.h "Calibration" states the bin
+    rule -- `n_bins` equal-width bins closed on the right -- and both Brier definitions).  column=None: top-label mode, confidence =
+    max_c p against (argmax == y); column=c: one-vs-rest, confidence = p[:, c] against (y == c).  `temperature`: None (T = 1), a
+    Python float (uploaded, no sync) or a float64 device tensor whose element 0 is read -- `fit_temperature(...)["result"]` as it is.
+    2 <= C <= 64, n_bins <= 256, N < 2^24; there is no CPU fallback.  Returns a dict of device tensors:
+
+        counts      [n_bins, 2] int64    rows and hits of every bin, exact
+        table       [n_bins, 3] float64  rows, mean confidence, hit rate (NaN, NaN for an empty bin)
+        summary     [6] float64          ECE, MCE (over the non-empty bins), Brier, NLL (of the full softmax), hit rate, mean confidence;
+                                         the rest are 0-d views of it:
+        ece, mce, brier, nll, accuracy, confidence
+
+    `out`: the dict of a previous call, to write into the same tensors (captured use); `workspace`: from `calibration_workspace`."""
+    _check(logits, y, "calibration")
+    N, C = logits.shape
+    M = int(n_bins)
+    if N < 1:
+        raise _lib.RaindropHipError("calibration: no samples")
+    col = -1 if column is None else int(column)
+    if column is not None and not 0 <= col < C:
+        raise ValueError("calibration: column must be None (top-label) or a column of the logits, got %r" % (column,))
+    dev = logits.device
+    if temperature is None or torch.is_tensor(temperature):
+        T = temperature
+        if T is not None and (not T.is_cuda or T.dtype != torch.float64 or T.numel() < 1 or T.device != dev
+                              or (T.dim() > 0 and not T.is_contiguous())):
+            raise _lib.RaindropHipError("calibration: a temperature tensor must be float64 on the logits' device (element 0 is read)")
+    else:
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float, np.floating)) or not 0.0 < float(temperature) < float("inf"):
+            raise ValueError("calibration: temperature must be None, a positive float or a float64 device tensor, got %r" % (temperature,))
+        T = torch.tensor([float(temperature)], dtype=torch.float64, device=dev)
+    if out is None:
+        s = torch.empty(6, dtype=torch.float64, device=dev)
+        out = {"counts": torch.empty((M, 2), dtype=torch.int64, device=dev), "table": torch.empty((M, 3), dtype=torch.float64, device=dev),
+               "summary": s, "ece": s[0], "mce": s[1], "brier": s[2], "nll": s[3], "accuracy": s[4], "confidence": s[5]}
+    elif tuple(out["counts"].shape) != (M, 2):
+        raise _lib.RaindropHipError("calibration: out= holds %d bins, this call has %d" % (out["counts"].shape[0], M))
+    ws = calibration_workspace(N, C, M, dev) if workspace is None else workspace
+    _lib.call("rd_calibration", int(N), int(C), _p(logits), int(logits.stride(0)), _p(y), _p(T), col, M, _p(out["counts"]),
+              _p(out["table"]), _p(out["summary"]), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def fit_temperature(logits, y, out=None):
+    """Temperature scaling (Guo et al., 2017): the scalar T that minimises the NLL of softmax(logits / T) against `y`, by a
+    safeguarded Newton iteration in 1 / T run by one workgroup in one launch (include/raindrop_hip.h "rd_fit_temperature").  N <= 16384,
+    2 <= C <= 64; there is no CPU fallback.  Returns a dict of device tensors:
+
+        result      [8] float64: T, 1 / T, NLL at T = 1, NLL at T, evaluations, status, the gradient at the end, 0; the rest are
+                    0-d views of it:
+        temperature, nll_before, nll_after, iterations, status      status 0 interior minimum, 1 stopped at T = 0.01 (separable
+                    rows), 2 stopped at T = 100, 3 evaluation cap, 4 non-finite gradient (T = 1 is written)
+
+    `result` can be passed to `calibration(temperature=)` as it is: nothing reads it on the host.  `out`: the dict of a previous call."""
+    _check(logits, y, "fit_temperature")
+    N, C = logits.shape
+    if N < 1:
+        raise _lib.RaindropHipError("fit_temperature: no samples")
+    if out is None:
+        r = torch.empty(8, dtype=torch.float64, device=logits.device)
+        out = {"result": r, "temperature": r[0], "nll_before": r[2], "nll_after": r[3], "iterations": r[4], "status": r[5]}
+    _lib.call("rd_fit_temperature", int(N), int(C), _p(logits), int(logits.stride(0)), _p(y), _p(out["result"]), _stream())
+    return out
 
 
 def confusion(logits, y, out=None):

@@ -61,11 +61,22 @@ class ReduceOnPlateau:
         return float(self.opt.lr)
 
 
+# what `fit(calibrate=True)` keeps of the final validation (feed.validate(calibration=, temperature="fit"))
+CALIBRATION_KEYS = ("ece", "mce", "brier", "nll", "reliability", "reliability_counts", "ece_uncalibrated", "nll_uncalibrated", "temperature",
+                    "temperature_status")
+
+
 def _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups=None, decoupled_weight_decay=False, lr_schedule=None,
-                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0, augment=None, bootstrap=None, bootstrap_seed=0):
+                    warmup_steps=0, accumulate=1, focal_gamma=None, label_smoothing=0.0, augment=None, bootstrap=None, bootstrap_seed=0,
+                    calibrate=False, calibration_bins=15):
     """what can be refused without a device"""
     _resolve_augment(augment)
     feed_mod.check_bootstrap(bootstrap, bootstrap_seed)
+    if not isinstance(calibrate, bool):
+        raise ValueError("calibrate must be True or False, got %r" % (calibrate,))
+    if calibration_bins is None:
+        raise ValueError("calibration_bins must be an integer in [1, 256], got None")
+    feed_mod.check_calibration(calibration_bins)
     if focal_gamma is not None:
         from .step import check_focal, focal_values
         focal_values(None, focal_gamma, 1)                                 # the range of gamma (the weights need the model's class count)
@@ -157,7 +168,7 @@ def _live_names(model):
 def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, weight_decay=0.0, max_grad_norm=None, ema_decay=None,
         class_weight=None, label_smoothing=0.0, distance_weight=0.0, transform="sigmoid", scheduler=True, seed=None, autotune=True,
         param_groups=None, decoupled_weight_decay=False, lr_schedule=None, warmup_steps=0, accumulate=1,
-        focal_gamma=None, augment=None, bootstrap=None, bootstrap_seed=0):
+        focal_gamma=None, augment=None, bootstrap=None, bootstrap_seed=0, calibrate=False, calibration_bins=15):
     """Train `model` (raindrop_amd.models_rd.Raindrop_v2 on a ROCm device) on `train_ds` for `epochs` epochs, validating on `val_ds`
     after each (both `feed.DeviceDataset` with labels), the way the reference's script does (`code/Raindrop.py:256-381`):
 
@@ -204,10 +215,17 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
     gains `val_ci`: a dict of that validation's `auroc`, `auprc`, `auroc_ci`, `auprc_ci` (95 % percentile intervals), `auroc_se`,
     `auprc_se` and `bootstrap_valid`.  None: as without it.
 
+    calibrate=True (`val_ds` of at most 16384 samples, at most 64 classes): once, at the end, on the restored best weights, beside the
+    bootstrap, `feed.validate(model, val_ds, calibration=calibration_bins, temperature="fit")`, and the result gains `temperature` (the
+    T fitted on the validation logits: pass it to `validate(test_ds, calibration=, temperature=T)`) and `val_calibration`: a dict of
+    that validation's `ece`, `mce`, `brier`, `nll`, `reliability`, `reliability_counts`, `ece_uncalibrated`, `nll_uncalibrated`,
+    `temperature` and `temperature_status`.  The calibrated figures are of the split the T was fitted on, so they are optimistic.
+    False: as without it.
+
     One process, one GPU: data-parallel `fit` is not implemented (the feed itself works under data parallelism -- every rank loads
     its own plan rows -- but the planner, the scheduler and the best-checkpoint logic here do not coordinate ranks)."""
     _check_fit_args(train_ds, val_ds, epochs, batch_size, strategy, param_groups, decoupled_weight_decay, lr_schedule, warmup_steps,
-                    accumulate, focal_gamma, label_smoothing, augment, bootstrap, bootstrap_seed)
+                    accumulate, focal_gamma, label_smoothing, augment, bootstrap, bootstrap_seed, calibrate, calibration_bins)
     from .step import TrainStep
     from .step_beta import BetaTrainStep
     if seed is not None:
@@ -284,6 +302,10 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         if bootstrap is not None:                                          # the parameters now hold what `best_auroc` was measured on
             v = feed_mod.validate(model, val_ds, bootstrap=int(bootstrap), bootstrap_seed=int(bootstrap_seed), **vkw)
             val_ci = {k: v[k] for k in ("auroc", "auprc", "auroc_ci", "auprc_ci", "auroc_se", "auprc_se", "bootstrap_valid")}
+        val_cal = None
+        if calibrate:
+            v = feed_mod.validate(model, val_ds, calibration=int(calibration_bins), temperature="fit", **vkw)
+            val_cal = {k: v[k] for k in CALIBRATION_KEYS}
     finally:
         step.close()
         model.train(was_training)
@@ -292,4 +314,6 @@ def fit(model, train_ds, val_ds, epochs, batch_size=128, strategy=2, lr=1e-4, we
         out["optimizer_steps"] = optimizer_steps
     if bootstrap is not None:
         out["val_ci"] = val_ci
+    if calibrate:
+        out["temperature"], out["val_calibration"] = val_cal["temperature"], val_cal
     return out
