@@ -45,6 +45,17 @@ size_t rd_debug_launch_log_read(char* out, size_t cap);
  *    8 lnb          LayerNorm backward as the prologue of the next product
  * Returns RD_OK or the error of a bad shape. */
 int rd_debug_encoder_route(const struct rd_shape* s, int32_t with_plan, uint32_t* bits);
+/* The route one pass of the attention core over this shape takes (rd_attention.hip attn_route + attn_check, the functions
+ * attn_forward / attn_backward call) in the current arithmetic mode and switches.  pass: 0 forward, 1 backward; with_plan: a token
+ * plan is set; aligned: qkv, out and dout all start on 16-byte boundaries.  Needs no device.  Returns RD_OK, the error of a bad
+ * shape, or what the pass refuses (words and names are filled in either way): a token plan outside the split-bf16 families, and the
+ * materialised family, which only the layer runs.  The launch-log names go to name[cap], joined by ',', and
+ *    words[0]  bits 0-1 family (0 exact-fp32 tiled, 1 single-tile split-bf16, 2 multi-tile split-bf16, 3 materialised scores), 2 vec
+ *              (16-byte head-tile loads), 3 one_product, 4 wide (eight-wave single-tile form), 8-11 nth = ceil(head_dim / 16),
+ *              12-13 nlaunch (0 materialised; 2: dq then dk / dv)
+ *    words[1 + 5 i ..], launch i:  grid x, grid y, block, dynamic LDS bytes of the kernel's attribute, of the launch (0 past nlaunch) */
+int rd_debug_attention_route(const struct rd_shape* s, int32_t pass, int32_t with_plan, int32_t aligned, uint32_t* words, char* name,
+                             size_t cap);
 /* The route one sensor-stage call of this shape takes (rd_k1_route.h k1_route) in the current arithmetic mode and switches.  ldz: row
  * stride of z / dz; with_pe: the call writes PE and the mask (rd_sensor_stage_fwd*; 0: rd_msgpass_fwd, rd_msgpass_bwd); with_coef:
  * a coefficient-dropout table is given.  Needs no device.  Bit i of *bits:

@@ -226,6 +226,8 @@ SIGNATURES = {
 # hooks of include/raindrop_hip_debug.h that tests call through this binding (not part of the ABI)
 DEBUG_SIGNATURES = {
     "rd_debug_encoder_route": (c_int32, [_SHP, c_int32, _P]),       # bits: ROUTE_BITS below
+    # shape, pass (ATTN_PASSES), with_plan, aligned, words[11] (words[0]: ATTN_FAMILIES / ATTN_ROUTE_BITS below), names joined by ',', cap
+    "rd_debug_attention_route": (c_int32, [_SHP, c_int32, c_int32, c_int32, _P, _P, c_size_t]),
     "rd_debug_sensor_route": (c_int32, [_SHP, c_int32, c_int32, c_int32, _P]),      # ldz, with_pe, with_coef; bits: SENSOR_ROUTE_BITS below
     "rd_debug_graph_beta_route": (c_int32, [c_int32] * 6 + [_P]),   # B, N, T, E, with_alpha, with_drop; bits: BETA_ROUTE_BITS below
     # M, N, K, sa_m, sa_k, sb_n, sb_k, nsplit, k_per_split, tile_hint, flags (GEMM_ROUTE_FLAGS), words[5], name, cap
@@ -239,6 +241,10 @@ DEBUG_SIGNATURES = {
 # bit i of rd_debug_encoder_route's mask (csrc/rd_temporal.hip EncRoute, in declaration order)
 ROUTE_BITS = ("rg", "dx_rowblock", "tw", "panel", "tw2", "big", "lnf1", "lnf2", "lnb", "chain_fwd", "chain_bwd", "attn_tiles",
               "afuse_fwd", "afuse_bwd", "lean", "infer", "plan_ok")
+# rd_debug_attention_route (csrc/rd_attention.hip AttnRoute): its pass argument; bits 0-1 of words[0]; the flags from bit 2 on
+ATTN_PASSES = ("fwd", "bwd")
+ATTN_FAMILIES = ("fp32", "one_b16", "mt_b16", "big")
+ATTN_ROUTE_BITS = ("vec", "one_product", "wide")
 # bit i of rd_debug_sensor_route's mask (csrc/rd_k1_route.h K1Route's flags, in declaration order); bits 8-9: the row-tile count rt
 SENSOR_ROUTE_BITS = ("fused", "specialised", "infer", "coef", "tiles", "wgrad_stream")
 # bit i of rd_debug_graph_beta_route's mask (csrc/rd_graph_beta.hip BetaFwdRoute / BetaBwdRoute); bits 8-23: the backward's chunk Tc

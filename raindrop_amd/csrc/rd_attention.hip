@@ -2,10 +2,12 @@
 // attention forward / backward between in_proj and out_proj.  Exact-fp32 tiled kernels (v_mfma_f32_16x16x4_f32) and their split-
 // bf16 forms, flash-style: sequence tiles are 64 steps; a P19 sample (T=60) is a single tile, P12 (215) / PAM (600) loop over key
 // tiles with an online softmax, so the [T,T] score matrix only ever exists in LDS; the materialised-score path of wide heads;
-// dispatch_attn (rd_encoder.h), which the layer launches, and the stand-alone rd_attention_fwd / rd_attention_bwd.
+// the route of a pass (attn_route: family, instantiation and launch geometry, decided once) behind attn_forward / attn_backward
+// (rd_encoder.h), which the layer calls, and the stand-alone rd_attention_fwd / rd_attention_bwd.
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rd_encoder.h"
 #include "rd_plan.h"
@@ -98,7 +100,7 @@ template <int NTH>
 struct HeadRegs { float4 v[NTH]; unsigned ok; };     // ok: bit 4*i+j = component j of chunk i is inside the tile
 
 // VEC: 16-byte loads (head_dim % 4 == 0, row strides % 4 == 0, 16-byte aligned bases -- decided once per kernel
-// by the host, attn_vec_ok, and compiled in as the kernels' VEC flag); otherwise four 4-byte loads per chunk.  Every load is UNCONDITIONAL
+// by the host, AttnRoute::vec, and compiled in as the kernels' VEC flag); otherwise four 4-byte loads per chunk.  Every load is UNCONDITIONAL
 // from a clamped (always legal) address and the zero padding is applied later by head_mask: a conditional
 // load is a phi of {0, loaded value}, which makes the compiler shuffle registers -- and therefore wait --
 // right behind the request.
@@ -162,6 +164,10 @@ __device__ __forceinline__ float head_rowdot(const HeadRegs<NTH>& a, const HeadR
 // ------------------------------------------------------------------------------------------------
 // forward: grid (q tiles, B*H).  Wave w owns query rows 16w..16w+15 of the tile.
 // ------------------------------------------------------------------------------------------------
+// dynamic LDS: Q, K, V [64][LDH] and P [64][LDP] -- no P where it overlays Q (one_tile below); the attribute takes the size with P
+constexpr size_t attn_fwd_lds(int nth, int T) {
+  return sizeof(float) * (3 * TS * (16 * nth + 4) + (T <= TS && 16 * nth + 4 >= LDP ? 0 : TS * LDP));
+}
 template <int NTH, bool VEC>
 __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -281,6 +287,9 @@ __global__ __launch_bounds__(256) void k_attn_fwd(AttnArgs a) {
 // ------------------------------------------------------------------------------------------------
 // backward, dQ: grid (q tiles, B*H); also writes delta = rowsum(dout * out).
 // ------------------------------------------------------------------------------------------------
+// dynamic LDS of the three backward kernels: Q, dO, K, V [64][LDH], lse and delta of the tile's rows, and np score tiles [64][LDP] --
+// P here, (P o M)^T and dS^T in k_attn_bwd_dkv, P o M and dS in k_attn_bwd_one
+constexpr size_t attn_bwd_lds(int nth, int np) { return sizeof(float) * (4 * TS * (16 * nth + 4) + np * TS * LDP + 2 * TS); }
 template <int NTH, bool VEC>
 __global__ __launch_bounds__(256) void k_attn_bwd_dq(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -690,6 +699,16 @@ __device__ __forceinline__ void store_t4(__bf16* Ph, __bf16* Pl, int key, int q4
   *reinterpret_cast<abf4*>(Pl + key * LDT + q4) = lo;
 }
 
+// row stride (bf16) of the hi / lo head planes of every split-bf16 kernel below
+constexpr int attn_ldb(int nth) { return 32 * ((16 * nth + 31) / 32) + 16; }
+// dynamic LDS of the single-tile kernels, four-wave and eight-wave form.  Forward: Q, K, V hi / lo [64][LDB], P^T hi / lo [64][LDT]
+// unless it overlays Q, and the eight-wave form's partial row maxima and sums; backward: Q, K, V, dO planes, (P o M)^T and dS^T
+// planes, lse and delta
+constexpr size_t attn_fwd_one_b16_lds(int nth, bool wide) {
+  const int LDB = attn_ldb(nth);
+  return (size_t)(6 * TS * LDB + (LDB >= LDT ? 0 : 2 * TS * LDT)) * sizeof(__bf16) + (wide ? 4 * TS * sizeof(float) : 0);
+}
+constexpr size_t attn_bwd_one_b16_lds(int nth) { return (size_t)(8 * TS * attn_ldb(nth) + 4 * TS * LDT) * sizeof(__bf16) + 2 * TS * sizeof(float); }
 template <int NTH, bool VEC>
 __global__ __launch_bounds__(256) void k_attn_fwd_one_b16(AttnArgs a, int one) {
   extern __shared__ __attribute__((aligned(16))) unsigned char bsm[];
@@ -1173,6 +1192,10 @@ __global__ __launch_bounds__(512) void k_attn_bwd_one_b16w(AttnArgs a, int one) 
 // ------------------------------------------------------------------------------------------------
 constexpr int QW = 8;                   // waves per workgroup: 16-row blocks of the owned dimension
 constexpr int QROWS = 16 * QW;
+// dynamic LDS: the streamed tile's four planes [64][LDB] and the tile's key-mask bytes (forward, dQ) or its lse and delta (dK / dV)
+constexpr size_t attn_mt_lds(int nth, bool dkv) {
+  return (size_t)4 * TS * attn_ldb(nth) * sizeof(__bf16) + (dkv ? 2 * TS * sizeof(float) : TS);
+}
 
 // bit i: key tile i of sample b holds at least one live key (tiles >= 64 are never skipped)
 __device__ __forceinline__ uint64_t live_key_tiles(const uint8_t* __restrict__ mrow, int T, int lane) {
@@ -1638,111 +1661,121 @@ __global__ __launch_bounds__(64 * QW) void k_attn_bwd_dkv_b16(AttnArgs a) {
   }
 }
 
-// 16-byte head-tile loads are legal: every row of every head starts on a 16-byte boundary.  Decided HERE and compiled into the
-// kernel (template flag): as a runtime flag the compiler merged the two load forms into four 4-byte loads per chunk -- 4x the
-// vector-memory instructions of every attention kernel.
-static bool attn_vec_ok(const AttnArgs& a) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  return (a.hd & 3) == 0 && (a.D & 3) == 0 && al(a.qkv) && al(a.out) && al(a.dout);
-}
-#define ATTN_LAUNCH(K, grid, block, lds_attr, lds, ...)                                                  \
-  do {                                                                                                   \
-    if (vec) {                                                                                           \
-      RD_LDS_ATTR((K<NTH, true>), lds_attr);                                                             \
-      hipLaunchKernelGGL((K<NTH, true>), grid, block, lds, st, __VA_ARGS__);                             \
-    } else {                                                                                             \
-      RD_LDS_ATTR((K<NTH, false>), lds_attr);                                                            \
-      hipLaunchKernelGGL((K<NTH, false>), grid, block, lds, st, __VA_ARGS__);                            \
-    }                                                                                                    \
-  } while (0)
+// ---- the route of an attention pass ----------------------------------------------------------------------------------------------
+// Which kernels one forward or backward of the core runs, in the current arithmetic mode and switches, and the geometry of each
+// launch.  Decided HERE and nowhere else, once per pass; no HIP call, so rd_debug_attention_route (include/raindrop_hip_debug.h)
+// answers without a device from the very functions the launch runs.  aligned: qkv, out and dout all start on 16-byte boundaries.
+enum AttnPass { ATTN_FWD = 0, ATTN_BWD = 1, ATTN_IS_BIG = 2 };      // ATTN_IS_BIG: `family == ATTN_BIG` or not alone (attn_big: the size queries)
+enum AttnFamily { ATTN_FP32 = 0, ATTN_ONE_B16 = 1, ATTN_MT_B16 = 2, ATTN_BIG = 3 };   // exact fp32 tiled | single-tile, multi-tile split-bf16 | materialised scores
+enum AttnKernel { AK_FWD, AK_BWD_DQ, AK_BWD_DKV, AK_BWD_ONE, AK_FWD_ONE_B16, AK_FWD_ONE_B16W, AK_BWD_ONE_B16, AK_BWD_ONE_B16W,
+                  AK_FWD_B16, AK_BWD_DQ_B16, AK_BWD_DKV_B16 };      // attn_route: an eight-wave kernel is its four-wave form + 1
+struct AttnLaunch {
+  int kernel; dim3 grid; int block;      // kernel: AttnKernel
+  size_t lds_attr, lds;                  // dynamic LDS bytes: the kernel's opt-in (its largest launch) and this launch's
+  const char* name;                      // what the launch reports to the error check and the launch log
+};
+struct AttnRoute {
+  int family;            // AttnFamily
+  int nth;               // 16-column tiles of a head, ceil(head_dim / 16): 1..6
+  bool vec;              // 16-byte head-tile loads: every row of every head starts on a 16-byte boundary.  Compiled into the kernels
+                         // (template flag): as a runtime flag the compiler merged the two load forms into four 4-byte loads per chunk
+  bool one_product;      // split-bf16 families in RD_PREC_BF16: hi*hi only
+  bool wide;             // ATTN_ONE_B16: the eight-wave kernels
+  int nlaunch;           // 0: ATTN_BIG (attn_big_fwd / attn_big_bwd run it); 2: a backward over several key tiles, dq (+ delta) then dk / dv
+  AttnLaunch l[2];
+};
 
-static bool attn_b16_mt_ok(const AttnArgs& a) {
-  const char* e = getenv("RD_ATTN_B16_MT");           // read per call (tests compare both paths in one process)
-  return !(e && atoi(e) == 0) && precision() != RD_PREC_FP32 && a.T > TS && a.hd <= 96;
-}
-#define ATTN_LAUNCH_MT(K, grid, lds, arg)                                                                \
-  do {                                                                                                   \
-    if (vec && one) { RD_LDS_ATTR((K<NTH, true, true>), lds); hipLaunchKernelGGL((K<NTH, true, true>), grid, dim3(64 * QW), lds, st, arg); }          \
-    else if (vec) { RD_LDS_ATTR((K<NTH, true, false>), lds); hipLaunchKernelGGL((K<NTH, true, false>), grid, dim3(64 * QW), lds, st, arg); }         \
-    else if (one) { RD_LDS_ATTR((K<NTH, false, true>), lds); hipLaunchKernelGGL((K<NTH, false, true>), grid, dim3(64 * QW), lds, st, arg); }         \
-    else { RD_LDS_ATTR((K<NTH, false, false>), lds); hipLaunchKernelGGL((K<NTH, false, false>), grid, dim3(64 * QW), lds, st, arg); }               \
-  } while (0)
-template <int NTH>
-int launch_attn_b16_mt(const AttnArgs& a, int which, hipStream_t st) {
-  const bool vec = attn_vec_ok(a);
-  constexpr int HDP = 32 * ((16 * NTH + 31) / 32), LDB = HDP + 16;
-  const bool one = precision() == RD_PREC_BF16;
-  const dim3 grid(cdiv(a.T, QROWS), a.B * a.H);
-  const size_t planes = (size_t)4 * TS * LDB * sizeof(__bf16);
-  if (which == 0) {
-    ATTN_LAUNCH_MT(k_attn_fwd_b16, grid, planes + TS, a);
-    return check_launch("k_attn_fwd_b16");
-  }
-  if (which == 1) {
-    ATTN_LAUNCH_MT(k_attn_bwd_dq_b16, grid, planes + TS, a);
-    return check_launch("k_attn_bwd_dq_b16");
-  }
-  ATTN_LAUNCH_MT(k_attn_bwd_dkv_b16, grid, planes + 2 * TS * sizeof(float), a);
-  return check_launch("k_attn_bwd_dkv_b16");
+// Whole literals, by AttnKernel: the launch log keeps the pointer, and the tests match on these names.  attn_route names each launch
+// as it adds it: this is the name of the route's last one ("" before the first).
+static const char* attn_name(const AttnRoute& r) {
+  static const char* const names[11] = {"k_attn_fwd", "k_attn_bwd_dq", "k_attn_bwd_dkv", "k_attn_bwd_one", "k_attn_fwd_one_b16", "k_attn_fwd_one_b16w",
+                                        "k_attn_bwd_one_b16", "k_attn_bwd_one_b16w", "k_attn_fwd_b16", "k_attn_bwd_dq_b16", "k_attn_bwd_dkv_b16"};
+  return r.nlaunch > 0 ? names[r.l[r.nlaunch - 1].kernel] : "";
 }
 
-static bool attn_b16_ok(const AttnArgs& a) {
-  const char* e = getenv("RD_ATTN_B16");              // read per call (tests compare both paths in one process)
-  return !(e && atoi(e) == 0) && precision() != RD_PREC_FP32 && a.T <= TS && a.hd <= 96;
+static AttnRoute attn_route(AttnPass pass, int T, int B, int D, int H, int hd, bool with_plan, bool aligned) {
+  // read once per process
+  static const bool fwd_w8 = [] { const char* e = getenv("RD_ATTN_FWD_W8"); return !(e && atoi(e) == 0); }();
+  static const bool bwd_w8 = [] { const char* e = getenv("RD_ATTN_BWD_W8"); return !(e && atoi(e) == 0); }();
+  // read per call (tests compare both paths in one process; the saved / workspace sizes follow RD_ATTN_BIG)
+  auto on = [](const char* name, bool dflt) { const char* e = getenv(name); return e ? atoi(e) != 0 : dflt; };
+  AttnRoute r{};
+  if (hd > ATTN_MAX_HD || on("RD_ATTN_BIG", false)) r.family = ATTN_BIG;
+  if (r.family == ATTN_BIG || pass == ATTN_IS_BIG) return r;
+  const bool fwd = pass == ATTN_FWD, b16 = precision() != RD_PREC_FP32;
+  r.nth = cdiv(hd, 16);
+  r.vec = (hd & 3) == 0 && (D & 3) == 0 && aligned;
+  auto add = [&](int kernel, dim3 grid, int block, size_t lds) {
+    r.l[r.nlaunch++] = AttnLaunch{kernel, grid, block, lds, lds, nullptr};
+    r.l[r.nlaunch - 1].name = attn_name(r);
+  };
+  if (b16 && T <= TS && on("RD_ATTN_B16", true)) {                // one workgroup per (sample, head)
+    r.family = ATTN_ONE_B16;
+    r.wide = (fwd ? fwd_w8 : bwd_w8) || with_plan;                // of the two forms only the eight-wave one reads a plan
+    add((fwd ? AK_FWD_ONE_B16 : AK_BWD_ONE_B16) + r.wide, dim3(B * H), r.wide ? 512 : 256,
+        fwd ? attn_fwd_one_b16_lds(r.nth, r.wide) : attn_bwd_one_b16_lds(r.nth));
+  } else if (b16 && T > TS && on("RD_ATTN_B16_MT", true)) {       // a workgroup owns 128 queries (dk / dv: keys)
+    r.family = ATTN_MT_B16;
+    const dim3 grid(cdiv(T, QROWS), B * H);
+    add(fwd ? AK_FWD_B16 : AK_BWD_DQ_B16, grid, 64 * QW, attn_mt_lds(r.nth, false));
+    if (!fwd) add(AK_BWD_DKV_B16, grid, 64 * QW, attn_mt_lds(r.nth, true));
+  } else {
+    r.family = ATTN_FP32;
+    const dim3 grid(cdiv(T, TS), B * H);
+    if (fwd) { add(AK_FWD, grid, 256, attn_fwd_lds(r.nth, TS + 1)); r.l[0].lds = attn_fwd_lds(r.nth, T); }     // less where P overlays Q
+    else if (T <= TS) add(AK_BWD_ONE, dim3(B * H), 256, attn_bwd_lds(r.nth, 2));      // single tile: S, P, dP, dS formed once
+    else { add(AK_BWD_DQ, grid, 256, attn_bwd_lds(r.nth, 1)); add(AK_BWD_DKV, grid, 256, attn_bwd_lds(r.nth, 2)); }
+  }
+  r.one_product = r.family != ATTN_FP32 && precision() == RD_PREC_BF16;
+  return r;
 }
-template <int NTH>
-int launch_attn_b16(const AttnArgs& a_in, int which, hipStream_t st) {
-  const bool vec = attn_vec_ok(a_in);
-  constexpr int HDP = 32 * ((16 * NTH + 31) / 32), LDB = HDP + 16;
-  const int one = precision() == RD_PREC_BF16;
-  AttnArgs a = a_in;
-  a.stamps = g_attn_stamps;
-  if (which == 0) {
-    const size_t lds = (size_t)(6 * TS * LDB + (LDB >= LDT ? 0 : 2 * TS * LDT)) * sizeof(__bf16);
-    static const bool widef = [] { const char* e = getenv("RD_ATTN_FWD_W8"); return !(e && atoi(e) == 0); }();
-    if (widef || a.plan) {
-      const size_t ldsw = lds + 4 * TS * sizeof(float);
-      ATTN_LAUNCH(k_attn_fwd_one_b16w, dim3(a.B * a.H), dim3(512), ldsw, ldsw, a, one);
-      return check_launch("k_attn_fwd_one_b16w");
+
+// what a pass refuses: the calls that reach it have taken the materialised form elsewhere (the layer) or refused it (rd_attention_*)
+static int attn_check(const AttnRoute& r, int hd, bool with_plan) {
+  if (with_plan && r.family != ATTN_ONE_B16 && r.family != ATTN_MT_B16)
+    return fail(RD_EUNSUPPORTED, "token plan: only the split-bf16 attention kernels (head_dim <= 96, bf16 modes) read it");
+  if (r.family != ATTN_BIG) return RD_OK;
+  return hd > ATTN_MAX_HD ? fail(RD_EUNSUPPORTED, "attention head_dim %d > 96 not built", hd)
+                          : fail(RD_EUNSUPPORTED, "attention: RD_ATTN_BIG takes the materialised scores, which only the layer runs");
+}
+
+// ---- one launcher: (kernel, nth, vec, one_product) -> the instantiation ----------------------------------------------------------
+template <auto KERNEL, class... One>
+static int attn_run(const AttnLaunch& l, const AttnArgs& a, hipStream_t st, One... one) {
+  // dynamic-LDS opt-in, once per process and kernel (RD_LDS_ATTR, under the route's name): lds_attr depends on the instantiation only
+  static const hipError_t attr = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l.lds_attr);
+  if (attr != hipSuccess) return fail((int)attr, "hipFuncSetAttribute(%s): %s", l.name, hipGetErrorString(attr));
+  hipLaunchKernelGGL(KERNEL, l.grid, dim3(l.block), l.lds, st, a, one...);
+  return check_launch(l.name);
+}
+// f(NTH, VEC) with the head's tile count (1..6) and the load form as compile-time constants
+template <int NTH = 1, class F>
+static int by_head(const AttnRoute& r, F&& f) {
+  if constexpr (NTH < 6)
+    if (r.nth > NTH) return by_head<NTH + 1>(r, f);
+  return r.vec ? f(std::integral_constant<int, NTH>{}, std::true_type{}) : f(std::integral_constant<int, NTH>{}, std::false_type{});
+}
+// launch i of the route.  The single-tile split-bf16 kernels take one_product as an argument, the multi-tile ones as a template flag
+static int attn_launch(AttnArgs a, const AttnRoute& r, int i, hipStream_t st) {
+  const AttnLaunch& l = r.l[i];
+  a.stamps = g_attn_stamps;                      // k_attn_*_one_b16 alone write stamps
+  const int one = r.one_product;
+  return by_head(r, [&](auto nth, auto vec) {
+    constexpr int N = decltype(nth)::value; constexpr bool V = decltype(vec)::value;
+    switch (l.kernel) {
+      case AK_FWD: return attn_run<k_attn_fwd<N, V>>(l, a, st);
+      case AK_BWD_DQ: return attn_run<k_attn_bwd_dq<N, V>>(l, a, st);
+      case AK_BWD_DKV: return attn_run<k_attn_bwd_dkv<N, V>>(l, a, st);
+      case AK_BWD_ONE: return attn_run<k_attn_bwd_one<N, V>>(l, a, st);
+      case AK_FWD_ONE_B16: return attn_run<k_attn_fwd_one_b16<N, V>>(l, a, st, one);
+      case AK_FWD_ONE_B16W: return attn_run<k_attn_fwd_one_b16w<N, V>>(l, a, st, one);
+      case AK_BWD_ONE_B16: return attn_run<k_attn_bwd_one_b16<N, V>>(l, a, st, one);
+      case AK_BWD_ONE_B16W: return attn_run<k_attn_bwd_one_b16w<N, V>>(l, a, st, one);
+      case AK_FWD_B16: return one ? attn_run<k_attn_fwd_b16<N, V, true>>(l, a, st) : attn_run<k_attn_fwd_b16<N, V, false>>(l, a, st);
+      case AK_BWD_DQ_B16: return one ? attn_run<k_attn_bwd_dq_b16<N, V, true>>(l, a, st) : attn_run<k_attn_bwd_dq_b16<N, V, false>>(l, a, st);
+      default: return one ? attn_run<k_attn_bwd_dkv_b16<N, V, true>>(l, a, st) : attn_run<k_attn_bwd_dkv_b16<N, V, false>>(l, a, st);
     }
-    ATTN_LAUNCH(k_attn_fwd_one_b16, dim3(a.B * a.H), dim3(256), lds, lds, a, one);
-    return check_launch("k_attn_fwd_one_b16");
-  }
-  const size_t lds = (size_t)(8 * TS * LDB + 4 * TS * LDT) * sizeof(__bf16) + 2 * TS * sizeof(float);
-  static const bool wide = [] { const char* e = getenv("RD_ATTN_BWD_W8"); return !(e && atoi(e) == 0); }();
-  if (wide || a.plan) {
-    ATTN_LAUNCH(k_attn_bwd_one_b16w, dim3(a.B * a.H), dim3(512), lds, lds, a, one);
-    return check_launch("k_attn_bwd_one_b16w");
-  }
-  ATTN_LAUNCH(k_attn_bwd_one_b16, dim3(a.B * a.H), dim3(256), lds, lds, a, one);
-  return check_launch("k_attn_bwd_one_b16");
-}
-
-template <int NTH>
-int launch_attn(const AttnArgs& a, int which, hipStream_t st) {
-  const bool vec = attn_vec_ok(a);
-  constexpr int LDH = 16 * NTH + 4;
-  dim3 grid(cdiv(a.T, TS), a.B * a.H);
-  size_t lds;
-  if (which == 0) {
-    lds = sizeof(float) * (3 * TS * LDH + TS * LDP);
-    const size_t lds_attr = lds;
-    if (a.T <= TS && LDH >= LDP) lds = sizeof(float) * (3 * TS * LDH);   // P overlays Q
-    ATTN_LAUNCH(k_attn_fwd, grid, dim3(256), lds_attr, lds, a);
-    return check_launch("k_attn_fwd");
-  } else if (which == 1) {
-    lds = sizeof(float) * (4 * TS * LDH + TS * LDP + 2 * TS);
-    ATTN_LAUNCH(k_attn_bwd_dq, grid, dim3(256), lds, lds, a);
-    return check_launch("k_attn_bwd_dq");
-  }
-  if (which == 3) {
-    lds = sizeof(float) * (4 * TS * LDH + 2 * TS * LDP + 2 * TS);
-    ATTN_LAUNCH(k_attn_bwd_one, dim3(a.B * a.H), dim3(256), lds, lds, a);
-    return check_launch("k_attn_bwd_one");
-  }
-  lds = sizeof(float) * (4 * TS * LDH + 2 * TS * LDP + 2 * TS);
-  ATTN_LAUNCH(k_attn_bwd_dkv, grid, dim3(256), lds, lds, a);
-  return check_launch("k_attn_bwd_dkv");
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1855,39 +1888,16 @@ int attn_big_bwd(const AttnArgs& a, const float* P, const float* PD, float* dS, 
   return launch_gemm(g, st);
 }
 
-int dispatch_attn(const AttnArgs& a, int which, hipStream_t st) {
-  if (a.plan && !(((which == 0 || which == 3) && attn_b16_ok(a)) || (which <= 2 && attn_b16_mt_ok(a))))
-    return fail(RD_EUNSUPPORTED, "token plan: only the split-bf16 attention kernels (head_dim <= 96, bf16 modes) read it");
-  if ((which == 0 || which == 3) && attn_b16_ok(a)) {
-    switch (cdiv(a.hd, 16)) {
-      case 1: return launch_attn_b16<1>(a, which, st);
-      case 2: return launch_attn_b16<2>(a, which, st);
-      case 3: return launch_attn_b16<3>(a, which, st);
-      case 4: return launch_attn_b16<4>(a, which, st);
-      case 5: return launch_attn_b16<5>(a, which, st);
-      default: return launch_attn_b16<6>(a, which, st);
-    }
-  }
-  if (which <= 2 && attn_b16_mt_ok(a)) {
-    switch (cdiv(a.hd, 16)) {
-      case 1: return launch_attn_b16_mt<1>(a, which, st);
-      case 2: return launch_attn_b16_mt<2>(a, which, st);
-      case 3: return launch_attn_b16_mt<3>(a, which, st);
-      case 4: return launch_attn_b16_mt<4>(a, which, st);
-      case 5: return launch_attn_b16_mt<5>(a, which, st);
-      default: return launch_attn_b16_mt<6>(a, which, st);
-    }
-  }
-  switch (cdiv(a.hd, 16)) {
-    case 1: return launch_attn<1>(a, which, st);
-    case 2: return launch_attn<2>(a, which, st);
-    case 3: return launch_attn<3>(a, which, st);
-    case 4: return launch_attn<4>(a, which, st);
-    case 5: return launch_attn<5>(a, which, st);
-    case 6: return launch_attn<6>(a, which, st);
-    default: return fail(RD_EUNSUPPORTED, "attention head_dim %d > 96 not built", a.hd);
-  }
+static int attn_pass(AttnPass pass, const AttnArgs& a, hipStream_t st) {
+  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const AttnRoute r = attn_route(pass, a.T, a.B, a.D, a.H, a.hd, a.plan != nullptr, al(a.qkv) && al(a.out) && al(a.dout));
+  int rc = attn_check(r, a.hd, a.plan != nullptr);
+  for (int i = 0; i < r.nlaunch && !rc; ++i) rc = attn_launch(a, r, i, st);
+  return rc;
 }
+int attn_forward(const AttnArgs& a, hipStream_t st) { return attn_pass(ATTN_FWD, a, st); }
+int attn_backward(const AttnArgs& a, hipStream_t st) { return attn_pass(ATTN_BWD, a, st); }
+bool attn_big(const EncDims& e) { return attn_route(ATTN_IS_BIG, e.T, e.B, e.D, e.H, e.Hd, false, true).family == ATTN_BIG; }
 }  // namespace rd
 
 using namespace rd;
@@ -1907,7 +1917,7 @@ extern "C" int rd_attention_fwd(const rd_shape* s, int32_t layer, const float* q
   RD_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "p_drop must be in [0,1)");
   const EncDims e = enc_dims(s);
   RD_REQUIRE(!attn_big(e), "rd_attention_fwd: head_dim %d > 96 runs as materialised products inside the layer only", e.Hd);
-  return dispatch_attn(attn_args(e, qkv, mask, out, lse, p_drop, seed, (uint32_t)layer, token_plan()), 0, (hipStream_t)stream);
+  return attn_forward(attn_args(e, qkv, mask, out, lse, p_drop, seed, (uint32_t)layer, token_plan()), (hipStream_t)stream);
 }
 // delta_ws: [B,H,T] floats of scratch
 extern "C" int rd_attention_bwd(const rd_shape* s, int32_t layer, const float* qkv, const uint8_t* mask, float p_drop, uint64_t seed,
@@ -1921,8 +1931,25 @@ extern "C" int rd_attention_bwd(const rd_shape* s, int32_t layer, const float* q
   RD_REQUIRE(!attn_big(e), "rd_attention_bwd: head_dim %d > 96 runs as materialised products inside the layer only", e.Hd);
   AttnArgs a = attn_args(e, qkv, mask, const_cast<float*>(out), const_cast<float*>(lse), p_drop, seed, (uint32_t)layer, token_plan());
   a.dout = dout; a.dqkv = dqkv; a.delta = delta_ws;
-  hipStream_t st = (hipStream_t)stream;
-  if (e.T <= TS) return dispatch_attn(a, 3, st);
-  if ((rc = dispatch_attn(a, 1, st))) return rc;
-  return dispatch_attn(a, 2, st);
+  return attn_backward(a, (hipStream_t)stream);
+}
+
+// not part of the ABI (include/raindrop_hip_debug.h): the route of one pass over this shape, from the pass's own functions
+extern "C" int rd_debug_attention_route(const rd_shape* s, int32_t pass, int32_t with_plan, int32_t aligned, uint32_t* words, char* name,
+                                        size_t cap) {
+  int rc = check_enc(s);
+  if (rc) return rc;
+  RD_REQUIRE(words && name && cap > 0, "NULL tensor");
+  RD_REQUIRE(pass == ATTN_FWD || pass == ATTN_BWD, "pass: 0 forward, 1 backward");
+  const EncDims e = enc_dims(s);
+  const AttnRoute r = attn_route((AttnPass)pass, e.T, e.B, e.D, e.H, e.Hd, with_plan != 0, aligned != 0);
+  words[0] = (uint32_t)r.family | (uint32_t)r.vec << 2 | (uint32_t)r.one_product << 3 | (uint32_t)r.wide << 4 | (uint32_t)r.nth << 8 |
+             (uint32_t)r.nlaunch << 12;
+  for (int i = 0; i < 2; ++i) {
+    const AttnLaunch l = i < r.nlaunch ? r.l[i] : AttnLaunch{0, dim3(0, 0), 0, 0, 0, ""};
+    const uint32_t w[5] = {l.grid.x, l.grid.y, (uint32_t)l.block, (uint32_t)l.lds_attr, (uint32_t)l.lds};
+    std::copy(w, w + 5, words + 1 + 5 * i);
+  }
+  snprintf(name, cap, "%s%s%s", r.nlaunch > 0 ? r.l[0].name : "", r.nlaunch > 1 ? "," : "", r.nlaunch > 1 ? r.l[1].name : "");
+  return attn_check(r, e.Hd, with_plan != 0);
 }

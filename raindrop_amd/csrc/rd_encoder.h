@@ -66,11 +66,12 @@ int launch_rowgemm(long M, int N, int K, const float* A, long lda, const void* W
 struct EncDims { long M; int D, Hd, nhid, H, T, B; };
 EncDims enc_dims(const rd_shape* s);
 int check_enc(const rd_shape* s);
-// wide heads take the materialised-score attention; RD_ATTN_BIG=1 forces it for every shape
-bool attn_big(const EncDims& e);
 
 // ---- attention core (rd_attention.hip) ---------------------------------------------------------------------------------------
 constexpr int TS = 64;          // sequence tile (queries and keys)
+constexpr int ATTN_MAX_HD = 96; // widest head of the tiled kernels (six 16-column tiles); wider heads take the materialised scores
+// the attention route's family is the materialised one: wide heads, or RD_ATTN_BIG=1 (read per call: saved / workspace sizes follow it)
+bool attn_big(const EncDims& e);
 
 struct AttnArgs {
   const float* qkv;      // [T,B,3D]
@@ -83,7 +84,7 @@ struct AttnArgs {
   int T, B, D, H, hd;
   float scale, p_drop; uint64_t seed; uint32_t site; const uint64_t* seed_cell;
   unsigned long long* stamps;   // debug only (tools/attn_timing.py)
-  const int32_t* plan;          // token plan (rd_plan.h) or null; honoured by the single-tile split-bf16 kernels (k_attn_*_one_b16w)
+  const int32_t* plan;          // token plan (rd_plan.h) or null; read by k_attn_*_one_b16w and k_attn_*_b16, refused on every other route
 };
 // the forward's arguments of layer `layer`; a backward adds dout, dqkv and delta
 inline AttnArgs attn_args(const EncDims& e, const float* qkv, const uint8_t* mask, float* out, float* lse, float p_drop, uint64_t seed,
@@ -95,9 +96,10 @@ inline AttnArgs attn_args(const EncDims& e, const float* qkv, const uint8_t* mas
   a.plan = plan;
   return a;
 }
-// which: 0 forward, 1 dq (+ delta), 2 dk / dv, 3 the single-tile backward (T <= TS)
-int dispatch_attn(const AttnArgs& a, int which, hipStream_t st);
-// materialised scores (head_dim > 96).  P, PD: [B*H][T][T] each (saved); dS: [B*H][T][T] workspace
+// one pass of the tiled kernels: the launches of its route (the backward over several key tiles: dq + delta, then dk / dv)
+int attn_forward(const AttnArgs& a, hipStream_t st);
+int attn_backward(const AttnArgs& a, hipStream_t st);
+// materialised scores (attn_big).  P, PD: [B*H][T][T] each (saved); dS: [B*H][T][T] workspace
 int attn_big_fwd(const AttnArgs& a, float* P, float* PD, hipStream_t st);
 int attn_big_bwd(const AttnArgs& a, const float* P, const float* PD, float* dS, hipStream_t st);
 

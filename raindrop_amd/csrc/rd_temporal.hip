@@ -28,17 +28,9 @@ int check_enc(const rd_shape* s) {
              "bad rd_shape");
   const int D = s->F * s->d_ob + s->d_pe;
   RD_REQUIRE(D % s->nhead == 0, "D=%d not divisible by nhead=%d", D, s->nhead);
-  RD_REQUIRE((long)s->B * s->nhead * s->T * s->T < (1L << 31) || D / s->nhead <= 96, "score tensor exceeds 2^31 elements");
+  RD_REQUIRE((long)s->B * s->nhead * s->T * s->T < (1L << 31) || D / s->nhead <= ATTN_MAX_HD, "score tensor exceeds 2^31 elements");
   RD_REQUIRE((long)s->T * s->B * (3L * D > s->nhid ? 3L * D : s->nhid) < (1L << 31), "tensor exceeds 2^31 elements");
   return RD_OK;
-}
-
-// wide heads take the materialised-score attention; RD_ATTN_BIG=1 forces it for every shape (tests: it must agree with the
-// tiled kernels, masks included).  Read per call: saved / workspace sizes depend on it.
-bool attn_big(const EncDims& e) {
-  if (e.Hd > 96) return true;
-  const char* v = getenv("RD_ATTN_BIG");
-  return v && atoi(v) != 0;
 }
 
 namespace {
@@ -94,7 +86,7 @@ struct EncRoute {
   bool panel;        // tiled family on its panel form (bf16 modes): the forward splits the eight weight orientations into `saved`
   bool tw2;          // [bwd] panel, and the same stream fed by ONE conversion pass over the eight operands (rd_tiles_export.hip), not four split-K
                      // GEMMs (SYN256: 11.2 -> 7.65 ms; narrow layers keep the GEMMs, PAM: 2.96 vs 3.04 ms).  RD_TILE_WGRAD_GENERIC=0: GEMMs
-  bool big;          // attention with materialised scores (attn_big)
+  bool big;          // attention with materialised scores (attn_big: the attention route's family)
   bool lnf1, lnf2;   // out_proj / linear2 carry the residual add + LayerNorm in their epilogue (a workgroup owns complete rows)
   bool lnb;          // the LayerNorm backward is the PROLOGUE of the input-gradient product that consumes its output
   bool chain_fwd;    // [fwd] out_proj + LayerNorm1 + linear1 + linear2 + LayerNorm2 as ONE launch (rd_encfuse.hip): the rows stay in LDS
@@ -405,7 +397,7 @@ static int layer_fwd(const rd_shape* s, int32_t layer, const float* x, const uin
   if (r.afuse_fwd)
     rc = launch_attn_fused_fwd(x, v.afw, w->in_proj_b, tp, e.T, e.B, e.D, e.H, e.Hd, p_drop, seed, SITE_ATTN_PROB + L, v.attn, v.lse, st);
   else if (r.big) rc = attn_big_fwd(a, v.pbig, v.pdbig, st);
-  else rc = dispatch_attn(a, 0, st);
+  else rc = attn_forward(a, st);
   if (rc) return rc;
   // ---- out_proj + LayerNorm1 + linear1 + linear2 + LayerNorm2 ------------------------------------------------------------------
   if (r.chain_fwd)
@@ -484,7 +476,7 @@ extern "C" int rd_encoder_layer_fwd_infer(const rd_shape* s, int32_t layer, cons
   } else {
     if ((rc = launch_rowgemm(e.M, 3 * e.D, e.D, x, e.D, v.pl[0][0], v.pl[0][1], v.qkv, 3 * e.D, w->in_proj_b, 0, nullptr, 0,
                              0.f, nullptr, 0, 0.f, 0, 0, st))) return rc;
-    if ((rc = dispatch_attn(attn_args(e, v.qkv, mask, v.attn, v.lse, 0.f, 0, L, tp), 0, st))) return rc;
+    if ((rc = attn_forward(attn_args(e, v.qkv, mask, v.attn, v.lse, 0.f, 0, L, tp), st))) return rc;
   }
   // ---- out_proj + LayerNorm1 + linear1 + linear2 + LayerNorm2: the save-free chain ---------------------------------------------
   return launch_enc_post_fwd(e.M, e.D, e.nhid, v.attn, x, v.pl[1][0], v.pl[2][0], v.pl[3][0], w->out_proj_b, w->lin1_b, w->lin2_b,
@@ -564,8 +556,7 @@ extern "C" int rd_encoder_layer_bwd(const rd_shape* s, int32_t layer, const floa
     rc = launch_attn_fused_bwd(x, v.afw, v.abw, w->in_proj_b, tp, e.T, e.B, e.D, e.H, e.Hd, p_drop, seed, SITE_ATTN_PROB + L, v.attn, v.lse,
                                ws.da, ws.ds1, dx, v.xt[0], ws.dt[3], st);
   else if (r.big) rc = attn_big_bwd(a, v.pbig, v.pdbig, ws.dsbig, st);
-  else if (e.T <= TS) rc = dispatch_attn(a, 3, st);         // single tile: S, P, dP, dS formed once
-  else if (!(rc = dispatch_attn(a, 1, st))) rc = dispatch_attn(a, 2, st);
+  else rc = attn_backward(a, st);
   if (rc) return rc;
   // ---- in_proj': dx = dqkv W_in + ds1 ----------------------------------------------------------------------------------------------
   if (wg_gemm && (rc = launch_wgrad(e.M, 3 * e.D, e.D, ws.dqkv, 3 * e.D, x, e.D, g->in_proj_w, g->in_proj_b, ws.splitk, st))) return rc;
