@@ -571,7 +571,7 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     validation split and that float on the test split.  `temperature` without `calibration` is refused.  None, None: the launches
     and the keys as without them."""
     from . import metrics
-    from .step import check_focal, criterion_values, focal_values
+    from .step import _spliced, check_focal, criterion_entry, criterion_values, focal_values
     check_bootstrap(bootstrap, bootstrap_seed, ci)
     check_calibration(calibration, temperature)
     if ds.y is None:
@@ -592,14 +592,9 @@ def validate(model, ds, transform="sigmoid", chunk=2048, group=None, save_free=T
     loss = torch.empty(1, dtype=torch.float32, device=ds.dev)
     dscores = torch.empty_like(scores)
     st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    if focal is not None:
-        focald = torch.tensor(focal, dtype=torch.float32, device=ds.dev)
-        _lib.call("rd_softmax_xent_focal", int(N), int(C), _p(scores), _p(ds.y), _p(focald), _p(loss), _p(dscores), st)
-    elif crit is not None:
-        critd = torch.tensor(crit, dtype=torch.float32, device=ds.dev)
-        _lib.call("rd_softmax_xent_crit", int(N), int(C), _p(scores), _p(ds.y), _p(critd), _p(loss), _p(dscores), st)
-    else:
-        _lib.call("rd_softmax_xent", int(N), int(C), _p(scores), _p(ds.y), _p(loss), _p(dscores), st)
+    suffix, vals = criterion_entry(focal, crit)
+    buf = None if vals is None else torch.tensor(vals, dtype=torch.float32, device=ds.dev)
+    _lib.call("rd_softmax_xent" + suffix, int(N), int(C), _p(scores), _p(ds.y), *_spliced(buf), _p(loss), _p(dscores), st)
     binary = C == 2
     parts = [r["mean"], loss.double(), r["auroc_per_class"], r["auprc_per_class"], cm.reshape(-1).double()]
     if bootstrap is not None:                              # the (n_valid, mean, deviation, lower, upper) rows of the reported column

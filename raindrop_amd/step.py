@@ -27,10 +27,16 @@ How the host layer is laid out:
 * What differs between the default branch and `use_beta` sits in a sensor-stage object (`SensorStage` here, `BetaSensorStage` in
   raindrop_amd/step_beta.py): model validation, buffer sizes, extra buffers, the forward and the backward call, and whether
   rd_step_prepare's K1 weight tiles apply.
+* Which loss entry point a head runs -- plain, `_crit` (class weights / label smoothing) or `_focal` -- and the buffer it takes is
+  decided in `criterion_entry`; `Step._loss_entry` applies it to the step's `crit` / `focal` buffers, feed.validate to its own.
 * `capture_graphs` is the one place that warms up on a side stream, joins, synchronizes and captures.
 * `TrainStep` adds what training needs: the two-graph data-parallel form, the autotune of the row-block knobs, the measurement
   captures of bench.py, `capture_full` with the optimizer inside, and gradient accumulation (`accumulate=k`: every form captured
   twice, the window's accumulate / close launch behind the body).
+* `TrainStep._enqueue` is the one statement of a micro-batch's order: feed gather | per part of `_parts()` the body, the window's
+  launch and the caller's `after_part` | (capture_full: the optimizer) | feed record.  Every form is that method with other
+  arguments: the eager `run()`, the per-graph bodies of `_capture_one`, `capture_full`'s graphs, and `_warm`, the warm-up all
+  captures share.  `_collectives` is the gradient all-reduce as an `after_part`, for `run_allreduce` and `capture_full` alike.
 
 The captured graph is replayed per step; dropout masks change per replay through the device seed
 cell (`rd_set_seed_cell` / `rd_seed_cell_advance`), which the graph bumps itself.  The gradient
@@ -176,6 +182,18 @@ def focal_values(class_weight, focal_gamma, n_classes):
         raise ValueError("focal_gamma must be a finite number in [0, %g], got %r" % (FOCAL_GAMMA_MAX, focal_gamma))
     w = criterion_values(class_weight, 0.0, n_classes)
     return [gamma] + ([1.0] * int(n_classes) if w is None else w[1:])
+
+
+def criterion_entry(focal, crit):
+    """(suffix, buffer): which instantiation of a loss entry point runs (`rd_head_train` / `rd_softmax_xent` + suffix) and the buffer
+    it takes behind `y` -- the focal loss's, else the weighted / smoothed criterion's, else ("", None): the plain mean cross entropy,
+    whose entry points take no buffer.  The one place that makes this choice (the steps' heads, feed.validate)."""
+    return ("_focal", focal) if focal is not None else ("_crit", crit) if crit is not None else ("", None)
+
+
+def _spliced(buf):
+    """the argument a criterion buffer adds to a call: none without one"""
+    return () if buf is None else (_p(buf),)
 
 
 def check_focal(label_smoothing, focal_gamma):
@@ -335,12 +353,11 @@ class Step:
         label_smoothing must be 0): the step owns `focal` = [gamma, w_0 ..] instead of `crit` and its head runs the `_focal` entry
         points (rd_head_train_focal / rd_softmax_xent_focal) on it; `set_criterion(class_weight=, focal_gamma=)` changes both
         between replays.  The denominator and the data-parallel rule are the weighted criterion's.  None: as without it."""
-        self._crit_vals = criterion_values(class_weight, label_smoothing, model.n_classes)
+        crit, focal = criterion_values(class_weight, label_smoothing, model.n_classes), None
         check_focal(label_smoothing, focal_gamma)
-        self._focal_vals = None
         if focal_gamma is not None:
-            self._focal_vals, self._crit_vals = focal_values(class_weight, focal_gamma, model.n_classes), None
-        if (self._crit_vals is not None or self._focal_vals is not None) and not (has_backward and labels):
+            crit, focal = None, focal_values(class_weight, focal_gamma, model.n_classes)
+        if (crit is not None or focal is not None) and not (has_backward and labels):
             raise ValueError("class_weight / label_smoothing / focal_gamma belong to a step that evaluates the loss itself (a training step with labels)")
         self.model, self.flat, self.batch, self.sensor, self.has_backward = model, flat, batch, sensor, bool(has_backward)
         self.infer = bool(save_free) and not self.has_backward
@@ -362,7 +379,7 @@ class Step:
         self.ts = model.pos_encoder.timescales(self.dev)
         self.P = dict(model.named_parameters())
         self.G = dict(zip(flat.names, flat.views)) if has_backward else {}      # gradient slices in the flat buffer
-        self._alloc()
+        self._alloc(crit, focal)
         self.seed_cell = torch.zeros(1, dtype=torch.int64, device=self.dev) if has_backward else None
         # side branch for the trailing launches of the step (the weight-gradient reduces, the head's weight gradients: nothing in
         # the backward chain reads them).  MEASURED round 4, same box, 3 x 300 steps each: 0.554 ms/step with the branch against
@@ -400,8 +417,9 @@ class Step:
         m = self.model
         return plan_supported(m.d_inp, m.d_ob, self.T, self.D, m.nhead, m.nhid, self.lib.rd_get_precision())
 
-    def _alloc(self):
-        """Every buffer of the step, in the arena's order (the offsets are part of the measured step: _Arena)."""
+    def _alloc(self, crit=None, focal=None):
+        """Every buffer of the step, in the arena's order (the offsets are part of the measured step: _Arena).  crit / focal: the
+        contents of the criterion buffers (`criterion_values` / `focal_values`), None for a step without that buffer."""
         lib, sp, B, T, D, m, bwd = self.lib, self.sp, self.B, self.T, self.D, self.model, self.has_backward
         self.nl = len(m.transformer_encoder.layers)
         k1_bytes = self.sensor.buffer_bytes(self)
@@ -438,16 +456,10 @@ class Step:
         # Forward-only: the eager surface's head in both layouts (raindrop_amd/evalstep.py has the reason)
         self.head_fused = bwd and bool(lib.rd_head_train_supported(D, self.Fe, m.n_classes))
         self.head_ws = a.u8(lib.rd_head_train_workspace_bytes(B, dh, m.n_classes)) if self.head_fused else None
-        # the criterion [eps, w_0 .. w_{C-1}] of a step with class weights / label smoothing (None: the plain mean cross entropy)
-        self.crit = None
-        if getattr(self, "_crit_vals", None) is not None:
-            self.crit = a.zeros((m.n_classes + 1,))
-            self.crit.copy_(torch.tensor(self._crit_vals, dtype=torch.float32))
+        # the criterion [eps, w_0 .. w_{C-1}] of a step with class weights / label smoothing (None: the plain mean cross entropy),
         # the focal loss's [gamma, w_0 .. w_{C-1}] of a step built with focal_gamma (then crit is None: one criterion per step)
-        self.focal = None
-        if getattr(self, "_focal_vals", None) is not None:
-            self.focal = a.zeros((m.n_classes + 1,))
-            self.focal.copy_(torch.tensor(self._focal_vals, dtype=torch.float32))
+        filled = lambda vals: None if vals is None else a.zeros((len(vals),)).copy_(torch.tensor(vals, dtype=torch.float32))
+        self.crit, self.focal = filled(crit), filled(focal)
         tables = lambda T_: [_lib.RdEncoderPtrs(*[T_["transformer_encoder.layers.%d.%s" % (i, n)].data_ptr() for n in ops.ENC_PARAM_NAMES])
                              for i in range(self.nl)]
         self.enc_w, self.enc_g = tables(self.P), tables(self.G) if bwd else []
@@ -462,6 +474,10 @@ class Step:
         or the head, wrote): dx[0] for the top layer, alternating downwards; _grad_in(-1) is what the sensor stage reads."""
         return self.dx[(self.nl - 1 - i) % 2]
 
+    def _one_launch_begin(self):
+        """the `begin` stage is rd_step_begin (which also advances a registered optimizer step cell: TrainStep.capture_full)"""
+        return self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
+
     def _begin(self):
         """Token plan, seed bump and weight splits: one launch (rd_step_begin) where all three exist, else one each."""
         b, P, sp, st, c = self.batch, self.P, self.sp, ops._stream(), self._call
@@ -469,9 +485,9 @@ class Step:
         prep = self.prep_enc or self.prep_k1
         prep_args = (self.nl if self.prep_enc else 0, self._prep_w, self._prep_saved, self._prep_bytes,
                      _p(W1) if self.prep_k1 else None, _p(W2) if self.prep_k1 else None, _p(self.k1_saved), self.k1_saved.numel(), st)
-        drops = self.p_drop > 0.0 or getattr(self.sensor, "edge_drop", False)   # (either sensor stage's coefficient dropout)
+        drops = self.p_drop > 0.0 or self.sensor.edge_drop                 # (either sensor stage's coefficient dropout)
         cell = _p(self.seed_cell) if drops else None
-        if self.plan is not None and prep and self.one_begin:
+        if self._one_launch_begin():
             return c("rd_step_begin", sp, _p(b["lengths"]), _p(self.plan), cell, 1, *prep_args)
         if self.plan is not None:                                          # lengths -> token plan (+ the seed bump: one launch)
             c("rd_token_plan", sp, _p(b["lengths"]), _p(self.plan), cell, 1, st)
@@ -520,16 +536,17 @@ class Step:
                  _p(b["static"]) if Fe else None) + w(P),
                 (w(G) if G else ()) + (_p(self._grad_in(self.nl - 1)), _p(self.head_ws), self.head_ws.numel(), ops._stream()))
 
+    def _loss_entry(self):
+        """(entry-point suffix, device buffer) of the step's loss: `criterion_entry` of its two buffers"""
+        return criterion_entry(self.focal, self.crit)
+
     def _head_train(self):
         """Classifier head + mean cross entropy and their backward, down to the encoder stack's entry gradient."""
         if not self.head_fused:
             return self._head_by_operator()
         common, tail = self._fused_head_args()
-        if getattr(self, "focal", None) is not None:                       # the focal loss: the focal instantiation
-            return self._call("rd_head_train_focal", *common, _p(self.batch["y"]), _p(self.focal), _p(self.loss), _p(self.logits), *tail)
-        if self.crit is not None:                                          # class weights / label smoothing: the criterion instantiation
-            return self._call("rd_head_train_crit", *common, _p(self.batch["y"]), _p(self.crit), _p(self.loss), _p(self.logits), *tail)
-        self._call("rd_head_train", *common, _p(self.batch["y"]), _p(self.loss), _p(self.logits), *tail)
+        suffix, buf = self._loss_entry()                                    # the plain, criterion or focal instantiation
+        self._call("rd_head_train" + suffix, *common, _p(self.batch["y"]), *_spliced(buf), _p(self.loss), _p(self.logits), *tail)
 
     def set_criterion(self, class_weight=None, label_smoothing=0.0, focal_gamma=None):
         """Change the step's loss to CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing) between steps: a copy of
@@ -538,29 +555,24 @@ class Step:
         the kernels that read it; any other refuses (build a new step).
         A step built with focal_gamma takes `class_weight` and `focal_gamma` the same way (its buffer is [gamma, w_0 ..]); it
         refuses label_smoothing, and a call without focal_gamma; a step not built focal refuses focal_gamma."""
-        focal = getattr(self, "focal", None)
-        if focal is not None:
+        suffix, buf = self._loss_entry()
+        if suffix == "_focal":
             check_focal(label_smoothing, 0.0 if focal_gamma is None else focal_gamma)
             if focal_gamma is None:
                 raise _lib.RaindropHipError("set_criterion: this step was built for the focal loss (focal_gamma=...) and its captured "
                                             "head runs the focal kernels; pass focal_gamma=... (0.0 is the weighted cross entropy), "
                                             "or build a new step for another criterion")
             vals = focal_values(class_weight, focal_gamma, self.model.n_classes)
-            self._focal_vals = vals
-            focal.copy_(torch.tensor(vals, dtype=torch.float32))
-            return
-        if focal_gamma is not None:
+        elif focal_gamma is not None:
             raise _lib.RaindropHipError("set_criterion: this step was not built for the focal loss (focal_gamma=None) and its captured "
                                         "head reads no gamma; build the step with focal_gamma=... to change it between steps")
-        if self.crit is None:
+        elif buf is None:
             raise _lib.RaindropHipError("set_criterion: this step was built for the plain mean cross entropy (class_weight=None, "
                                         "label_smoothing=0) and its captured head reads no criterion buffer; build the step with "
                                         "class_weight=... or label_smoothing=... to change them between steps")
-        vals = criterion_values(class_weight, label_smoothing, self.model.n_classes)
-        if vals is None:
-            vals = [0.0] + [1.0] * self.model.n_classes
-        self._crit_vals = vals
-        self.crit.copy_(torch.tensor(vals, dtype=torch.float32))
+        else:
+            vals = criterion_values(class_weight, label_smoothing, self.model.n_classes) or [0.0] + [1.0] * self.model.n_classes
+        buf.copy_(torch.tensor(vals, dtype=torch.float32))
 
     def _head_fwd(self):
         """The head around a loss the caller evaluates (or none): up to self.logits."""
@@ -584,12 +596,8 @@ class Step:
         c = self._call
         self._head_forward_by_operator()
         # ---------------- loss: mean cross entropy (code/Raindrop.py:255,322) and its gradient ----------
-        if getattr(self, "focal", None) is not None:
-            c("rd_softmax_xent_focal", B, C, _p(self.logits), _p(b["y"]), _p(self.focal), _p(self.loss), _p(self.dlogits), st)
-        elif self.crit is not None:
-            c("rd_softmax_xent_crit", B, C, _p(self.logits), _p(b["y"]), _p(self.crit), _p(self.loss), _p(self.dlogits), st)
-        else:
-            c("rd_softmax_xent", B, C, _p(self.logits), _p(b["y"]), _p(self.loss), _p(self.dlogits), st)
+        suffix, buf = self._loss_entry()
+        c("rd_softmax_xent" + suffix, B, C, _p(self.logits), _p(b["y"]), *_spliced(buf), _p(self.loss), _p(self.dlogits), st)
         # ---------------- backward ----------------
         ws, wsn = _p(self.wg_ws), self.wg_ws.numel()
         c("rd_linear_bwd_weight", B, C, dh, _p(self.dlogits), C, _p(self.hid), dh, _p(G["mlp_static.2.weight"]),
@@ -826,8 +834,7 @@ class TrainStep(Step):
         def timed(r32, w16):
             _lib.call("rd_set_rowgemm_rows32", r32)
             _lib.call("rd_set_rowgemm_waves16", w16)
-            self._capture_one()
-            graphs = (self.graph, self.graph_b, self.graph_close, self.graph_b_close)   # (timed: the first two, a non-closing position)
+            graphs = self._capture_one()                             # (timed: the first two, a non-closing position)
 
             def replay():
                 graphs[0].replay()
@@ -859,46 +866,51 @@ class TrainStep(Step):
         _lib.call("rd_set_rowgemm_waves16", best_w16)
 
 
-    def _enqueue_whole(self, closing=True):
-        """the step as one piece: feed gather, body, the window's launch, feed record"""
-        self._feed_gather()
-        self._body()
-        self._window_tail(closing)
-        self._feed_record()
+    def _parts(self):
+        """the parts a micro-batch is enqueued in: the two halves of the split form -- 'a' ends where the gradients from
+        early_grad_offset() on are final --, else the step as one piece"""
+        return ("a", "b") if self.split else (None,)
 
-    def _enqueue_first(self, closing=True):
-        """the split form's first half: everything up to the point where the gradients from early_grad_offset() on are final"""
-        self._feed_gather()
-        self._body("a")
-        self._window_tail(closing, "a")
+    def _enqueue(self, closing=True, parts=None, after_part=None, opt=None):
+        """THE order of a micro-batch, for every form of the step: feed gather | per part: body, the window's launch, `after_part(part)`
+        (what a caller puts behind a part: `between`, a collective) | feed record.  `parts`: `_parts()`, or (None,): the step as one
+        piece whatever `split` says (the warm-up passes, capture_full's micro graph), or ONE of 'a', 'b': that half alone, for a
+        graph of its own -- the gather goes in front of 'a', the record behind 'b'.  `opt` (capture_full's closing pass): the
+        optimizer's update behind the last part, in front of the record; its step cell is registered from the gather to the first
+        body where the `begin` stage advances it (`_one_launch_begin`), else the update advances it itself."""
+        parts = self._parts() if parts is None else parts
+        if parts[0] != "b":
+            self._feed_gather()
+            if opt is not None and self._one_launch_begin():
+                opt.register_cell(True)
+        for k, part in enumerate(parts):
+            self._body(part)
+            if opt is not None and k == 0:
+                opt.register_cell(False)
+            self._window_tail(closing, part)
+            if after_part is not None:
+                after_part(part)
+        if parts[-1] != "a":
+            if opt is not None:
+                opt.step_captured(advance=not self._one_launch_begin())
+            self._feed_record()
 
-    def _enqueue_second(self, closing=True):
-        self._body("b")
-        self._window_tail(closing, "b")
-        self._feed_record()
+    def _warm(self, after_part=None):
+        """What every capture of the step warms up with, whatever it captures: the step as ONE piece (the split forms too), under
+        accumulation a non-closing position and then a closing one."""
+        if self.acc is not None:
+            self._enqueue(False, parts=(None,))
+        self._enqueue(True, parts=(None,), after_part=after_part)
 
     def _capture_one(self):
         """`graph` (+ `graph_b`, split form): the step.  With accumulate > 1 these are the graphs of a window's positions 0 .. k-2
-        and `graph_close` (+ `graph_b_close`) those of position k-1: the same body captured twice, out of one pool."""
-        whole, first, second = self._enqueue_whole, self._enqueue_first, self._enqueue_second
-        micro = lambda fn: (lambda: fn(False))
-
-        def both():                                                        # warm-up: one non-closing and one closing position
-            whole(False)
-            whole(True)
-
-        def cap():
-            self.graph_close = self.graph_b_close = None
-            if self.acc is not None and self.split:
-                self.graph, self.graph_b, self.graph_close, self.graph_b_close = capture_graphs(
-                    [micro(first), micro(second), first, second], warm=both)
-            elif self.acc is not None:
-                (self.graph, self.graph_close), self.graph_b = capture_graphs([micro(whole), whole], warm=both), None
-            elif self.split:
-                self.graph, self.graph_b = capture_graphs([first, second], warm=whole)
-            else:
-                (self.graph,), self.graph_b = capture_graphs([whole]), None
-        self._with_cell(cap)
+        and `graph_close` (+ `graph_b_close`) those of position k-1: the same body captured twice, out of one pool.  Returns the four."""
+        bodies = [lambda c=closing, p=part: self._enqueue(c, parts=(p,))
+                  for closing in ((False, True) if self.acc is not None else (True,)) for part in self._parts()]
+        graphs = self._with_cell(lambda: capture_graphs(bodies, warm=self._warm))
+        n, pair = len(self._parts()), lambda gs: (gs + [None, None])[:2]
+        self.graph, self.graph_b, self.graph_close, self.graph_b_close = pair(graphs[:n]) + pair(graphs[n:])
+        return self.graph, self.graph_b, self.graph_close, self.graph_b_close
 
     def capture_segments(self, parts=("begin", "k1f", "mid", "k1b")):
         """The same step as consecutive hipGraphs, one per part (measurement only: bench.py brackets the 'k1f' / 'k1b' replays with
@@ -980,16 +992,9 @@ class TrainStep(Step):
                     between()
                 second.replay()
         else:
-            def eager():
-                with torch.no_grad():
-                    if self.split:
-                        self._enqueue_first(closing)
-                        if between is not None:
-                            between()
-                        self._enqueue_second(closing)
-                    else:
-                        self._enqueue_whole(closing)
-            self._with_cell(eager)
+            after = None if between is None else (lambda part: between() if part == "a" else None)
+            with torch.no_grad():
+                self._with_cell(lambda: self._enqueue(closing, after_part=after))
         self._advance_window(closing)
         for p, v in zip(self.flat.params, self.flat.views):
             p.grad = v
@@ -1001,20 +1006,28 @@ class TrainStep(Step):
         rest of the backward pass; the remainder follows the second graph.  Returns the loss tensor.
         accumulate > 1: only the call that closes a window reduces (the window's mean; in the split form with the same overlap);
         on the other positions no collective is issued at all.  `window_closed` tells the caller which it was."""
-        flat = self.flat
         if not self._closing_next():
             return self.run()
-        if not self.split:
-            loss = self.run()
-            flat.allreduce()
-            return loss
-        off, hold = self.early_grad_offset(), []
-        loss = self.run(between=lambda: hold.append(flat.allreduce_range_async(off, flat.flat.numel())))
-        rest = flat.allreduce_range_async(0, off)
-        for h in hold:
-            flat.allreduce_wait(h)
-        flat.allreduce_wait(rest)
+        collective = self._collectives()
+        loss = self.run(between=lambda: collective("a"))
+        collective("b" if self.split else None)
         return loss
+
+    def _collectives(self):
+        """The gradient all-reduce of a closing pass as an `after_part` of `_enqueue`: behind the whole step flat.allreduce(); in the
+        split form [early_grad_offset(), n) started behind 'a', beside the rest of the backward pass, and [0, offset) behind 'b',
+        then both waited for, in that order."""
+        flat, started = self.flat, []
+
+        def after(part):
+            if part is None:
+                return flat.allreduce()
+            off = self.early_grad_offset()
+            started.append(flat.allreduce_range_async(off, flat.flat.numel()) if part == "a" else flat.allreduce_range_async(0, off))
+            if part == "b":
+                while started:
+                    flat.allreduce_wait(started.pop(0))
+        return after
 
 
     # ------------------------------------------------------------------------------------------
@@ -1033,52 +1046,19 @@ class TrainStep(Step):
         opt.sync_cells(full=True)                                          # the device step state and the cells of whatever the optimizer has on
         # the optimizer's device step state is advanced by the step's FIRST launch (rd_step_begin, next to the seed bump) where
         # the step has that launch -- registered for the capture only --, else by a one-thread launch in front of the update
-        begin_adv = self.plan is not None and (self.prep_enc or self.prep_k1) and self.one_begin
-
-        def warm():                                                        # outside the capture: RCCL's lazy inits, too
-            if self.acc is not None:
-                self._enqueue_whole(False)                                 # (a non-closing position and its launch)
-            self._feed_gather()
-            self._body()
-            self._window_tail(True)
-            flat.allreduce()
-            self._feed_record()
-
-        def whole():
-            self._feed_gather()
-            if begin_adv:
-                opt.register_cell(True)
-            if self.split:
-                off = self.early_grad_offset()
-                self._body("a")
-                opt.register_cell(False)
-                self._window_tail(True, "a")                               # the window's mean in the range the collective takes
-                h1 = flat.allreduce_range_async(off, flat.flat.numel())
-                self._body("b")
-                self._window_tail(True, "b")
-                h0 = flat.allreduce_range_async(0, off)
-                flat.allreduce_wait(h1)
-                flat.allreduce_wait(h0)
-            else:
-                self._body()
-                opt.register_cell(False)
-                self._window_tail(True)
-                flat.allreduce()
-            opt.step_captured(advance=not begin_adv)
-            self._feed_record()
+        # (`_enqueue`).  The warm-up runs a real flat.allreduce(): outside the capture, RCCL's lazy inits too.
+        # positions 0 .. k-2 (accumulate > 1): the step as one piece -- the optimizer's cell is not registered (its step state
+        # stays), no collective, no update
+        bodies = [lambda: self._enqueue(False, parts=(None,))] if self.acc is not None else []
+        bodies.append(lambda: self._enqueue(True, after_part=self._collectives(), opt=opt))
 
         def cap():
             try:
-                if self.acc is not None:
-                    # positions 0 .. k-2: feed gather, body, accumulate, feed record -- the optimizer's cell is not registered (its
-                    # step state stays), no collective, no update
-                    self.graph_full_micro, self.graph_full = capture_graphs([lambda: self._enqueue_whole(False), whole], warm=warm)
-                else:
-                    self.graph_full, = capture_graphs([whole], warm=warm)
+                return capture_graphs(bodies, warm=lambda: self._warm(lambda part: flat.allreduce()))
             finally:
                 opt.register_cell(False)
         with self._feed_kept():
-            self._with_cell(cap)
+            self.graph_full_micro, self.graph_full = ([None] + self._with_cell(cap))[-2:]
         opt.sync_step_cell()                                               # the warm-up did not step the optimizer; neither did the capture
         self._full_opt = opt
         self._full_hyper = opt.hyper()                                     # betas, eps are launch arguments: baked into the graph (lr, weight decay: device cell)

@@ -123,9 +123,11 @@ def flat_of(m, cfg, beta=False):
     return dp.FlatGradAllReduce([(n, named[n]) for n in names], n_buckets=2)
 
 
-def _train(rec, cfg, B, run=True, **kw):
+def _train(rec, cfg, B, run=True, coef_dropout=None, **kw):
     from raindrop_amd.step import TrainStep
     m, b = make(cfg, B)
+    if coef_dropout is not None:                                     # the attributes upstream users set
+        m.ob_propagation.dropout, m.ob_propagation_layer2.dropout = coef_dropout
     if kw.get("module_mode"):
         b = {k: v for k, v in b.items() if k != "y"}
     ts = TrainStep(m, flat_of(m, cfg), b, use_graph=False, autotune=False, **kw)
@@ -193,9 +195,11 @@ def form_full(rec, cfg, B):
     ts.close()
 
 
-def _beta(rec, cfg, B, lam):
+def _beta(rec, cfg, B, lam, coef_dropout=None):
     from raindrop_amd.step_beta import BetaTrainStep
     m, b = make(cfg, B, use_beta=True, compute_distance=True)
+    if coef_dropout is not None:
+        m.ob_propagation.dropout = coef_dropout
     ts = BetaTrainStep(m, flat_of(m, cfg, beta=True), b, use_graph=False, autotune=False, split=False, distance_weight=lam)
     rec.mark("plan=%d head_fused=%d" % (ts.plan is not None, ts.head_fused))
     ts.run()
@@ -234,12 +238,138 @@ def form_eval_beta_padded(rec, cfg, B):
     _eval(rec, cfg, B, False, use_beta=True)
 
 
+def _weights(cfg):
+    """class weights with one class at 0 (the criterion's denominator leaves its samples out)"""
+    return [0.0] + [1.0 + 0.5 * c for c in range(1, cfg["n_classes"])]
+
+
+def form_run_crit(rec, cfg, B):
+    _train(rec, cfg, B, split=False, class_weight=_weights(cfg), label_smoothing=0.1)
+
+
+def form_run_focal(rec, cfg, B):
+    _train(rec, cfg, B, split=False, class_weight=_weights(cfg), focal_gamma=2.0)
+
+
+def form_run_crit_head_by_operator(rec, cfg, B):
+    with environ(RD_HEAD_FUSED="0"):
+        form_run_crit(rec, cfg, B)
+
+
+def form_run_focal_head_by_operator(rec, cfg, B):
+    with environ(RD_HEAD_FUSED="0"):
+        form_run_focal(rec, cfg, B)
+
+
+def _runs(rec, ts, n):
+    """n more micro-batches of an accumulating step, a mark in front of each"""
+    for k in range(n):
+        rec.mark("position=%d" % ts.window_position())
+        ts.run(between=lambda: rec.mark("between"))
+
+
+def form_run_accum(rec, cfg, B):
+    _runs(rec, _train(rec, cfg, B, split=False, accumulate=3), 2)          # two micro positions and the close
+
+
+def form_run_accum_split(rec, cfg, B):
+    _runs(rec, _train(rec, cfg, B, split=True, accumulate=2), 1)
+
+
+def _graph(rec, cfg, B, **kw):
+    """construction with use_graph=True (warm-up + capture), then one replay"""
+    from raindrop_amd.step import TrainStep
+    m, b = make(cfg, B)
+    ts = TrainStep(m, flat_of(m, cfg), b, use_graph=True, autotune=False, **kw)
+    rec.mark("captured split=%d" % ts.split)
+    ts.run(between=lambda: rec.mark("between"))
+    ts.close()
+
+
+def form_graph(rec, cfg, B):
+    _graph(rec, cfg, B, split=False)
+
+
+def form_graph_split(rec, cfg, B):
+    _graph(rec, cfg, B, split=True)
+
+
+def form_graph_accum(rec, cfg, B):
+    _graph(rec, cfg, B, split=False, accumulate=2)
+
+
+def form_graph_accum_split(rec, cfg, B):
+    _graph(rec, cfg, B, split=True, accumulate=2)
+
+
+def _full(rec, cfg, B, replays, **kw):
+    from raindrop_amd.optim import FlatAdam
+    from raindrop_amd.step import TrainStep
+    m, b = make(cfg, B)
+    flat = flat_of(m, cfg)
+    opt = FlatAdam(flat.flatten_parameters(), lr=1e-3)
+    ts = TrainStep(m, flat, b, use_graph=False, autotune=False, **kw)
+    ts.capture_full(opt)
+    rec.mark("captured split=%d" % ts.split)
+    for _ in range(replays):
+        ts.run_full()
+    ts.close()
+
+
+def form_full_split(rec, cfg, B):
+    _full(rec, cfg, B, 1, split=True)
+
+
+def form_full_accum(rec, cfg, B):
+    _full(rec, cfg, B, 2, split=False, accumulate=2)
+
+
+def form_full_accum_split(rec, cfg, B):
+    _full(rec, cfg, B, 2, split=True, accumulate=2)
+
+
+def _feed(cfg, B):
+    """an epoch feed over the smallest dataset that gives two batches, its plan loaded"""
+    import numpy as np
+    from raindrop_amd import feed
+    data = synth.make_batch(cfg, 2 * B, seed=43)
+    ds = feed.DeviceDataset(data["src"], data["times"], data["static"], data["y"], device=DEV)
+    fd = feed.EpochFeed(ds, B, capacity=2)
+    fd.load_epoch([np.arange(B), np.arange(B, 2 * B)])
+    return fd
+
+
+def form_run_feed(rec, cfg, B):
+    _train(rec, cfg, B, split=False, feed=_feed(cfg, B))
+
+
+def form_full_feed(rec, cfg, B):
+    _full(rec, cfg, B, 1, split=False, feed=_feed(cfg, B))
+
+
+def form_run_coef_dropout(rec, cfg, B):
+    _train(rec, cfg, B, split=False, coef_dropout=(0.25, 0.125))
+
+
+def form_beta_coef_dropout(rec, cfg, B):
+    _beta(rec, cfg, B, 0.0, coef_dropout=0.25)
+
+
 FORMS = {"run": form_run, "run_split": form_run_split, "run_padded": form_run_padded, "run_no_dropout": form_run_no_dropout,
          "run_head_by_operator": form_run_head_by_operator, "segments": form_segments, "segments_module": form_segments_module,
          "marked": form_marked, "full": form_full, "beta": form_beta, "beta_distance": form_beta_distance, "eval": form_eval,
-         "eval_padded": form_eval_padded, "eval_beta": form_eval_beta, "eval_beta_padded": form_eval_beta_padded}
+         "eval_padded": form_eval_padded, "eval_beta": form_eval_beta, "eval_beta_padded": form_eval_beta_padded,
+         # the forms the features since the restructuring into stages added (recorded from the last commit that restated the
+         # step's order per form)
+         "run_crit": form_run_crit, "run_focal": form_run_focal, "run_crit_head_by_operator": form_run_crit_head_by_operator,
+         "run_focal_head_by_operator": form_run_focal_head_by_operator, "run_accum": form_run_accum,
+         "run_accum_split": form_run_accum_split, "graph": form_graph, "graph_split": form_graph_split,
+         "graph_accum": form_graph_accum, "graph_accum_split": form_graph_accum_split, "full_split": form_full_split,
+         "full_accum": form_full_accum, "full_accum_split": form_full_accum_split, "run_feed": form_run_feed,
+         "full_feed": form_full_feed, "run_coef_dropout": form_run_coef_dropout, "beta_coef_dropout": form_beta_coef_dropout}
 # the captures on the two P19 configurations only (what bench.py and graph_module capture); every enqueued form on every width
-CAPTURES = ("segments", "segments_module", "marked", "full")
+CAPTURES = ("segments", "segments_module", "marked", "full", "graph", "graph_split", "graph_accum", "graph_accum_split", "full_split",
+            "full_accum", "full_accum_split", "full_feed")
 
 
 def cases():

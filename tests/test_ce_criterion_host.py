@@ -137,7 +137,7 @@ def _bare_step(fused, crit, monkeypatch):
     s.x, s.dx, s.mask = [z(T, B, D)] * 3, [z(T, B, D), z(T, B, D)], z(B, T)
     s.feat, s.dfeat, s.hid, s.dhid, s.logits, s.dlogits = z(B, D), z(B, D), z(B, D), z(B, D), z(B, C), z(B, C)
     s.loss, s.wg_ws, s.head_ws = z(()), torch.zeros(64, dtype=torch.uint8), torch.zeros(64, dtype=torch.uint8)
-    s.head_fused, s.crit = fused, crit
+    s.head_fused, s.crit, s.focal = fused, crit, None
     s.calls = []
     s._call = lambda name, *a: s.calls.append((name, a))
     return s
